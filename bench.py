@@ -9,10 +9,15 @@ k_pip_exact over the candidate lists it left; its first blocks locate the few po
 Workload (N=1): BASELINE.json configs[1], USCounty (base, 7.1 M segments) |><| BlockGroup
 (query, 28.8 M segments), as synthetic stand-ins of those sizes (the real files are
 not obtainable).  Inputs are resident in HBM before the timed region.  Index build is timed
-separately and reported, never part of `value`.  The default single-GPU run also times four
-harder pairs (fewer steps) -- USCounty |><| NestedBlockGroup (shared vertices, 11x the
-intersections), WaterBodies |><| BlockGroup (BASELINE config 5's maps), a lake-shaped base map and a
-query map with the published intersection density -- so the best-case lattice is never the only number.
+separately and reported, never part of `value`.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it sets up, warms up,
+times the K steps, writes the last timed step's results when `--dump-outputs DIR` is given, and prints the line.
+`--full` adds everything else: the pipelined and caller-array forms of the step, each kernel alone, the rooflines,
+the result digest, the CPU baseline, the --detail file and, on the default single-GPU workload, four harder pairs
+(fewer steps) -- USCounty |><| NestedBlockGroup (shared vertices, 11x the intersections), WaterBodies |><| BlockGroup
+(BASELINE config 5's maps), a lake-shaped base map and a query map with the published intersection density -- so the
+best-case lattice is never the only number.
 
 N>1 (`python bench.py --gpus N` starts its own N ranks; under a launcher -- torch.distributed.run
 --nproc-per-node N bench.py [--gpus N] -- it is one of them, one rank per GPU): the query map is sharded by contiguous chain ranges balanced
@@ -23,9 +28,9 @@ overlapped with the PIP kernels) and the all-gather of the PIP result queues (cl
 complete inside the timed region).  `ms_per_step_pairs_only` times the same steps without the PIP
 gather.  Total work is fixed: "strong" scaling.
 
-Prints ONE JSON line on rank 0's stdout: the headline, under 6 000 bytes (contract fields, config, flat
-rooflines, cpu_baseline, one short entry per secondary pair).  Each secondary pair's compact line goes
-to stderr before it, the full record (plan, checks, instruction rooflines ...) to the --detail file.
+Prints ONE JSON line on rank 0's stdout: the headline, under 6 000 bytes (contract fields, config; with --full also
+flat rooflines, cpu_baseline, one short entry per secondary pair).  Under --full each secondary pair's compact line
+goes to stderr before it, the full record (plan, checks, instruction rooflines ...) to the --detail file.
 """
 import argparse
 import gc
@@ -83,7 +88,23 @@ def parse():
                          "the checks, the instruction rooflines): stdout carries the compact headline only")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="N>1 rehearsal on a 1-GPU box: every rank uses cuda:0, collectives over gloo")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: pipelined and caller-array steps, kernels alone, rooflines, digest, "
+                         "CPU baseline, secondary pairs and the --detail file (a plain run times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's results to DIR/<name>.npy (float64; N = 1 only)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus or int(os.environ.get("WORLD_SIZE", "1"))) > 1:
+        ap.error("--dump-outputs needs a single-GPU run")
+    if not args.full:
+        idle = [o for o, given in (("--detail", args.detail != ap.get_default("detail")), ("--no-secondary", args.no_secondary),
+                                   ("--no-cpu-baseline", args.no_cpu_baseline)) if given]
+        if idle:
+            print("bench.py: %s act only with --full: a plain run times the headline's steps alone and writes no detail file"
+                  % ", ".join(idle), file=sys.stderr)
+    return args
 
 
 def cpu_baseline(args, ctx, base_name, query_name):
@@ -132,11 +153,58 @@ def cpu_baseline(args, ctx, base_name, query_name):
     }
 
 
+DUMP_MAX_PAIRS = 1 << 18    # intersections written in full up to this many, else a seeded sample of the sorted ones
+DUMP_POINTS = 1 << 20       # PIP results: a seeded sample of this many query points (the whole set is 29.7 M)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(path, torch, n, cap, pairs, xsects, closest, faces, n_pts):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files (every value below 2^53: exact),
+    in an order that does not depend on the run -- the LSI queue is filled in no fixed order, so its pairs and their
+    48-byte records are sorted by (map-0 eid, map-1 eid).  Inputs are seeded, so two builds can be compared file by file:
+      lsi_count          [1]     intersections found
+      lsi_pairs          [m, 2]  (map-0 eid, map-1 eid), sorted
+      lsi_records        [m, 7]  x_num, x_den, y_num, y_den, eid0, eid1, mid_point_polygon_id (rj_xsect), same order
+      lsi_pair_index     [m]     position of each written pair in the sorted list (all of them up to DUMP_MAX_PAIRS)
+      pip_point_index    [k]     the sampled query points (seeded, sorted)
+      pip_closest_eids   [k]     closest map-0 eid above each (4294967295 = none)
+      pip_face_ids       [k]     its face id"""
+    os.makedirs(path, exist_ok=True)
+    m = min(int(n), cap)
+    pr = pairs[:m].to(torch.int64) & 0xFFFFFFFF
+    order = torch.argsort((pr[:, 0] - (1 << 31)) * (1 << 32) + pr[:, 1])   # (offset: the key of any two 32-bit eids fits int64)
+    rec = xsects[:m][order]
+    pr = pr[order]
+    sel = np.arange(m)
+    if m > DUMP_MAX_PAIRS:
+        sel = np.sort(np.random.default_rng(DUMP_SEED).choice(m, DUMP_MAX_PAIRS, replace=False))
+    sel_d = torch.from_numpy(sel).to(pr.device)
+    pr, rec = pr[sel_d], rec[sel_d]
+    rec = torch.stack([rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3], rec[:, 4] & 0xFFFFFFFF, (rec[:, 4] >> 32) & 0xFFFFFFFF,
+                       (rec[:, 5] & 0xFFFFFFFF).to(torch.int32).to(torch.int64)], dim=1)
+    k = min(DUMP_POINTS, n_pts)
+    idx = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(n_pts, k, replace=False)) if k < n_pts else np.arange(n_pts)
+    idx_d = torch.from_numpy(idx).to(closest.device)
+    arrays = {
+        "lsi_count": np.array([n], dtype=np.float64),
+        "lsi_pairs": pr.cpu().numpy().astype(np.float64),
+        "lsi_records": rec.cpu().numpy().astype(np.float64),
+        "lsi_pair_index": sel.astype(np.float64),
+        "pip_point_index": idx.astype(np.float64),
+        "pip_closest_eids": (closest[:n_pts][idx_d].to(torch.int64) & 0xFFFFFFFF).cpu().numpy().astype(np.float64),
+        "pip_face_ids": faces[:n_pts][idx_d].cpu().numpy().astype(np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 DEBUG_PHASES = bool(os.environ.get("RJ_BENCH_STEP_TIMES"))
 
 
-def run_workload(args, env, base_name, query_name, steps, warmup, headline, with_cpu):
-    """Times `steps` steps of base |><| query on this rank's shard; rank 0 returns the line (a dict)."""
+def run_workload(args, env, base_name, query_name, steps, warmup, headline, with_cpu, full=True, dump_dir=None):
+    """Times `steps` steps of base |><| query on this rank's shard; rank 0 returns the line (a dict).  full=False: the
+    timed steps and the headline's fields only (N > 1 still times its pipelined steps: they are its headline).
+    dump_dir: where the last timed step's results go (dump_outputs), None = nowhere."""
     torch, dist, dev, world, rank, local_rank = env
     from rayjoin_amd import _capi, maps, synth
     from rayjoin_amd import dist as rjd
@@ -408,8 +476,11 @@ def run_workload(args, env, base_name, query_name, steps, warmup, headline, with
     settled = args.serial_kernels or never_paired or h.get_option("pip_schedule") >= 0
     elapsed = timed(steps)
     ms_per_step = elapsed * 1e3 / steps
+    if dump_dir and rank == 0 and world == 1:
+        # (the last timed step's results, before anything below runs another query into the same buffers)
+        dump_outputs(dump_dir, torch, state["n"], cap, state["last_pairs"], xsects, state["closest"], faces, p1 - p0)
     ms_synced = ms_pipelined = None
-    if settled and steps >= 2:
+    if settled and steps >= 2 and (full or world > 1):
         el_p = timed_pipelined(steps)
         ms_pipelined = el_p * 1e3 / steps
         if world > 1:
@@ -424,7 +495,7 @@ def run_workload(args, env, base_name, query_name, steps, warmup, headline, with
     state["two_pass"] = state["two_pass"] and h.get_option("pip_last_passes") == 3
     lsi_k = float(np.mean(lsi_ms)); pip_k = float(np.mean(pip_ms)); walk_k = float(np.mean(walk_ms)) if (walk_ms and state["two_pass"]) else None
     ms_pairs_only = None
-    if gather_pip:
+    if gather_pip and full:
         ms_pairs_only = (timed_pipelined if ms_synced is not None else timed)(steps, with_gather=False) * 1e3 / steps
     if world > 1:
         tot = torch.tensor([state["n"]], dtype=torch.int64, device=dev)
@@ -465,9 +536,9 @@ def run_workload(args, env, base_name, query_name, steps, warmup, headline, with
                 dist.all_reduce(v)
         names = ("pairs", "points_xy", "pip_hits", "pip_eids", "pip_faces")
         return {k: int(x) for k, x in zip(names, v.tolist())}
-    result_digest = digest()
+    result_digest = digest() if full else None
     gathered_ok = None
-    if gather_pip and state.get("ids_all") is not None:
+    if full and gather_pip and state.get("ids_all") is not None:
         # every rank now holds every shard's queue: this rank's slice of the gathered buffer is its own result
         gathered_ok = bool(torch.equal(state["ids_all"][rank, :p1 - p0], closest[:p1 - p0]))
 
@@ -476,7 +547,7 @@ def run_workload(args, env, base_name, query_name, steps, warmup, headline, with
     # this rank's vertices.  After its first query the handle enqueues such a query without a host round trip and pairs
     # it with the LSI query in flight like a map-owned range; the results must be the map-owned ones.
     caller = None
-    if world == 1 and p1 > p0:
+    if full and world == 1 and p1 > p0:
         own = closest[:p1 - p0].clone()
         cpts = torch.from_numpy(np.ascontiguousarray(query.pts[p0:p1])).to(dev)
         state["caller_pts"] = cpts
@@ -497,27 +568,31 @@ def run_workload(args, env, base_name, query_name, steps, warmup, headline, with
         h.set_option("timers", 1)  # (an unsampled step switches the stage timers off: what follows reads them)
         state["timers_on"] = True
 
-    # phase split (synchronous calls, wall clock), one extra untimed pass
-    t0 = time.perf_counter(); h.lsi_query(0, 1, e0, e1, cap, pairs); t_lsi_wall = time.perf_counter() - t0
-    t0 = time.perf_counter(); h.pip_query(0, 1, None, p0, p1 - p0, closest, faces); t_pip_wall = time.perf_counter() - t0
-    # each kernel with the chip to itself (synchronous queries), median of three
-    alone = {"lsi": [], "pip": [], "walk": []}
-    for _ in range(3):
-        h.lsi_query(0, 1, e0, e1, cap, pairs); alone["lsi"].append(h.last_ms(_capi.RJ_T_LSI_KERNEL))
-        h.pip_query(0, 1, None, p0, p1 - p0, closest, faces); alone["pip"].append(h.last_ms(_capi.RJ_T_PIP_KERNEL))
-        if state["two_pass"]:
-            alone["walk"].append(h.last_ms(_capi.RJ_T_PIP_WALK))
-    lsi_alone_ms, pip_alone_ms = float(np.median(alone["lsi"])), float(np.median(alone["pip"]))
-    walk_alone_ms = float(np.median(alone["walk"])) if alone["walk"] else None
+    t_lsi_wall = t_pip_wall = None
+    if full:
+        # phase split (synchronous calls, wall clock), one extra untimed pass
+        t0 = time.perf_counter(); h.lsi_query(0, 1, e0, e1, cap, pairs); t_lsi_wall = time.perf_counter() - t0
+        t0 = time.perf_counter(); h.pip_query(0, 1, None, p0, p1 - p0, closest, faces); t_pip_wall = time.perf_counter() - t0
+        # each kernel with the chip to itself (synchronous queries), median of three
+        alone = {"lsi": [], "pip": [], "walk": []}
+        for _ in range(3):
+            h.lsi_query(0, 1, e0, e1, cap, pairs); alone["lsi"].append(h.last_ms(_capi.RJ_T_LSI_KERNEL))
+            h.pip_query(0, 1, None, p0, p1 - p0, closest, faces); alone["pip"].append(h.last_ms(_capi.RJ_T_PIP_KERNEL))
+            if state["two_pass"]:
+                alone["walk"].append(h.last_ms(_capi.RJ_T_PIP_WALK))
+        lsi_alone_ms, pip_alone_ms = float(np.median(alone["lsi"])), float(np.median(alone["pip"]))
+        walk_alone_ms = float(np.median(alone["walk"])) if alone["walk"] else None
 
     checks = None
     if args.check and rank == 0 and world == 1 and headline:
         checks = run_checks(h, torch, dev, n_x, cap, state.get("last_pairs", pairs), closest, faces, query, e0, e1)
 
     out = None
-    if rank == 0:
+    n_s_loc, n_p_loc = e1 - e0, p1 - p0
+    # (a base map of isolated rings has a column index: the first pass reads the point's strip instead of walking the tree)
+    walk_name = "k_pip_strip" if state.get("columns") else ("k_pip_walk2" if state["walk_points"] == 2 else "k_pip_walk")
+    if rank == 0 and full:
         # ALGORITHMIC bytes: every input element once, every output once
-        n_s_loc, n_p_loc = e1 - e0, p1 - p0
         b_lsi = 32 * n_s_loc + 32 * n_r + 8 * state["n"]
         b_pip = 16 * n_p_loc + 32 * n_r + 4 * n_p_loc + 4 * n_p_loc  # + face ids
         # PMC evidence (tools/profile_run.sh + tools/pmc_summary.py): quoted only for the headline
@@ -542,8 +617,6 @@ def run_workload(args, env, base_name, query_name, steps, warmup, headline, with
             elif sec:  # (another pair with a section of its own: the ring-shaped ones)
                 traffic, sq, prof_note = sec.get("traffic", {}), sec.get("sq", {}), "profiles/%s_pmc_sections.csv, section %s_%s (each kernel alone on its full grid)" % (doc.get("tag"), base_name, query_name)
                 fetch_cal = doc.get("fetch_calibration")
-        # (a base map of isolated rings has a column index: the first pass reads the point's strip instead of walking the tree)
-        walk_name = "k_pip_strip" if state.get("columns") else ("k_pip_walk2" if state["walk_points"] == 2 else "k_pip_walk")
         pip_kernel = walk_name if state["two_pass"] else "k_pip"
         # (the kernel the handle's plan names: k_lsi2 / k_lsi, or -- a tree without a second order of its steep blocks: maps of closed
         #  rings -- k_lsi2x / k_lsix, the same bodies with nothing of that order left in them)
@@ -640,6 +713,7 @@ def run_workload(args, env, base_name, query_name, steps, warmup, headline, with
             roof["pip"]["query_ms_alone"] = round(pip_alone_ms, 4)
         dom = "lsi" if lsi_k >= pip_k else "pip"
         b_step = b_lsi + b_pip + 56 * state["n"]  # + the 48-byte records and the pairs read back for them
+    if rank == 0:
         sharding = "single GPU"
         if world > 1:
             sharding = ("query map by chain range x%d, base+LBVH replicated, RCCL all-gather-v of LSI pairs (overlapped with the PIP kernels)%s"
@@ -667,30 +741,34 @@ def run_workload(args, env, base_name, query_name, steps, warmup, headline, with
                        "schedule_settled_before_timing": bool(settled),
                        "pip_passes": ("%s + k_pip_exact (its first blocks locate the %s points whose candidate list overflowed)" % (walk_name, pip_rest)) if state["two_pass"]
                                      else "k_pip alone" + (" (the walk left %s lists to it: auto dropped the first pass)" % pip_rest if h.get_option("pip_walk") else "")},
-            "lsi_ms": round(t_lsi_wall * 1e3, 4), "pip_ms": round(t_pip_wall * 1e3, 4),
-            "lsi_msegs_per_s": round(n_s_loc * world / max(t_lsi_wall, 1e-9) / 1e6, 2) if world == 1 else None,
-            "pip_mpoints_per_s": round(n_p / max(t_pip_wall, 1e-9) / 1e6, 2) if world == 1 else None,
-            "lsi_points_ms": round(float(np.mean(pts_ms)), 4), "result_digest": result_digest,
             "intersections": n_x, "intersections_per_query_segment": round(n_x / max(1, n_s), 5), "build_index_ms": round(first_build_ms, 3), "build_index_wall_ms": round(first_build_wall_ms, 3),
             "build_index_runs_ms": round(build_runs_ms, 3), "rebuild_index_ms": round(build_ms, 3),
-            "pip_caller_array": caller,
             "index_leaves": "polyline runs" if h.get_option("leaf_order_used0") == 1 else "Hilbert neighbours",
             "index_slots_per_segment": round(h.get_option("leaf_slots0") / max(1, n_r), 3),
             "index_extras": {"skyline": bool(h.get_option("skyline_used0")), "pip_columns": bool(h.get_option("pip_columns_used0")),
                              "closed_chains": h.get_option("closed_chains0")},
             "host_ms": {"generate": round(t_gen * 1e3, 1), "upload_and_segment_build": round(t_upload * 1e3, 1)},
-            "roofline": roof[dom], "roofline_other": roof["pip" if dom == "lsi" else "lsi"],
-            # the whole step against the same roofline: all algorithmic bytes of the step over the step's time
-            "roofline_step": {"bound": "hbm", "achieved": round(b_step / (ms_per_step * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                              "frac": round(b_step / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5), "algorithmic_bytes": b_step},
         }
+        if full:
+            out.update({
+                "lsi_ms": round(t_lsi_wall * 1e3, 4), "pip_ms": round(t_pip_wall * 1e3, 4),
+                "lsi_msegs_per_s": round(n_s_loc * world / max(t_lsi_wall, 1e-9) / 1e6, 2) if world == 1 else None,
+                "pip_mpoints_per_s": round(n_p / max(t_pip_wall, 1e-9) / 1e6, 2) if world == 1 else None,
+                "lsi_points_ms": round(float(np.mean(pts_ms)), 4), "result_digest": result_digest,
+                "pip_caller_array": caller,
+                "roofline": roof[dom], "roofline_other": roof["pip" if dom == "lsi" else "lsi"],
+                # the whole step against the same roofline: all algorithmic bytes of the step over the step's time
+                "roofline_step": {"bound": "hbm", "achieved": round(b_step / (ms_per_step * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                  "frac": round(b_step / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5), "algorithmic_bytes": b_step},
+            })
         if ms_pipelined is not None:
             out["ms_per_step_pipelined"] = round(ms_pipelined, 4)  # step j + 1 launched before step j's count / heads are read
         if ms_synced is not None:
             out["ms_per_step_synced"] = round(ms_synced, 4)        # every step ending in the host's read of the gathered heads
         out["pipelined"] = ms_synced is not None
         # the ranks that ran: the launcher's count, and -- on the native transport -- what RCCL counts in the handle's communicator
-        out["plan"] = state.get("plan")  # rj_get_plan right after the timed steps: kernels, grids, schedule, and why
+        if full:
+            out["plan"] = state.get("plan")  # rj_get_plan right after the timed steps: kernels, grids, schedule, and why
         out["ranks"] = {"world_size": world, "rccl_comm_ranks": h.get_option("comm_ranks") or None,
                         "transport": ("gloo (one-GPU rehearsal: every rank on cuda:0)" if args.rehearse_one_gpu else "rccl") if world > 1 else None}
         if world > 1 and not args.rehearse_one_gpu and out["ranks"]["rccl_comm_ranks"] != world:
@@ -779,7 +857,12 @@ def headline(out, sec, written):
 
 
 def emit(out, sec, detail_path):
-    """rank 0: the full record to `detail_path`, each secondary pair's compact line to stderr, the headline to stdout -- last"""
+    """rank 0: the full record to `detail_path` (None: no file, a plain run), each secondary pair's compact line to stderr,
+    the headline to stdout -- last"""
+    if detail_path is None:
+        print(json.dumps(compact(out)))
+        sys.stdout.flush()
+        return
     written = None
     try:
         os.makedirs(os.path.dirname(os.path.abspath(detail_path)), exist_ok=True)
@@ -810,6 +893,21 @@ def launch_ranks(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # (dmabuf IPC: RCCL across processes needs it on this driver)
     env.setdefault("OMP_NUM_THREADS", "1")
     return subprocess.call(cmd, env=env)
+
+
+def run_pairs(args, env):
+    """the headline workload -- the only one whose results --dump-outputs writes -- then, on the default single-GPU run
+    under --full, the harder pairs (each adds a few seconds); -> (headline line, [secondary lines])"""
+    torch, world = env[0], env[3]
+    with_cpu = args.full and world == 1 and not args.no_cpu_baseline
+    out = run_workload(args, env, args.base, args.query, args.steps, args.warmup, True, with_cpu, args.full, dump_dir=args.dump_outputs)
+    default_run = world == 1 and not args.emulate_shard and args.scale == 1.0 and (args.base, args.query) == ("USCounty", "BlockGroup")
+    sec = []
+    if args.full and default_run and not args.no_secondary:
+        for b, q in SECONDARY:
+            torch.cuda.empty_cache()
+            sec.append(run_workload(args, env, b, q, max(5, min(args.steps, 10)), max(5, args.warmup), False, with_cpu, True, dump_dir=None))
+    return out, sec
 
 
 def main():
@@ -845,17 +943,9 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
     env = (torch, dist, dev, world, rank, local_rank)
 
-    with_cpu = world == 1 and not args.no_cpu_baseline
-    out = run_workload(args, env, args.base, args.query, args.steps, args.warmup, True, with_cpu)
-    # the harder pairs, in the same line: only on the default single-GPU run (each adds a few seconds)
-    default_run = world == 1 and not args.emulate_shard and args.scale == 1.0 and (args.base, args.query) == ("USCounty", "BlockGroup")
-    sec = []
-    if default_run and not args.no_secondary:
-        for b, q in SECONDARY:
-            torch.cuda.empty_cache()
-            sec.append(run_workload(args, env, b, q, max(5, min(args.steps, 10)), max(5, args.warmup), False, with_cpu))
+    out, sec = run_pairs(args, env)
     if rank == 0:
-        emit(out, sec, args.detail)
+        emit(out, sec, args.detail if args.full else None)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

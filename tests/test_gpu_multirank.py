@@ -24,7 +24,7 @@ def _free_port():
 
 
 def _bench(nproc, extra=(), plain=False):
-    common = ["bench.py", "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--scale", "0.12", "--no-cpu-baseline"]
+    common = ["bench.py", "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--scale", "0.12", "--no-cpu-baseline", "--full"]
     if plain:  # the driver's single-GPU form with N > 1: bench.py starts its own ranks (a child torch.distributed.run)
         cmd = [sys.executable] + common + ["--rehearse-one-gpu"]
     elif nproc > 1:

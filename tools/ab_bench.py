@@ -14,7 +14,7 @@ res = [{k: [] for k in keys}, {k: [] for k in keys}]
 for r in range(rounds):
     for i, lib in enumerate(libs):
         env = dict(os.environ, RAYJOIN_AMD_LIB=lib)
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-secondary", "--no-cpu-baseline"] + extra,
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-secondary", "--no-cpu-baseline"] + extra,
                              env=env, capture_output=True, text=True, timeout=900)
         line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
         if not line:

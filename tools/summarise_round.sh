@@ -1,7 +1,7 @@
 #!/bin/bash
-# After tools/profile_run.sh <tag> ran on the GPU box and gpurun_out/ came back: everything profiles/<tag>_* that is made HERE
+# After tools/profile_run.sh <tag> ran on the GPU box and its runs/ (or $RJ_OUT) came back: everything profiles/<tag>_* that is made HERE
 # (counter summaries with their sections, copies of the trace tables), in one go.  usage: tools/summarise_round.sh r05
-TAG=${1:?tag}; G=gpurun_out
+TAG=${1:?tag}; G=${RJ_OUT:-runs}
 R=$(cd "$(dirname "$0")/.." && pwd); cd $R
 SEC=""
 for s in shared WaterBodiesLike_BlockGroup LakesLike_ParksLike USCounty_NestedBlockGroup WaterBodies_BlockGroup USCounty_CrossingZipcode; do
