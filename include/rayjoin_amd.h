@@ -258,6 +258,31 @@ int rj_allgather_u32(rj_handle h, const uint32_t* src_dev, uint64_t n_local, uin
 int rj_overlay_edge_xsects(rj_handle h, int im, const uint32_t* pairs_dev, uint64_t n,
                            rj_xsect* xsects_dev);
 
+/* One row of the overlay's face table: a face of map 0 and a face of map 1 that overlap, and twice the signed area of
+ * their overlap in scaled units^2 (exact: a two's-complement int128, value = area2_hi * 2^64 + area2_lo). */
+typedef struct {
+  int32_t face[2];   /* face of map 0, face of map 1; both != RJ_EXTERIOR_FACE_ID */
+  uint64_t area2_lo;
+  int64_t area2_hi;
+} rj_overlay_face;   /* 24 bytes */
+
+/* extends: WriteOutputChain (src/app/output_chain.h:42-205) -- what a caller of the overlay wants from the output map,
+ * computed on the device instead of written as text.  The pieces are the output map's (every chain cut at its records,
+ * each piece labelled with the face of the other map it lies in); every consecutive point pair a -> b of a kept piece
+ * adds cross(a, b) to (the chain's left face, the piece's other face) and -cross(a, b) to (right face, other face), a
+ * side with face 0 adding nothing.  Rows (face of map 0, face of map 1) with at least one contribution, ascending by
+ * ((uint64)(uint32)face[0] << 32) | (uint32)face[1].  On maps in general position every area2 is positive; where the
+ * maps share boundary the table inherits the output map's labels, like the CDB file.  The unordered pairs {min, max} of
+ * the rows are the output map's faces (its "Total faces").  Face ids are nonnegative.
+ * xsectsK_dev: the n records of rj_overlay_edge_xsects(h, K, ...) (both from the same pairs, LBVH or grid);
+ * vertex_faceK_dev: face_id_dev of rj_pip_query(h, 1 - K, K, NULL, 0, np_K, ...) (or rj_pip_query_grid) -- the face in
+ * the other map of every vertex of map K.  n == 0 is valid (disjoint maps, a map inside one face of the other).
+ * out_dev[capacity] is caller-owned device memory; RJ_E_OVERFLOW when there are more rows: *n_faces holds the true count
+ * and nothing beyond capacity is written.  One host sync, at the end, to read the count. */
+int rj_overlay_faces(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                     const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev,
+                     uint64_t capacity, rj_overlay_face* out_dev, uint64_t* n_faces);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

@@ -20,6 +20,8 @@ MISS_EID = 0xFFFFFFFF
 XSECT_DTYPE = np.dtype(
     [("x_num", "<i8"), ("x_den", "<i8"), ("y_num", "<i8"), ("y_den", "<i8"),
      ("eid", "<u4", (2,)), ("mid_point_polygon_id", "<i4"), ("_pad", "<i4")])
+# rj_overlay_face: (face of map 0, face of map 1), twice the overlap's signed area as a two's-complement int128
+FACE_DTYPE = np.dtype([("face", "<i4", (2,)), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
 _vp, _u64, _i64, _int = C.c_void_p, C.c_uint64, C.c_int64, C.c_int
@@ -61,6 +63,7 @@ SYMBOLS = {
     "rj_exchange_verdict": (_int, [_vp, _vp, _int, C.POINTER(_u64), C.POINTER(_int)]),
     "rj_last_ms_all": (_int, [_vp, _vp, _int]),
     "rj_overlay_edge_xsects": (_int, [_vp, _int, _vp, _u64, _vp]),
+    "rj_overlay_faces": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -413,6 +416,16 @@ class Handle:
 
     def overlay_edge_xsects(self, im, pairs_dev, n, xsects_dev):
         self._check(self.L.rj_overlay_edge_xsects(self.h, im, _ptr(pairs_dev), n, _ptr(xsects_dev)))
+
+    def overlay_faces(self, xsects0_dev, xsects1_dev, n, vertex_face0_dev, vertex_face1_dev, capacity, out_dev):
+        """rows of the face table into out_dev (FACE_DTYPE); returns the row count, QueueOverflow past capacity"""
+        nf = _u64()
+        rc = self.L.rj_overlay_faces(self.h, _ptr(xsects0_dev), _ptr(xsects1_dev), n, _ptr(vertex_face0_dev),
+                                     _ptr(vertex_face1_dev), capacity, _ptr(out_dev), C.byref(nf))
+        if rc == RJ_E_OVERFLOW:
+            raise QueueOverflow(self.L.rj_last_error_string(self.h).decode(), nf.value)
+        self._check(rc)
+        return nf.value
 
     def sort_pairs(self, pairs_dev, n):
         self._check(self.L.rj_sort_pairs(self.h, _ptr(pairs_dev), n))

@@ -586,7 +586,7 @@ int rj_create(int device_id, rj_handle* out) {
   // that would otherwise land in the first upload, the first index build and the first query)
   ok = ok && warm_query_kernels(h->stream) == hipSuccess && warm_grid_kernels(h->stream) == hipSuccess &&
        warm_stitch_kernels(h->stream) == hipSuccess && warm_strip_kernels(h->stream) == hipSuccess &&
-       hipStreamSynchronize(h->stream) == hipSuccess;
+       warm_overlay_kernels(h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
   if (!ok) { delete h; return RJ_E_HIP; }
   *out = h;
   return RJ_OK;
@@ -2543,6 +2543,35 @@ int rj_overlay_edge_xsects(rj_handle h, int im, const uint32_t* pairs_dev, uint6
   } while (0);
   if (rc) return rc;
   RJ_HIP(h, e);
+  return RJ_OK;
+}
+
+int rj_overlay_faces(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                     const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint64_t capacity,
+                     rj_overlay_face* out_dev, uint64_t* n_faces) {
+  RJ_CHECK_H(h);
+  if (!n_faces) return fail(h, RJ_E_INVALID, "rj_overlay_faces: n_faces is null");
+  *n_faces = 0;
+  if (!h->map[0].present || !h->map[1].present) return fail(h, RJ_E_INVALID, "rj_overlay_faces: both maps must be uploaded");
+  if (n && (!xsects0_dev || !xsects1_dev)) return fail(h, RJ_E_INVALID, "rj_overlay_faces: null records");
+  if ((h->map[0].np && !vertex_face0_dev) || (h->map[1].np && !vertex_face1_dev))
+    return fail(h, RJ_E_INVALID, "rj_overlay_faces: null vertex faces");
+  if (capacity && !out_dev) return fail(h, RJ_E_INVALID, "rj_overlay_faces: null output");
+  if (n >= (1ull << 32)) return fail(h, RJ_E_INVALID, "rj_overlay_faces: too many intersections");
+  if (int r = set_device(h)) return r;
+  RJ_HIP(h, join_aux(h));
+  OverlayFacesMap m[2];
+  for (int im = 0; im < 2; im++) {
+    const MapState& s = h->map[im];
+    m[im] = OverlayFacesMap{s.pts, s.edge_chain, s.edge_begin, s.left, s.right, s.ne, s.nc};
+  }
+  const rj_xsect* const xs[2] = {xsects0_dev, xsects1_dev};
+  const int32_t* const vf[2] = {vertex_face0_dev, vertex_face1_dev};
+  uint64_t rows = 0;
+  RJ_HIP(h, overlay_faces_device(h->stream, m, xs, n, vf, capacity, out_dev, &rows, &h->arena, &h->arena_bytes));
+  *n_faces = rows;
+  if (rows > capacity)
+    return fail(h, RJ_E_OVERFLOW, "rj_overlay_faces: %llu rows, capacity %llu", (unsigned long long) rows, (unsigned long long) capacity);
   return RJ_OK;
 }
 

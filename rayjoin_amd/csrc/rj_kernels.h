@@ -1,5 +1,6 @@
 // rj_kernels.h -- kernel argument blocks and launch wrappers (implemented in rj_kernels.hip)
 #pragma once
+#include "../../include/rayjoin_amd.h"
 #include "rj_device.h"
 
 namespace rj {
@@ -124,6 +125,7 @@ hipError_t warm_query_kernels(hipStream_t st);
 hipError_t warm_grid_kernels(hipStream_t st);
 hipError_t warm_stitch_kernels(hipStream_t st);
 hipError_t warm_strip_kernels(hipStream_t st);
+hipError_t warm_overlay_kernels(hipStream_t st);
 // The column index of an indexed map (rj_strip.hip, rj_device.h DeviceStrips) and the PIP pass on it.  Both build passes
 // answer a call with temp == nullptr with the temporary bytes they need.
 hipError_t launch_strip_width(hipStream_t st, const QBox* box0, const uint32_t* seid, uint64_t n0p, unsigned long long* out2);
@@ -180,5 +182,17 @@ hipError_t launch_pip_exact(hipStream_t st, const PipArgs& a, int blocks, const 
 int pip_walk_list_slots();  // candidates a todo record holds
 uint32_t pip_walk_group_lanes(uint64_t n, int top, int cus);  // points per wave k_pip_walk uses when the caller leaves it open
 int pip_walk_blocks_per_cu(int top);  // resident 256-thread blocks of k_pip_walk per compute unit for a tree of this height
+
+// The overlay's face table (rj_overlay.hip, rj_overlay.h): one map's device arrays as the contribution pass reads them.
+struct OverlayFacesMap {
+  const int64_t* pts;
+  const uint32_t *edge_chain, *edge_begin, *left, *right;
+  uint64_t ne, nc;
+};
+// rows (face 0, face 1, int128 area2) ascending by key into out[<= capacity]; *n_rows = the true row count (read back
+// with the stream's one sync).  Scratch: the caller's grow-only block.
+hipError_t overlay_faces_device(hipStream_t st, const OverlayFacesMap maps[2], const rj_xsect* const xsects[2], uint64_t n,
+                                const int32_t* const vertex_face[2], uint64_t capacity, rj_overlay_face* out, uint64_t* n_rows,
+                                char** scratch, size_t* scratch_bytes);
 
 }  // namespace rj

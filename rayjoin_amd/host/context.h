@@ -41,6 +41,9 @@ class Scaling {
   int64_t get_internal_min() const { return internal_min_; }
   int64_t get_internal_max() const { return internal_max_; }
   int64_t get_internal_range() const { return internal_range_; }
+  // input units per scaled unit: an area of a scaled units^2 is a * get_rrx() * get_rry() in input units
+  double get_rrx() const { return rrx_; }
+  double get_rry() const { return rry_; }
 
  private:
   int64_t internal_max_ = INT64_MAX >> 17, internal_min_ = INT64_MIN >> 17;

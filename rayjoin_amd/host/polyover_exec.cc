@@ -4,6 +4,8 @@
 //                    ComputeOutputPolygons, WriteResult}     src/app/map_overlay_lbvh.h:25-270
 //   -mode=grid (MapOverlayGrid, src/app/map_overlay_grid.h) runs the same stages on the device-side
 //   uniform grid; -check compares the LBVH results with the grid's, as run_overlay.cu:18-141 does.
+//   -face_table <path> (ours): the overlay's face table computed on the device from the same records
+//   (rj_overlay_faces) -- "f0 f1 area" per row, area in input units.
 #include <iostream>
 
 #include "context.h"
@@ -17,14 +19,15 @@ namespace {
 
 class MapOverlayLBVH {
  public:
-  MapOverlayLBVH(Context& ctx, double xsect_factor, bool grid = false, int grid_size = 2048)
-      : ctx_(ctx), xsect_factor_(xsect_factor), grid_(grid), grid_size_(grid_size) {}
+  MapOverlayLBVH(Context& ctx, double xsect_factor, bool grid = false, int grid_size = 2048, bool keep_xsects = false)
+      : ctx_(ctx), xsect_factor_(xsect_factor), grid_(grid), grid_size_(grid_size), keep_xsects_(keep_xsects) {}
   ~MapOverlayLBVH() {
     rj_handle h = ctx_.handle();
     if (pairs_) rj_dev_free(h, pairs_);
     for (int im = 0; im < 2; im++) {
       if (closest_[im]) rj_dev_free(h, closest_[im]);
       if (faces_[im]) rj_dev_free(h, faces_[im]);
+      if (xsects_dev_[im]) rj_dev_free(h, xsects_dev_[im]);
     }
   }
   void Init() {  // map_overlay_lbvh.h:25-40
@@ -70,9 +73,43 @@ class MapOverlayLBVH {
       int rc = rj_overlay_edge_xsects(h, im, pairs_, n_xsects_, d);
       xsects_[im].resize(n_xsects_);
       if (rc == RJ_OK) rc = rj_memcpy_d2h(h, xsects_[im].data(), d, 48 * n_xsects_);
-      rj_dev_free(h, d);
+      if (keep_xsects_) xsects_dev_[im] = d;  // (the face table reads them)
+      else rj_dev_free(h, d);
       rj_check(h, rc, "rj_overlay_edge_xsects");
     }
+  }
+  // the face table on the device (rj_overlay_faces): rows to the host, one sync for the count (and a second run only
+  // when the first guess of the row count was too small)
+  void ComputeFaceTable() {
+    rj_handle h = ctx_.handle();
+    uint64_t cap = 4 * (uint64_t) n_xsects_ + 1024, n = 0;
+    for (int attempt = 0; attempt < 2; attempt++) {
+      rj_overlay_face* d = nullptr;
+      rj_check(h, rj_dev_alloc(h, sizeof(rj_overlay_face) * cap, (void**) &d), "rj_dev_alloc");
+      int rc = rj_overlay_faces(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], cap, d, &n);
+      if (rc == RJ_E_OVERFLOW && attempt == 0) {
+        rj_dev_free(h, d);
+        cap = n;
+        continue;
+      }
+      face_rows_.resize(n);
+      if (rc == RJ_OK && n) rc = rj_memcpy_d2h(h, face_rows_.data(), d, sizeof(rj_overlay_face) * n);
+      rj_dev_free(h, d);
+      rj_check(h, rc, "rj_overlay_faces");
+      break;
+    }
+  }
+  // one line per row: "f0 f1 area", the area in input units (area2 / 2 * rrx * rry)
+  void WriteFaceTable(const char* path) const {
+    FILE* fp = fopen(path, "w");
+    if (!fp) throw std::runtime_error(std::string("Cannot open ") + path);
+    const Scaling& sc = ctx_.get_scaling();
+    const double k = 0.5 * sc.get_rrx() * sc.get_rry();
+    for (const rj_overlay_face& r : face_rows_) {
+      const __int128 a2 = (__int128) (((unsigned __int128) (uint64_t) r.area2_hi << 64) | r.area2_lo);
+      fprintf(fp, "%d %d %.17g\n", r.face[0], r.face[1], (double) a2 * k);
+    }
+    fclose(fp);
   }
   void WriteResult(const char* path) {  // :267-270
     std::vector<int32_t> pip[2];
@@ -123,7 +160,10 @@ class MapOverlayLBVH {
   double xsect_factor_;
   bool grid_;
   int grid_size_;
+  bool keep_xsects_;
   size_t cap_ = 0, n_xsects_ = 0;
+  rj_xsect* xsects_dev_[2] = {nullptr, nullptr};
+  std::vector<rj_overlay_face> face_rows_;
   uint32_t* pairs_ = nullptr;
   uint32_t* closest_[2] = {nullptr, nullptr};
   int32_t* faces_[2] = {nullptr, nullptr};
@@ -139,7 +179,7 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
   auto g2 = load_from(f.poly2, f.serialize, f.v);
   tm.next("Create App");
   Context ctx({g1, g2}, f.device, f.scale_fma);
-  MapOverlayLBVH overlay(ctx, f.xsect_factor, f.mode == "grid", f.grid_size);
+  MapOverlayLBVH overlay(ctx, f.xsect_factor, f.mode == "grid", f.grid_size, !f.face_table.empty());
   tm.next("Load Data");
   ctx.LoadToDevice();
   tm.next("Init");
@@ -154,6 +194,10 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
   }
   tm.next("Computer output polygons");
   overlay.ComputeOutputPolygons();
+  if (!f.face_table.empty()) {
+    tm.next("Compute face table");
+    overlay.ComputeFaceTable();
+  }
   if (f.check && f.mode != "grid") {  // run_overlay.cu:199-204: compare with -mode=grid
     tm.next("Check result");
     if (!overlay.CheckAgainstGrid(f.grid_size)) throw std::runtime_error("result differs from -mode=grid");
@@ -161,6 +205,10 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
   if (!f.output.empty()) {
     tm.next("Write to file");
     overlay.WriteResult(f.output.c_str());
+  }
+  if (!f.face_table.empty()) {
+    tm.next("Write face table");
+    overlay.WriteFaceTable(f.face_table.c_str());
   }
   tm.end();
 }

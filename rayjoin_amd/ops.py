@@ -9,6 +9,10 @@
 
   LSIGrid / PIPGrid + DeviceContext.BuildGrid(grid_size): the uniform-grid operators
       -- src/app/lsi_grid.h:80-131, src/app/pip_grid.h:14-70, src/grid/uniform_grid.h:132-349
+  MapOverlay(ctx).Init(); .BuildIndex(); .IntersectEdge(); .LocateVerticesInOtherMap(im);
+      .ComputeOutputPolygons(); .get_xsects(im); .FaceTable()
+      -- src/app/map_overlay.h:19-29, src/app/map_overlay_lbvh.h:25-265 (grid_size: MapOverlayGrid);
+         FaceTable is the overlay's answer computed on the device (rj_overlay_faces)
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -176,3 +180,95 @@ class PIPGrid(PIPLBVH):
             self.h.pip_query_grid(base, query_map_id, None, b, n, self.closest, self.faces)
         self.n = n
         return n
+
+
+FACE_TABLE_DTYPE = np.dtype([("face0", "<i4"), ("face1", "<i4"), ("area2", object), ("area", "<f8")])
+
+
+class MapOverlay:
+    """The overlay stages of MapOverlayLBVH (src/app/map_overlay.h:19-29), or of MapOverlayGrid with grid_size set, on
+    both maps of a DeviceContext, and the face table: which face of map 0 overlaps which face of map 1, and by how much."""
+
+    def __init__(self, dctx, grid_size=None):
+        self.ctx_ = dctx
+        self.h = dctx.handle
+        self.grid_size = grid_size
+        self.n_xsects = 0
+        self.xsects = [None, None]
+
+    def Init(self, xsect_factor=0.2):
+        """map_overlay_lbvh.h:25-40: a queue of xsect_factor * (edges of both maps) intersections"""
+        m = [self.ctx_.get_map(im) for im in range(2)]
+        self.capacity = int(xsect_factor * (m[0].n_edges + m[1].n_edges))
+        self.pairs = self.h.alloc(8 * max(1, self.capacity))
+        self.closest = [self.h.alloc(4 * max(1, m[im].n_points)) for im in range(2)]
+        self.faces = [self.h.alloc(4 * max(1, m[im].n_points)) for im in range(2)]
+        self.located = [False, False]
+        return self
+
+    def BuildIndex(self):
+        for im in range(2):
+            if self.grid_size:
+                self.h.build_grid(im, self.grid_size)
+            else:
+                self.h.build_lbvh(im)
+                self.ctx_.indexed[im] = True
+
+    def IntersectEdge(self, query_map_id=0):
+        """every edge of map query_map_id against the other map; returns the number of intersections"""
+        if self.grid_size:
+            self.n_xsects = self.h.lsi_query_grid(self.capacity, self.pairs)
+        else:
+            qe = self.ctx_.get_map(query_map_id).n_edges
+            self.n_xsects = self.h.lsi_query(1 - query_map_id, query_map_id, 0, qe, self.capacity, self.pairs)
+        return self.n_xsects
+
+    def LocateVerticesInOtherMap(self, query_map_id):
+        np_ = self.ctx_.get_map(query_map_id).n_points
+        fn = self.h.pip_query_grid if self.grid_size else self.h.pip_query
+        fn(1 - query_map_id, query_map_id, None, 0, np_, self.closest[query_map_id], self.faces[query_map_id])
+        self.located[query_map_id] = True
+
+    def ComputeOutputPolygons(self):
+        """the per-map records, ordered along every edge, with their mid-point faces (rj_overlay_edge_xsects)"""
+        for im in range(2):
+            self.xsects[im] = self.h.alloc(48 * max(1, self.n_xsects))
+            self.h.overlay_edge_xsects(im, self.pairs, self.n_xsects, self.xsects[im])
+
+    def get_xsects(self, im):
+        return self.xsects[im].to_host(_capi.XSECT_DTYPE, self.n_xsects)
+
+    def get_vertex_faces(self, im):
+        return self.faces[im].to_host(np.int32, self.ctx_.get_map(im).n_points)
+
+    def FaceTable(self, capacity=None):
+        """rows (face0, face1, area2, area) ascending by (face0, face1): area2 is twice the overlap's signed area in
+        scaled units^2, exact (a Python int); area is in input units (area2 / 2 * rrx * rry of the context's Scaling)."""
+        if not (self.located[0] and self.located[1]) or self.xsects[0] is None:
+            raise RuntimeError("MapOverlay.FaceTable needs LocateVerticesInOtherMap(0), (1) and ComputeOutputPolygons() first")
+        cap = int(capacity) if capacity is not None else max(64, 2 * self.n_xsects + 64)
+        while True:
+            out = self.h.alloc(_capi.FACE_DTYPE.itemsize * max(1, cap))
+            try:
+                n = self.h.overlay_faces(self.xsects[0], self.xsects[1], self.n_xsects, self.faces[0], self.faces[1], cap, out)
+                break
+            except _capi.QueueOverflow as e:
+                if capacity is not None:
+                    raise
+                out.free()
+                cap = e.n_found
+        raw = out.to_host(_capi.FACE_DTYPE, n)
+        out.free()
+        return face_table_from_rows(raw, self.ctx_.ctx.scaling)
+
+
+def face_table_from_rows(raw, scaling):
+    """FACE_DTYPE rows -> FACE_TABLE_DTYPE (exact area2 as Python ints, area in input units)"""
+    t = np.empty(len(raw), dtype=FACE_TABLE_DTYPE)
+    t["face0"] = raw["face"][:, 0]
+    t["face1"] = raw["face"][:, 1]
+    a2 = [(int(hi) << 64) | int(lo) for lo, hi in zip(raw["area2_lo"].tolist(), raw["area2_hi"].tolist())]
+    t["area2"] = a2
+    k = 0.5 * float(scaling.rrx) * float(scaling.rry)
+    t["area"] = [float(v) * k for v in a2]
+    return t
