@@ -383,10 +383,13 @@ int rj_last_stats(rj_handle h, uint64_t stats[16]);
  *                                             they are recorded regardless.
  * "stats"            0 / 1                    the instrumented kernels (visit counters for rj_last_stats; slower).
  * "own_stream"       1                        back to the handle's private stream (see rj_set_stream).
+ * A new handle takes the defaults of six from the environment (A/B runs; a value the option refuses keeps the default):
+ * RJ_LEAF_ORDER, RJ_LEAF_YSORT, RJ_PIP_COLUMNS, RJ_LSI_SEGMENTS, RJ_WALK_POINTS ("pip_walk_points"), RJ_POINTS_SPLIT ("lsi_points_split").
  *
  * rj_get_option reads any of these, and what the handle did or decided:
  *   "leaf_order_used0/1", "leaf_slots0/1", "leaf_runs0/1", "skyline_used0/1", "closed_chains0/1",
- *   "pip_columns_used0/1", "pip_column_entries0/1", "pip_column_shift0/1"   the index of map 0 / 1
+ *   "pip_columns_used0/1", "pip_column_entries0/1", "pip_column_shift0/1", "occ_permille0/1",
+ *   "leaf_ysort_used0/1"                                         the index of map 0 / 1
  *   "stitch_rounds", "stitch_loop_ends"                         the last run cutting (pointer-jumping rounds; closed loops)
  *   "pip_schedule" (0 turns, 1 shared, 2 full grids, -1 still trying), "pip_schedule_trials", "pip_schedule_us0/1/2",
  *   "lsi_share_blocks", "pip_share_blocks"                      what "pip_concurrent" 2 measured and settled on
@@ -407,8 +410,8 @@ int rj_get_option(rj_handle h, const char* name, int64_t* value);
  * is written to buf (NUL-terminated, truncated to cap) and its full length to *need; either may be NULL / 0. */
 int rj_get_plan(rj_handle h, char* buf, size_t cap, size_t* need);
 /* Experiment knobs for tools/ and the fault-path tests -- grids, chunk sizes, run lengths ("chunk_groups",
- * "group_lanes", "max_blocks", "lsi_share_blocks", "pip_share_blocks", "stack_cap", "walk_stack", "strip_shift", "run_cap", "pack_solo",
- * "pack_spread"; rj_api.hip lists their ranges).  Not needed by a host of the library, never a correctness input,
+ * "group_lanes", "max_blocks", "lsi_share_blocks", "pip_share_blocks", "stack_cap", "walk_stack", "strip_shift", "lazy_columns_min",
+ * "run_cap", "pack_solo", "pack_spread"; rj_api.hip lists their ranges).  Not needed by a host of the library, never a correctness input,
  * no promise that a name survives a round. */
 int rj_set_debug_option(rj_handle h, const char* name, int64_t value);
 int rj_get_debug_option(rj_handle h, const char* name, int64_t* value);

@@ -205,8 +205,6 @@ struct rj_handle_s {
   int debug_stack_cap = 1 << 30;            // tests of the fault path only
   int debug_walk_stack = 0;                 // tests of the groups that leave the walk (0: kWalkStack entries)
   int debug_strip_shift = 0;                // the column index of the next build on strips of 2^this quanta (0: by the map)
-  int debug_query_key_strips = 0;           // experiment: a re-ordered PIP query set over a column index is sorted strip-major (strip, then y), not by Morton key
-  int order_strip_shift = 0;                // ... the strip width the next query-key pass sorts by (0: Morton keys)
   // Round 6: a spatially INCOHERENT point set (the reference's GeneratePIPQueries: uniform random points) is answered by the
   // column index -- every point on its own, nothing to share, nothing to sort -- built at the first such query of at least
   // `lazy_columns_min` points when "pip_columns" is auto and the base map has none (8.4 M uniform random points, PIP query:
@@ -216,7 +214,7 @@ struct rj_handle_s {
   bool lazy_columns_want = false;           // ... the estimate's answer
   hipEvent_t ev[kNumTimers][2];
   bool ev_valid[kNumTimers] = {false};
-  bool stats_on = false;
+  int stats_on = 0;          // "stats": 1 the instrumented kernels
   GridState grid[2];
   int query_order = 1;  // 0 never, 1 auto (estimate coherence), 2 always
   bool last_ordered = false;
@@ -377,8 +375,6 @@ void free_bvh(BvhState& b) {
   b = BvhState();
 }
 
-static bool g_lsi_root_skip = true;  // (environment RJ_LSI_ROOT_SKIP=0: A/B runs)
-
 DeviceBvh bvh_view(const BvhState& b) {
   DeviceBvh d;
   d.sseg = b.sseg; d.seid = b.seid; d.sface = b.sface; d.box0 = b.box0; d.pmx1 = b.pmx1; d.xtab = b.xtab; d.ytab2 = b.ysort ? b.ytab2 : nullptr; d.occ = b.occ; d.sky = b.use_sky ? b.sky : nullptr;
@@ -388,7 +384,7 @@ DeviceBvh bvh_view(const BvhState& b) {
   }
   d.top = b.top; d.n0 = b.n0; d.occ_permille = b.occ_permille;
   // (the LSI traversals start one level below a top level that holds a handful of nodes: rj_device.h DeviceBvh::lsi_root)
-  d.lsi_root = g_lsi_root_skip && b.top >= 2 && b.nlvl[b.top] <= 4 && b.nlvl[b.top - 1] <= 128 ? b.top - 1 : b.top;
+  d.lsi_root = b.top >= 2 && b.nlvl[b.top] <= 4 && b.nlvl[b.top - 1] <= 128 ? b.top - 1 : b.top;
   d.strips.ytab = b.strips_built ? b.strip_ytab : nullptr;
   d.strips.ebox = b.strip_box; d.strips.einfo = b.strip_info; d.strips.tall = b.strip_tall; d.strips.shift = b.strip_shift;
   return d;
@@ -517,6 +513,182 @@ int check_fault(rj_handle h) {
               l && p ? " and " : "", p ? "k_pip" : "");
 }
 
+// Every query kernel clears the scheduler counters of the NEXT launch of its kind, so launches of one
+// kind must stay ordered on one stream: a switch drains the old stream (and the aux stream) first.
+int switch_stream(rj_handle h, hipStream_t s) {
+  if (s == h->stream) return RJ_OK;
+  if (int r = set_device(h)) return r;
+  RJ_HIP(h, hipStreamSynchronize(h->stream));
+  RJ_HIP(h, join_aux(h));
+  h->lsi_shared = h->lsi_inflight = false;
+  h->co_measure = false;
+  h->stream = s;
+  return RJ_OK;
+}
+
+// ---- options ------------------------------------------------------------------------------------
+// The options that do more than store a value (called after the value was accepted; they store it themselves)
+int set_stats(rj_handle h, int64_t v) { h->stats_on = v != 0; return RJ_OK; }
+int set_own_stream(rj_handle h, int64_t) { return switch_stream(h, h->own_stream); }
+int set_pip_concurrent(rj_handle h, int64_t v) {
+  if (join_aux(h) != hipSuccess) return fail(h, RJ_E_HIP, "pip_concurrent: stream sync failed");
+  h->pip_concurrent = (int) v;
+  co_reset(h);
+  return RJ_OK;
+}
+int set_pip_exact_stream(rj_handle h, int64_t v) {
+  if ((int) v == h->exact_own_stream) return RJ_OK;
+  // the two modes keep the aux stream's rest counts in different words: drain, then start both from zeroed words
+  if (int r = set_device(h)) return r;
+  RJ_HIP(h, hipStreamSynchronize(h->stream));
+  h->aux_pending = true;
+  RJ_HIP(h, join_aux(h));
+  RJ_HIP(h, hipStreamSynchronize(h->exact_stream));
+  for (size_t wd : kExactRestWord) RJ_HIP(h, hipMemsetAsync(h->d_counter + wd, 0, 8, h->stream));
+  RJ_HIP(h, hipStreamSynchronize(h->stream));
+  h->exact_rot = 0; h->exact_buf = 0; h->exact_last = -1; h->exact_out_closest = h->exact_out_face = nullptr;
+  h->exact_recorded[0] = h->exact_recorded[1] = false;
+  h->exact_own_stream = (int) v;
+  return RJ_OK;
+}
+
+// Every option of rj_set_option (debug = false) and rj_set_debug_option (true).  A value is accepted if it lies in
+// lo..hi or is one of `also`; the hint is the message of a refused one ("name: lo..hi" where none is given).
+// `field` is what the matching get reads back (nullptr: set only); `set`, where given, does the store itself.
+// `env`: the environment variable that gives a new handle another default -- atoi, then the same test; a value that
+// fails keeps the default (only plain stores take one).
+constexpr int64_t kAnyLo = INT64_MIN, kAnyHi = INT64_MAX;
+struct Option {
+  const char* name;
+  bool debug;
+  int rj_handle_s::*field;
+  int64_t lo, hi;
+  const char* hint;
+  const char* env;
+  int (*set)(rj_handle h, int64_t v);
+  int nalso;
+  int64_t also[5];
+  bool accepts(int64_t v) const {
+    if (v >= lo && v <= hi) return true;
+    for (int i = 0; i < nalso; i++) if (v == also[i]) return true;
+    return false;
+  }
+};
+const Option kOptions[] = {
+    {"leaf_order", false, &rj_handle_s::leaf_order, 0, 1, "leaf_order: 0 Hilbert neighbours, 1 chain runs", "RJ_LEAF_ORDER"},
+    {"skyline", false, &rj_handle_s::skyline, -1, 1, "skyline: -1 auto (maps of isolated rings), 0 never, 1 always"},
+    {"leaf_ysort", false, &rj_handle_s::leaf_ysort, 0, 1, "leaf_ysort: 1 blocks taller than wide get a second order by y (LSI), 0 x order only", "RJ_LEAF_YSORT"},
+    {"pip_columns", false, &rj_handle_s::pip_columns, -1, 1, "pip_columns: -1 auto (maps of closed rings or of short chains), 0 never, 1 always",
+     "RJ_PIP_COLUMNS"},
+    {"lsi_segments", false, &rj_handle_s::lsi_segments, 1, 2, "lsi_segments: 1 or 2", "RJ_LSI_SEGMENTS"},
+    {"pip_walk_points", false, &rj_handle_s::walk_points, 1, 2, "pip_walk_points: 1 or 2", "RJ_WALK_POINTS"},
+    {"pip_walk", false, &rj_handle_s::pip_walk, 0, 2, "pip_walk: 0 k_pip alone, 1 auto, 2 always two passes"},
+    {"lsi_points_split", false, &rj_handle_s::points_split, -1, 1, "lsi_points_split: -1 by the last count, 0 never, 1 always", "RJ_POINTS_SPLIT"},
+    {"query_order", false, &rj_handle_s::query_order, 0, 2, "query_order: 0 never, 1 auto, 2 always"},
+    {"timers", false, &rj_handle_s::timers, 0, 1, "timers: 0 or 1"},
+    {"pip_concurrent", false, &rj_handle_s::pip_concurrent, 0, 2,
+     "pip_concurrent: 0 never, 1 LSI and PIP queries come in pairs and share the chip, 2 the same if it measures faster", nullptr, set_pip_concurrent},
+    {"pip_exact_stream", false, &rj_handle_s::exact_own_stream, 0, 1, "pip_exact_stream: 0 or 1", nullptr, set_pip_exact_stream},
+    {"stats", false, &rj_handle_s::stats_on, kAnyLo, kAnyHi, nullptr, nullptr, set_stats},  // (any value but 0 is 1)
+    {"own_stream", false, nullptr, kAnyLo, kAnyHi, nullptr, nullptr, set_own_stream},
+    // experiment knobs (tools/, tests of the fault path): not part of what a host of the library needs, never a
+    // correctness input, no promise that they survive a round
+    {"chunk_groups", true, &rj_handle_s::chunk_groups, 0, 4096},  // consecutive groups handed to a wave at a time (0: per kernel, 8 / 6)
+    {"group_lanes", true, &rj_handle_s::group_lanes, 0, 0, "group_lanes: 0 (auto), 4, 8, 16, 32 or 64", nullptr, nullptr, 5, {4, 8, 16, 32, 64}},  // queries per wave
+    {"max_blocks", true, &rj_handle_s::max_blocks, 1, 1 << 20},  // cap on the persistent grids
+    {"lsi_share_blocks", true, &rj_handle_s::lsi_share_set, 0, 1 << 20},  // fixed grids of the shared schedule (0: derived)
+    {"pip_share_blocks", true, &rj_handle_s::pip_share_set, 0, 1 << 20},
+    {"stack_cap", true, &rj_handle_s::debug_stack_cap, 1, 1 << 30},  // instrumented kernels: fewer traversal-stack entries (fault path)
+    {"walk_stack", true, &rj_handle_s::debug_walk_stack, 0, 1 << 30},  // k_pip_walk*: fewer stack entries (groups that need more leave the walk)
+    {"strip_shift", true, &rj_handle_s::debug_strip_shift, 15, 20, "strip_shift: 0 or 15..20 (the sort key holds 16 bits of strip)", nullptr, nullptr, 1, {0}},
+    {"lazy_columns_min", true, &rj_handle_s::debug_lazy_columns_min, 0, 1 << 30},  // points from which an incoherent PIP query set makes the base map's column index (0: 2^22)
+    {"run_cap", true, &rj_handle_s::debug_run_cap, 2, 64, "run_cap: 0 or 2..64", nullptr, nullptr, 1, {0}},  // edges per polyline run of the next first build of a map (0: 64)
+    {"pack_solo", true, &rj_handle_s::debug_pack_solo, 0, 64},  // a run longer than this never shares its leaf (0: 48)
+    {"pack_spread", true, &rj_handle_s::debug_pack_spread, 0, 1000000},  // a shared leaf may be this many times as large as its runs (0: 8)
+};
+
+const Option* find_option(const char* name, bool debug) {
+  for (const Option& o : kOptions)
+    if (o.debug == debug && !strcmp(name, o.name)) return &o;
+  return nullptr;
+}
+
+int set_option(rj_handle h, const char* name, int64_t value, bool debug) {
+  RJ_CHECK_H(h);
+  if (!name) return fail(h, RJ_E_INVALID, "null option name");
+  const Option* o = find_option(name, debug);
+  if (!o) return fail(h, RJ_E_INVALID, debug ? "unknown debug option '%s'" : "unknown option '%s'", name);
+  if (!o->accepts(value))
+    return o->hint ? fail(h, RJ_E_INVALID, "%s", o->hint) : fail(h, RJ_E_INVALID, "%s: %lld..%lld", name, (long long) o->lo, (long long) o->hi);
+  if (o->set) return o->set(h, value);
+  h->*o->field = (int) value;
+  return RJ_OK;
+}
+
+// What rj_get_option reports besides the options: what the handle did or decided.  A report with `per` > 0 is read as
+// its name and one digit below `per` -- the map 0 / 1, the schedule 0 / 1 / 2 -- which the reader gets as k.
+int read_gcd_pairs(rj_handle h, int, int64_t* v) {  // pairs the last two-kernel records launch left to the gcd leg (synchronises the main stream)
+  if (int r = set_device(h)) return r;
+  unsigned long long c = 0;
+  RJ_HIP(h, hipStreamSynchronize(h->stream));
+  RJ_HIP(h, hipMemcpy(&c, h->d_counter + kSlowCountWord + (1 - h->flip_slow), 8, hipMemcpyDeviceToHost));
+  *v = h->last_points_split ? (int64_t) c : -1;
+  return RJ_OK;
+}
+int read_comm_ranks(rj_handle h, int, int64_t* v) {  // the ranks RCCL itself counts in the handle's communicator (0: rj_comm_init was not called)
+  int c = 0;
+  if (h->comm && ncclCommCount(h->comm, &c) != ncclSuccess) return fail(h, RJ_E_HIP, "ncclCommCount failed");
+  *v = c;
+  return RJ_OK;
+}
+struct Report {
+  const char* name;
+  int per;
+  int (*get)(rj_handle h, int k, int64_t* v);
+};
+#define RJ_READ(expr) [](rj_handle h, int k, int64_t* v) { *v = (int64_t) (expr); return (int) RJ_OK; }
+const Report kReports[] = {
+    {"query_last_ordered", 0, RJ_READ(h->last_ordered ? 1 : 0)},  // the last query ran through a Morton permutation of its queries
+    {"pip_schedule", 0, RJ_READ(h->pip_concurrent == 2 ? h->co_choice : (h->pip_concurrent == 1 ? 1 : 0))},
+    {"pip_schedule_trials", 0, RJ_READ(h->co_trials)},
+    {"pip_schedule_us", 3, RJ_READ(h->co_best[k] < 1e29f ? (int64_t) (h->co_best[k] * 1000.0f) : -1)},  // best span seen per schedule, microseconds (-1: not measured)
+    {"lsi_last_segments", 0, RJ_READ(h->last_lsi_segments)},
+    {"pip_last_walk_points", 0, RJ_READ(h->last_walk_points)},
+    {"lsi_points_last_split", 0, RJ_READ(h->last_points_split)},
+    {"lsi_points_gcd_pairs", 0, read_gcd_pairs},
+    {"pip_last_passes", 0, RJ_READ(h->last_passes)},  // how the last PIP query ran: 3 = walk + exact + k_pip, 1 = k_pip alone
+    {"pip_last_columns", 0, RJ_READ(h->last_columns)},
+    {"pip_rest", 0, RJ_READ(h->h_rest[0])},  // points the last finished two-pass query on the main stream left to k_pip (-1: none yet)
+    {"pip_rest_aux", 0, RJ_READ(h->h_rest[1])},
+    {"leaf_order_used", 2, RJ_READ(h->bvh[k].leaf_order)},  // what the index of map k was built with
+    {"leaf_slots", 2, RJ_READ(h->bvh[k].n0p)},              // slots of the index of map k (64 per leaf, padding included)
+    {"leaf_runs", 2, RJ_READ(h->map[k].runs_cut ? (int64_t) h->map[k].nruns : -1)},  // polyline runs cut for map k (-1: none cut)
+    {"occ_permille", 2, RJ_READ(h->bvh[k].occ_permille)},
+    {"leaf_ysort_used", 2, RJ_READ(h->bvh[k].ysort ? 1 : 0)},
+    {"pip_columns_used", 2, RJ_READ(h->bvh[k].strips_built ? 1 : 0)},
+    {"pip_column_entries", 2, RJ_READ(h->bvh[k].strip_entries)},
+    {"pip_column_shift", 2, RJ_READ(h->bvh[k].strips_built ? h->bvh[k].strip_shift : 0)},
+    {"skyline_used", 2, RJ_READ(h->bvh[k].use_sky ? 1 : 0)},
+    {"closed_chains", 2, RJ_READ(h->map[k].closed_chains)},
+    {"stitch_rounds", 0, RJ_READ(h->stitch_stats[0])},     // the last run cutting: pointer-jumping rounds that had work
+    {"stitch_loop_ends", 0, RJ_READ(h->stitch_stats[1])},  // ... chain ends on closed loops of paired chains
+    {"comm_ranks", 0, read_comm_ranks},
+    {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
+    {"pip_share_blocks", 0, RJ_READ(h->last_pip_share ? h->last_pip_share : h->pip_share_blocks())},
+};
+#undef RJ_READ
+
+const Report* find_report(const char* name, int* k) {
+  for (const Report& r : kReports) {
+    const size_t len = strlen(r.name);
+    if (strncmp(name, r.name, len)) continue;
+    const char* tail = name + len;  // "", or the one digit of a report with `per`
+    if (!r.per && !tail[0]) { *k = 0; return &r; }
+    if (r.per && tail[0] >= '0' && tail[0] < '0' + r.per && !tail[1]) { *k = tail[0] - '0'; return &r; }
+  }
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -531,13 +703,9 @@ int rj_create(int device_id, rj_handle* out) {
   rj_handle h = new (std::nothrow) rj_handle_s();
   if (!h) return RJ_E_NOMEM;
   h->device = device_id;
-  if (const char* e = getenv("RJ_LEAF_ORDER")) h->leaf_order = atoi(e) == 0 ? 0 : 1;
-  if (const char* e = getenv("RJ_LSI_SEGMENTS")) h->lsi_segments = atoi(e) == 1 ? 1 : 2;  // (A/B runs)
-  if (const char* e = getenv("RJ_WALK_POINTS")) h->walk_points = atoi(e) == 1 ? 1 : (atoi(e) == 4 ? 4 : 2);  // (A/B runs)
-  if (const char* e = getenv("RJ_POINTS_SPLIT")) { const int v = atoi(e); h->points_split = v < -1 || v > 1 ? -1 : v; }  // (A/B runs, like the above)
-  if (const char* e = getenv("RJ_LSI_ROOT_SKIP")) g_lsi_root_skip = atoi(e) != 0;                                          // (A/B runs)
-  if (const char* e = getenv("RJ_LEAF_YSORT")) h->leaf_ysort = atoi(e) == 0 ? 0 : 1;                                    // (A/B runs)
-  if (const char* e = getenv("RJ_PIP_COLUMNS")) { const int v = atoi(e); h->pip_columns = v < -1 || v > 1 ? -1 : v; }    // (A/B runs: the column index on / off whatever the map)
+  for (const Option& o : kOptions)  // (A/B runs)
+    if (const char* e = o.env ? getenv(o.env) : nullptr)
+      if (o.accepts(atoi(e))) h->*o.field = atoi(e);
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) h->cus = prop.multiProcessorCount;
@@ -621,19 +789,6 @@ int rj_destroy(rj_handle h) {
   return RJ_OK;
 }
 
-// Every query kernel clears the scheduler counters of the NEXT launch of its kind, so launches of one
-// kind must stay ordered on one stream: a switch drains the old stream (and the aux stream) first.
-static int switch_stream(rj_handle h, hipStream_t s) {
-  if (s == h->stream) return RJ_OK;
-  if (int r = set_device(h)) return r;
-  RJ_HIP(h, hipStreamSynchronize(h->stream));
-  RJ_HIP(h, join_aux(h));
-  h->lsi_shared = h->lsi_inflight = false;
-  h->co_measure = false;
-  h->stream = s;
-  return RJ_OK;
-}
-
 int rj_set_stream(rj_handle h, void* s) {
   RJ_CHECK_H(h);
   return switch_stream(h, (hipStream_t) s);  // NULL is HIP's null (legacy default) stream, e.g. torch's default
@@ -665,59 +820,11 @@ int rj_invalidate(rj_handle h) {
 int rj_get_option(rj_handle h, const char* name, int64_t* value) {
   RJ_CHECK_H(h);
   if (!name || !value) return fail(h, RJ_E_INVALID, "rj_get_option: null argument");
-  if (!strcmp(name, "stats")) *value = h->stats_on;
-  else if (!strcmp(name, "query_order")) *value = h->query_order;
-  else if (!strcmp(name, "query_last_ordered")) *value = h->last_ordered ? 1 : 0;  // the last query ran through a Morton permutation of its queries
-  else if (!strcmp(name, "pip_concurrent")) *value = h->pip_concurrent;
-  else if (!strcmp(name, "pip_schedule")) *value = h->pip_concurrent == 2 ? h->co_choice : (h->pip_concurrent == 1 ? 1 : 0);
-  else if (!strcmp(name, "pip_schedule_trials")) *value = h->co_trials;
-  else if (!strncmp(name, "pip_schedule_us", 15) && name[15] >= '0' && name[15] <= '2' && !name[16])  // best span seen per schedule, microseconds (-1: not measured)
-    *value = h->co_best[name[15] - '0'] < 1e29f ? (int64_t) (h->co_best[name[15] - '0'] * 1000.0f) : -1;
-  else if (!strcmp(name, "pip_walk")) *value = h->pip_walk;
-  else if (!strcmp(name, "timers")) *value = h->timers;
-  else if (!strcmp(name, "pip_walk_points")) *value = h->walk_points;
-  else if (!strcmp(name, "pip_exact_stream")) *value = h->exact_own_stream;
-  else if (!strcmp(name, "lsi_segments")) *value = h->lsi_segments;
-  else if (!strcmp(name, "lsi_last_segments")) *value = h->last_lsi_segments;
-  else if (!strcmp(name, "pip_last_walk_points")) *value = h->last_walk_points;
-  else if (!strcmp(name, "lsi_points_split")) *value = h->points_split;
-  else if (!strcmp(name, "lsi_points_last_split")) *value = h->last_points_split;
-  else if (!strcmp(name, "lsi_points_gcd_pairs")) {  // pairs the last two-kernel records launch left to the gcd leg (synchronises the main stream)
-    if (int r = set_device(h)) return r;
-    unsigned long long c = 0;
-    RJ_HIP(h, hipStreamSynchronize(h->stream));
-    RJ_HIP(h, hipMemcpy(&c, h->d_counter + kSlowCountWord + (1 - h->flip_slow), 8, hipMemcpyDeviceToHost));
-    *value = h->last_points_split ? (int64_t) c : -1;
-  }
-  else if (!strcmp(name, "pip_last_passes")) *value = h->last_passes;  // how the last PIP query ran: 3 = walk + exact + k_pip, 1 = k_pip alone
-  else if (!strcmp(name, "leaf_order")) *value = h->leaf_order;
-  else if (!strcmp(name, "leaf_order_used0") || !strcmp(name, "leaf_order_used1")) *value = h->bvh[name[15] - '0'].leaf_order;  // what the index of map 0 / 1 was built with
-  else if (!strcmp(name, "leaf_slots0") || !strcmp(name, "leaf_slots1")) *value = (int64_t) h->bvh[name[10] - '0'].n0p;  // slots of the index of map 0 / 1 (64 per leaf, padding included)
-  else if (!strcmp(name, "leaf_runs0") || !strcmp(name, "leaf_runs1")) *value = h->map[name[9] - '0'].runs_cut ? (int64_t) h->map[name[9] - '0'].nruns : -1;  // polyline runs cut for map 0 / 1 (-1: none cut)
-  else if (!strcmp(name, "stitch_rounds")) *value = h->stitch_stats[0];      // the last run cutting: pointer-jumping rounds that had work
-  else if (!strcmp(name, "stitch_loop_ends")) *value = h->stitch_stats[1];   // ... chain ends on closed loops of paired chains
-  else if (!strcmp(name, "skyline")) *value = h->skyline;
-  else if (!strcmp(name, "pip_columns")) *value = h->pip_columns;
-  else if (!strcmp(name, "leaf_ysort")) *value = h->leaf_ysort;
-  else if (!strcmp(name, "occ_permille0") || !strcmp(name, "occ_permille1")) *value = h->bvh[name[12] - '0'].occ_permille;
-  else if (!strcmp(name, "leaf_ysort_used0") || !strcmp(name, "leaf_ysort_used1")) *value = h->bvh[name[15] - '0'].ysort ? 1 : 0;
-  else if (!strcmp(name, "pip_columns_used0") || !strcmp(name, "pip_columns_used1")) *value = h->bvh[name[16] - '0'].strips_built ? 1 : 0;
-  else if (!strcmp(name, "pip_column_entries0") || !strcmp(name, "pip_column_entries1")) *value = (int64_t) h->bvh[name[18] - '0'].strip_entries;
-  else if (!strcmp(name, "pip_column_shift0") || !strcmp(name, "pip_column_shift1")) *value = h->bvh[name[16] - '0'].strips_built ? h->bvh[name[16] - '0'].strip_shift : 0;
-  else if (!strcmp(name, "pip_last_columns")) *value = h->last_columns;
-  else if (!strcmp(name, "skyline_used0") || !strcmp(name, "skyline_used1")) *value = h->bvh[name[12] - '0'].use_sky ? 1 : 0;
-  else if (!strcmp(name, "closed_chains0") || !strcmp(name, "closed_chains1")) *value = (int64_t) h->map[name[13] - '0'].closed_chains;
-  else if (!strcmp(name, "pip_rest")) *value = (int64_t) h->h_rest[0];  // points the last finished two-pass query on the main stream left to k_pip (-1: none yet)
-  else if (!strcmp(name, "pip_rest_aux")) *value = (int64_t) h->h_rest[1];
-  else if (!strcmp(name, "comm_ranks")) {  // the ranks RCCL itself counts in the handle's communicator (0: rj_comm_init was not called)
-    int c = 0;
-    if (h->comm && ncclCommCount(h->comm, &c) != ncclSuccess) return fail(h, RJ_E_HIP, "ncclCommCount failed");
-    *value = c;
-  }
-  else if (!strcmp(name, "lsi_share_blocks")) *value = h->lsi_share_blocks();
-  else if (!strcmp(name, "pip_share_blocks")) *value = h->last_pip_share ? h->last_pip_share : h->pip_share_blocks();
-  else return fail(h, RJ_E_INVALID, "unknown option '%s'", name);
-  return RJ_OK;
+  const Option* o = find_option(name, false);
+  if (o && o->field) { *value = h->*o->field; return RJ_OK; }
+  int k = 0;
+  if (const Report* r = find_report(name, &k)) return r->get(h, k, value);
+  return fail(h, RJ_E_INVALID, "unknown option '%s'", name);
 }
 
 // rj_get_plan: one JSON object (text) -- what the last query of each kind ran and why.  Host-side state only: nothing is
@@ -806,138 +913,16 @@ int rj_get_plan(rj_handle h, char* buf, size_t cap, size_t* need) {
   return RJ_OK;
 }
 
-int rj_set_option(rj_handle h, const char* name, int64_t value) {
-  RJ_CHECK_H(h);
-  if (!name) return fail(h, RJ_E_INVALID, "null option name");
-  if (!strcmp(name, "stats")) { h->stats_on = value != 0; return RJ_OK; }
-  if (!strcmp(name, "own_stream")) return switch_stream(h, h->own_stream);
-  if (!strcmp(name, "pip_concurrent")) {
-    if (join_aux(h) != hipSuccess) return fail(h, RJ_E_HIP, "pip_concurrent: stream sync failed");
-    if (value < 0 || value > 2) return fail(h, RJ_E_INVALID, "pip_concurrent: 0 never, 1 LSI and PIP queries come in pairs and share the chip, 2 the same if it measures faster");
-    h->pip_concurrent = (int) value;
-    co_reset(h);
-    return RJ_OK;
-  }
-  if (!strcmp(name, "leaf_order")) {
-    if (value < 0 || value > 1) return fail(h, RJ_E_INVALID, "leaf_order: 0 Hilbert neighbours, 1 chain runs");
-    h->leaf_order = (int) value;
-    return RJ_OK;
-  }
-  if (!strcmp(name, "skyline")) {
-    if (value < -1 || value > 1) return fail(h, RJ_E_INVALID, "skyline: -1 auto (maps of isolated rings), 0 never, 1 always");
-    h->skyline = (int) value;
-    return RJ_OK;
-  }
-  if (!strcmp(name, "leaf_ysort")) {
-    if (value < 0 || value > 1) return fail(h, RJ_E_INVALID, "leaf_ysort: 1 blocks taller than wide get a second order by y (LSI), 0 x order only");
-    h->leaf_ysort = (int) value;
-    return RJ_OK;
-  }
-  if (!strcmp(name, "pip_columns")) {
-    if (value < -1 || value > 1) return fail(h, RJ_E_INVALID, "pip_columns: -1 auto (maps of closed rings or of short chains), 0 never, 1 always");
-    h->pip_columns = (int) value;
-    return RJ_OK;
-  }
-  if (!strcmp(name, "lsi_segments")) {
-    if (value != 1 && value != 2) return fail(h, RJ_E_INVALID, "lsi_segments: 1 or 2");
-    h->lsi_segments = (int) value;
-    return RJ_OK;
-  }
-  if (!strcmp(name, "pip_walk_points")) {
-    if (value != 1 && value != 2 && value != 4) return fail(h, RJ_E_INVALID, "pip_walk_points: 1, 2 or 4");
-    h->walk_points = (int) value;
-    return RJ_OK;
-  }
-  if (!strcmp(name, "pip_exact_stream")) {
-    if (value < 0 || value > 1) return fail(h, RJ_E_INVALID, "pip_exact_stream: 0 or 1");
-    if ((int) value == h->exact_own_stream) return RJ_OK;
-    // the two modes keep the aux stream's rest counts in different words: drain, then start both from zeroed words
-    if (int r = set_device(h)) return r;
-    RJ_HIP(h, hipStreamSynchronize(h->stream));
-    h->aux_pending = true;
-    RJ_HIP(h, join_aux(h));
-    RJ_HIP(h, hipStreamSynchronize(h->exact_stream));
-    for (size_t wd : kExactRestWord) RJ_HIP(h, hipMemsetAsync(h->d_counter + wd, 0, 8, h->stream));
-    RJ_HIP(h, hipStreamSynchronize(h->stream));
-    h->exact_rot = 0; h->exact_buf = 0; h->exact_last = -1; h->exact_out_closest = h->exact_out_face = nullptr;
-    h->exact_recorded[0] = h->exact_recorded[1] = false;
-    h->exact_own_stream = (int) value;
-    return RJ_OK;
-  }
-  if (!strcmp(name, "timers")) {
-    if (value < 0 || value > 1) return fail(h, RJ_E_INVALID, "timers: 0 or 1");
-    h->timers = (int) value;
-    return RJ_OK;
-  }
-  if (!strcmp(name, "lsi_points_split")) {
-    if (value < -1 || value > 1) return fail(h, RJ_E_INVALID, "lsi_points_split: -1 by the last count, 0 never, 1 always");
-    h->points_split = (int) value;
-    return RJ_OK;
-  }
-  if (!strcmp(name, "pip_walk")) {
-    if (value < 0 || value > 2) return fail(h, RJ_E_INVALID, "pip_walk: 0 k_pip alone, 1 auto, 2 always two passes");
-    h->pip_walk = (int) value;
-    return RJ_OK;
-  }
-  if (!strcmp(name, "query_order")) {
-    if (value < 0 || value > 2) return fail(h, RJ_E_INVALID, "query_order: 0 never, 1 auto, 2 always");
-    h->query_order = (int) value;
-    return RJ_OK;
-  }
-  return fail(h, RJ_E_INVALID, "unknown option '%s'", name);
-}
+int rj_set_option(rj_handle h, const char* name, int64_t value) { return set_option(h, name, value, false); }
 
-// Experiment knobs (tools/, tests of the fault path): not part of what a host of the library needs, never a
-// correctness input, no promise that they survive a round.
-int rj_set_debug_option(rj_handle h, const char* name, int64_t value) {
-  RJ_CHECK_H(h);
-  if (!name) return fail(h, RJ_E_INVALID, "null option name");
-  struct { const char* name; int* var; int64_t lo, hi; } knobs[] = {
-      {"chunk_groups", &h->chunk_groups, 0, 4096},        // consecutive groups handed to a wave at a time (0: per kernel, 8 / 6)
-      {"max_blocks", &h->max_blocks, 1, 1 << 20},         // cap on the persistent grids
-      {"lsi_share_blocks", &h->lsi_share_set, 0, 1 << 20},  // fixed grids of the shared schedule (0: derived)
-      {"pip_share_blocks", &h->pip_share_set, 0, 1 << 20},
-      {"stack_cap", &h->debug_stack_cap, 1, 1 << 30},     // instrumented kernels: fewer traversal-stack entries (fault path)
-      {"walk_stack", &h->debug_walk_stack, 0, 1 << 30},   // k_pip_walk*: fewer stack entries (groups that need more leave the walk)
-      {"strip_shift", &h->debug_strip_shift, 0, 20},      // the column index on strips of 2^this quanta (0: chosen by the map; 15..20)
-      {"lazy_columns_min", &h->debug_lazy_columns_min, 0, 1 << 30},  // points from which an incoherent PIP query set makes the base map's column index (0: 2^22)
-      {"query_key_strips", &h->debug_query_key_strips, 0, 1},  // "query_order" 2 over a column index: sort the points strip-major instead of by Morton key
-      {"run_cap", &h->debug_run_cap, 0, 64},              // edges per polyline run of the next first build of a map (0: 64)
-      {"pack_solo", &h->debug_pack_solo, 0, 64},          // a run longer than this never shares its leaf (0: 48)
-      {"pack_spread", &h->debug_pack_spread, 0, 1000000}, // a shared leaf may be this many times as large as its runs (0: 8)
-  };
-  for (auto& k : knobs)
-    if (!strcmp(name, k.name)) {
-      if (value < k.lo || value > k.hi) return fail(h, RJ_E_INVALID, "%s: %lld..%lld", name, (long long) k.lo, (long long) k.hi);
-      if (!strcmp(name, "run_cap") && value == 1) return fail(h, RJ_E_INVALID, "run_cap: 0 or 2..64");
-      if (!strcmp(name, "strip_shift") && value != 0 && value < 15) return fail(h, RJ_E_INVALID, "strip_shift: 0 or 15..20 (the sort key holds 16 bits of strip)");
-      *k.var = (int) value;
-      return RJ_OK;
-    }
-  if (!strcmp(name, "group_lanes")) {  // queries per wave (0: 64 unless the query set is small)
-    if (value != 0 && value != 4 && value != 8 && value != 16 && value != 32 && value != 64)
-      return fail(h, RJ_E_INVALID, "group_lanes: 0 (auto), 4, 8, 16, 32 or 64");
-    h->group_lanes = (int) value;
-    return RJ_OK;
-  }
-  return fail(h, RJ_E_INVALID, "unknown debug option '%s'", name);
-}
+int rj_set_debug_option(rj_handle h, const char* name, int64_t value) { return set_option(h, name, value, true); }
 
 int rj_get_debug_option(rj_handle h, const char* name, int64_t* value) {
   RJ_CHECK_H(h);
   if (!name || !value) return fail(h, RJ_E_INVALID, "rj_get_debug_option: null argument");
-  if (!strcmp(name, "chunk_groups")) *value = h->chunk_groups;
-  else if (!strcmp(name, "group_lanes")) *value = h->group_lanes;
-  else if (!strcmp(name, "max_blocks")) *value = h->max_blocks;
-  else if (!strcmp(name, "lsi_share_blocks")) *value = h->lsi_share_set;
-  else if (!strcmp(name, "pip_share_blocks")) *value = h->pip_share_set;
-  else if (!strcmp(name, "stack_cap")) *value = h->debug_stack_cap;
-  else if (!strcmp(name, "walk_stack")) *value = h->debug_walk_stack;
-  else if (!strcmp(name, "strip_shift")) *value = h->debug_strip_shift;
-  else if (!strcmp(name, "run_cap")) *value = h->debug_run_cap;
-  else if (!strcmp(name, "pack_solo")) *value = h->debug_pack_solo;
-  else if (!strcmp(name, "pack_spread")) *value = h->debug_pack_spread;
-  else return fail(h, RJ_E_INVALID, "unknown debug option '%s'", name);
+  const Option* o = find_option(name, true);
+  if (!o) return fail(h, RJ_E_INVALID, "unknown debug option '%s'", name);
+  *value = h->*o->field;
   return RJ_OK;
 }
 
@@ -1457,7 +1442,7 @@ int rj_build_lbvh(rj_handle h, int base_map_id) {
 static int sort_query_points(rj_handle h, const int64_t* pts, uint64_t n) {  // -> h->ord_vout
   if (int r = ensure_sort_scratch(h, n)) return r;
   tic(h, RJ_T_ORDER);
-  RJ_HIP(h, launch_query_keys(h->stream, true, pts, nullptr, 0, n, h->ord_kin, h->ord_vin, h->order_strip_shift));
+  RJ_HIP(h, launch_query_keys(h->stream, true, pts, nullptr, 0, n, h->ord_kin, h->ord_vin));
   size_t tb = h->ord_temp_bytes;
   RJ_HIP(h, sort_morton_pairs(h->stream, h->ord_temp, tb, h->ord_kin, h->ord_kout, h->ord_vin, h->ord_vout, n));
   toc(h, RJ_T_ORDER);
@@ -1572,7 +1557,7 @@ static int maybe_order_queries(rj_handle h, bool points, const int64_t* pts, con
   if (int r = ensure_sort_scratch(h, n)) return r;
   h->order_fresh = true;
   tic(h, RJ_T_ORDER);
-  RJ_HIP(h, launch_query_keys(h->stream, points, pts, segs, begin, n, h->ord_kin, h->ord_vin, points ? h->order_strip_shift : 0));
+  RJ_HIP(h, launch_query_keys(h->stream, points, pts, segs, begin, n, h->ord_kin, h->ord_vin));
   size_t tb = h->ord_temp_bytes;
   RJ_HIP(h, sort_morton_pairs(h->stream, h->ord_temp, tb, h->ord_kin, h->ord_kout, h->ord_vin, h->ord_vout, n));
   toc(h, RJ_T_ORDER);
@@ -1821,7 +1806,6 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
   // (a base map with a column index answers every point on its own -- nothing is shared between the points of a wave,
   //  so a scattered query set needs no re-ordering there)
   bool by_columns = h->bvh[base_map_id].strips_built && h->pip_walk != 0 && (!h->stats_on || h->pip_walk == 2);
-  h->order_strip_shift = by_columns && h->debug_query_key_strips ? h->bvh[base_map_id].strip_shift : 0;
   if (by_columns && h->query_order != 2) { h->last_ordered = false; h->order_fresh = false; h->cur_caller = -1; h->cur_order = nullptr; }
   else {
     // (an incoherent set of enough points over a base map without a column index, "pip_columns" auto: build the index now
@@ -1995,10 +1979,8 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
     // stack is cut at kWalkStack entries whatever the tree's height, so eight blocks per CU fit on every tree.)
     // From four 128-position groups per resident wave on: below that -- a 1/8 shard of the headline's query map -- the
     // one-point kernel's smaller groups fill the waves better (1/8 shard, pipelined step: 0.203 -> 0.190 ms).
-    const int wp = h->walk_points == 4 ? 4 : 2;  // (four per lane: 256 positions per wave, half the blocks per CU)
-    const bool two = h->walk_points >= 2 && w.group_lanes == 64 && !h->chunk_groups &&
-                     pip_walk2_blocks_per_cu(w.bvh.top, wp) >= (wp == 4 ? 3 : 6) &&
-                     n >= (uint64_t) wp * 256 * 4 * h->cus * pip_walk2_blocks_per_cu(w.bvh.top, wp);  // (four groups per resident wave)
+    const bool two = h->walk_points >= 2 && w.group_lanes == 64 && !h->chunk_groups && pip_walk2_blocks_per_cu(w.bvh.top) >= 6 &&
+                     n >= (uint64_t) 2 * 256 * 4 * h->cus * pip_walk2_blocks_per_cu(w.bvh.top);  // (four groups per resident wave)
     tic(h, RJ_T_PIP_WALK, st);
     // a base map with a column index (isolated rings): the first pass reads the point's strip instead of walking the tree
     const bool columns = w.bvh.strips.ytab != nullptr;  // (instrumented too: k_pip_strip counts its scans)
@@ -2008,9 +1990,9 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
       RJ_HIP(h, launch_pip_strip(st, w, walk_blocks, h->cus));
     } else if (two) {
       if (aux && h->lsi_shared && !h->pip_share_set)
-        walk_blocks = h->cus * pip_walk2_blocks_beside(w.bvh.top, walk_share_of_this_pair / h->cus < 1 ? 1 : walk_share_of_this_pair / h->cus, wp);
-      RJ_HIP(h, launch_pip_walk2(st, w, walk_blocks, h->cus, h->stats_on, wp));
-      h->last_walk_points = wp;
+        walk_blocks = h->cus * pip_walk2_blocks_beside(w.bvh.top, walk_share_of_this_pair / h->cus < 1 ? 1 : walk_share_of_this_pair / h->cus);
+      RJ_HIP(h, launch_pip_walk2(st, w, walk_blocks, h->cus, h->stats_on));
+      h->last_walk_points = 2;
     } else {
       RJ_HIP(h, launch_pip_walk(st, w, h->stats_on, walk_blocks));
     }

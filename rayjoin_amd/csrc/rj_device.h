@@ -29,7 +29,8 @@ constexpr int kMaxTop = kMaxLevels - 1;  // highest level a tree accepted by rj_
 //   * popping TWO entries per step (k_lsi keeps two node loads in flight) grows it by <= 126 per
 //     step, and by induction over the level of the entries on top (a batch of pushed children is
 //     consumed completely before anything below it is touched) by <= 126 (top - 1) in all:
-//     64 + 126 (top - 1) entries.
+//     64 + 126 (top - 1) entries.  Where the top level holds <= 4 nodes k_lsi starts one level lower
+//     (DeviceBvh::lsi_root), from <= 128 entries: 128 + 126 (top - 2) <= 64 + 126 (top - 1).
 // Both bounds are checked against a simulation of the stack discipline in
 // tests/test_stack_bounds.py; the kernels still test every push against the capacity and raise
 // the handle's fault word (-> RJ_E_INTERNAL) instead of writing past the stack.

@@ -168,16 +168,16 @@ hipError_t launch_group_extent(hipStream_t st, bool points, const int64_t* pts, 
                                uint64_t n, unsigned long long* out2);
 hipError_t launch_group_extent_tail(hipStream_t st, const int64_t* pts, const uint32_t* order, uint64_t n, unsigned long long* out_mapped);
 hipError_t launch_query_keys(hipStream_t st, bool points, const int64_t* pts, const Seg* segs, uint64_t begin,
-                             uint64_t n, MortonKey* keys, uint32_t* vals, int strip_shift = 0);
+                             uint64_t n, MortonKey* keys, uint32_t* vals);
 hipError_t launch_lsi_points(hipStream_t st, const Seg* seg0, const Seg* seg1, const uint32_t* pairs,
                              uint64_t n, const unsigned long long* n_dev, XsectRec* out, uint32_t* slow_list,
                              unsigned long long* slow_count, unsigned long long* next_slow_count,
                              unsigned long long* count_hint);
 hipError_t launch_pip(hipStream_t st, const PipArgs& a, bool stats, int max_blocks);
 hipError_t launch_pip_walk(hipStream_t st, const PipArgs& a, bool stats, int max_blocks);
-hipError_t launch_pip_walk2(hipStream_t st, const PipArgs& a, int max_blocks, int cus, bool stats = false, int points = 2);
-int pip_walk2_blocks_per_cu(int top, int points = 2);
-int pip_walk2_blocks_beside(int top, int lsi_blocks_per_cu, int points = 2);
+hipError_t launch_pip_walk2(hipStream_t st, const PipArgs& a, int max_blocks, int cus, bool stats = false);
+int pip_walk2_blocks_per_cu(int top);
+int pip_walk2_blocks_beside(int top, int lsi_blocks_per_cu);
 hipError_t launch_pip_exact(hipStream_t st, const PipArgs& a, int blocks, const PipRestArgs& r);
 int pip_walk_list_slots();  // candidates a todo record holds
 uint32_t pip_walk_group_lanes(uint64_t n, int top, int cus);  // points per wave k_pip_walk uses when the caller leaves it open

@@ -671,7 +671,7 @@ __global__ __launch_bounds__(1024) void k_group_extent_tail(const int64_t* __res
 template <bool POINTS>
 __global__ __launch_bounds__(256) void k_query_keys(const int64_t* __restrict__ pts, const Seg* __restrict__ segs,
                                                     uint64_t begin, uint64_t n, MortonKey* __restrict__ keys,
-                                                    uint32_t* __restrict__ vals, int strip_shift) {
+                                                    uint32_t* __restrict__ vals) {
   for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) {
     int64_t mx, my;
     if (POINTS) {
@@ -679,14 +679,6 @@ __global__ __launch_bounds__(256) void k_query_keys(const int64_t* __restrict__ 
     } else {
       const Seg s = segs[begin + i];
       mx = (s.x1 + s.x2) >> 1; my = (s.y1 + s.y2) >> 1;
-    }
-    if (strip_shift) {
-      // STRIP-MAJOR order (a PIP query over a column index, rj_strip.hip): the point's strip above its height -- consecutive
-      // positions then read consecutive places of ONE strip's table and list
-      const int nb = 31 - strip_shift;  // bits of strip
-      keys[i] = (MortonKey) ((((uint32_t) quant(mx) >> strip_shift) << (32 - nb)) | ((uint32_t) quant(my) >> (nb - 1)));
-      vals[i] = (uint32_t) i;
-      continue;
     }
     const uint32_t ux = (uint32_t) ((uint64_t) (mx + kCoordOffset) >> 15), uy = (uint32_t) ((uint64_t) (my + kCoordOffset) >> 15);
     keys[i] = (MortonKey) (((spread32(uy) << 1) | spread32(ux)) >> kMortonDropBits);
@@ -2025,7 +2017,7 @@ __global__ __launch_bounds__(256, 8) void k_pip_walk(PipArgs A) {
 // of whose lanes wants a leaf block skips it (wave-uniform).  Same stack, twice the candidate lists; the hand-over
 // (one todo slot per position, one mask per 64 positions, the rest list) is exactly k_pip_walk's, so k_pip_exact
 // cannot tell the two apart.  Requires group_lanes == 64 (a large query set).
-// (P points per lane: 2, or 4 -- 256 positions per wave, the traversal's own costs shared by twice the points)
+// (the body takes P points per lane; only P = 2 is built -- four per lane measured slower)
 __host__ __device__ __forceinline__ size_t walk2_wave_lds(int top, int P = 2) { return (size_t) 16 * walk_stack_entries(top) + (size_t) kWalkList * 256 * P; }
 
 // (96 SGPRs: above that the hardware admits one block per CU fewer than the occupancy query reports, and the shared
@@ -2391,8 +2383,6 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
 // of its blocks fit beside two of k_lsi2's 80 on a SIMD's 512.
 __global__ __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(96))) __attribute__((amdgpu_num_vgpr(28))) void k_pip_walk2(PipArgs A) { pip_walk_many<false, 2>(A); }
 __global__ __launch_bounds__(256, 4) __attribute__((amdgpu_num_sgpr(96))) void k_pip_walk2_stats(PipArgs A) { pip_walk_many<true, 2>(A); }
-__global__ __launch_bounds__(256, 4) __attribute__((amdgpu_num_sgpr(96))) void k_pip_walk4(PipArgs A) { pip_walk_many<false, 4>(A); }
-__global__ __launch_bounds__(256, 4) __attribute__((amdgpu_num_sgpr(96))) void k_pip_walk4_stats(PipArgs A) { pip_walk_many<true, 4>(A); }
 
 
 // The walk's leftovers: the exact predicate (pip.h:36-95, as in k_pip's evaluate) over each listed point's complete
@@ -2736,12 +2726,12 @@ hipError_t launch_group_extent_tail(hipStream_t st, const int64_t* pts, const ui
 }
 
 hipError_t launch_query_keys(hipStream_t st, bool points, const int64_t* pts, const Seg* segs, uint64_t begin,
-                             uint64_t n, MortonKey* keys, uint32_t* vals, int strip_shift) {
+                             uint64_t n, MortonKey* keys, uint32_t* vals) {
   if (n == 0) return hipSuccess;
   if (points)
-    hipLaunchKernelGGL(k_query_keys<true>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, pts, segs, begin, n, keys, vals, strip_shift);
+    hipLaunchKernelGGL(k_query_keys<true>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, pts, segs, begin, n, keys, vals);
   else
-    hipLaunchKernelGGL(k_query_keys<false>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, pts, segs, begin, n, keys, vals, 0);
+    hipLaunchKernelGGL(k_query_keys<false>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, st, pts, segs, begin, n, keys, vals);
   return hipGetLastError();
 }
 
@@ -2796,57 +2786,47 @@ hipError_t launch_pip_walk(hipStream_t st, const PipArgs& a_in, bool stats, int 
   return hipGetLastError();
 }
 
-int pip_walk2_blocks_per_cu(int top, int points) {
-  const size_t block = 4 * walk2_wave_lds(top, points == 4 ? 4 : 2) + 64;
+int pip_walk2_blocks_per_cu(int top) {
+  const size_t block = 4 * walk2_wave_lds(top) + 64;
   const size_t by_lds = (size_t) 160 * 1024 / block;
-  const size_t cap = points == 4 ? 4 : 8;  // (k_pip_walk2<*, 4> is built for four blocks per CU: its registers)
-  return (int) (by_lds < cap ? by_lds : cap);
+  return (int) (by_lds < 8 ? by_lds : 8);
 }
 
 // ... beside `lsi_blocks_per_cu` resident blocks of k_lsi (17.5 KiB of LDS and one wave slot per SIMD each)
-int pip_walk2_blocks_beside(int top, int lsi_blocks_per_cu, int points) {
-  const int P = points == 4 ? 4 : 2;
-  const size_t block = 4 * walk2_wave_lds(top, P) + 64;
+int pip_walk2_blocks_beside(int top, int lsi_blocks_per_cu) {
+  const size_t block = 4 * walk2_wave_lds(top) + 64;
   const size_t left = (size_t) 160 * 1024 > (size_t) lsi_blocks_per_cu * 17920 ? (size_t) 160 * 1024 - (size_t) lsi_blocks_per_cu * 17920 : 0;
   int n = (int) (left / block);
   if (n > 8 - lsi_blocks_per_cu) n = 8 - lsi_blocks_per_cu;
   // ... and of a SIMD's 512 VGPRs 80 per wave of k_lsi2 and 56 per wave of the walk (it is kept to that: the point
   // indices are read again at the end, base + lane addresses are not held): 6 beside 2.  (At 64 it was 5 beside 2.
   // Tried: k_lsi2 held to 64 VGPRs instead -- 14 spilled registers make it 48 % slower.)
-  static int walk_regs[2] = {0, 0}, lsi_regs = 0;
-  if (!walk_regs[0]) {
+  static int walk_regs = 0, lsi_regs = 0;
+  if (!walk_regs) {
     hipFuncAttributes fa;
-    walk_regs[0] = hipFuncGetAttributes(&fa, (const void*) k_pip_walk2) == hipSuccess && fa.numRegs > 0 ? (fa.numRegs + 7) / 8 * 8 : 64;
-    walk_regs[1] = hipFuncGetAttributes(&fa, (const void*) k_pip_walk4) == hipSuccess && fa.numRegs > 0 ? (fa.numRegs + 7) / 8 * 8 : 96;
+    walk_regs = hipFuncGetAttributes(&fa, (const void*) k_pip_walk2) == hipSuccess && fa.numRegs > 0 ? (fa.numRegs + 7) / 8 * 8 : 64;
     lsi_regs = hipFuncGetAttributes(&fa, (const void*) k_lsi2) == hipSuccess && fa.numRegs > 0 ? (fa.numRegs + 7) / 8 * 8 : 80;
   }
-  const int by_vgpr = (512 - lsi_blocks_per_cu * lsi_regs) / walk_regs[P == 4];
+  const int by_vgpr = (512 - lsi_blocks_per_cu * lsi_regs) / walk_regs;
   if (n > by_vgpr) n = by_vgpr;
-  if (n > pip_walk2_blocks_per_cu(top, P)) n = pip_walk2_blocks_per_cu(top, P);
+  if (n > pip_walk2_blocks_per_cu(top)) n = pip_walk2_blocks_per_cu(top);
   return n < 1 ? 1 : n;
 }
 
-hipError_t launch_pip_walk2(hipStream_t st, const PipArgs& a_in, int max_blocks, int cus, bool stats, int points) {
+hipError_t launch_pip_walk2(hipStream_t st, const PipArgs& a_in, int max_blocks, int cus, bool stats) {
   PipArgs a = a_in;
-  const int P = points == 4 ? 4 : 2;
-  const size_t lds = 4 * walk2_wave_lds(a.bvh.top, P);
-  const int res = cus * pip_walk2_blocks_per_cu(a.bvh.top, P);
-  a.group_lanes = 64;  // (positions per mask; a wave takes P of them)
-  const uint64_t ngroups = (a.n + 64 * P - 1) / (64 * P);
-  a.chunk_groups = a.chunk_groups ? a.chunk_groups : (P == 2 ? 3 : 2);  // (128-point groups: the same 6 x 64 positions per chunk; 256-point groups: 8 x 64)
+  const size_t lds = 4 * walk2_wave_lds(a.bvh.top);
+  const int res = cus * pip_walk2_blocks_per_cu(a.bvh.top);
+  a.group_lanes = 64;  // (positions per mask; a wave takes two of them)
+  const uint64_t ngroups = (a.n + 127) / 128;
+  a.chunk_groups = a.chunk_groups ? a.chunk_groups : 3;  // (128-point groups: the same 6 x 64 positions per chunk)
   const uint64_t nchunks = (ngroups + a.chunk_groups - 1) / a.chunk_groups;
   const int grid = grid_for(nchunks, 4, res < max_blocks ? res : max_blocks);
-  note(P == 4 ? "k_pip_walk4" : "k_pip_walk2", grid, P);
-  if (P == 4) {
-    if (stats)
-      hipLaunchKernelGGL(k_pip_walk4_stats, dim3(grid), dim3(256), lds, st, a);
-    else
-      hipLaunchKernelGGL(k_pip_walk4, dim3(grid), dim3(256), lds, st, a);
-  } else if (stats) {
+  note("k_pip_walk2", grid, 2);
+  if (stats)
     hipLaunchKernelGGL(k_pip_walk2_stats, dim3(grid), dim3(256), lds, st, a);
-  } else {
+  else
     hipLaunchKernelGGL(k_pip_walk2, dim3(grid), dim3(256), lds, st, a);
-  }
   return hipGetLastError();
 }
 

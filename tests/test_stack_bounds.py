@@ -57,6 +57,12 @@ def test_stack_capacities_cover_the_worst_case(top):
         assert peak1 <= k_top + 63 * (top - 1) <= c["kPipStack"]
         if top <= 3:
             assert done1 and done2
+    # k_lsi's start one level lower (DeviceBvh::lsi_root: a top level of <= 4 nodes): <= 128 entries at level top - 1
+    if top > 1:
+        peak, done = _simulate(top - 1, 128, True, budget)
+        assert peak <= 128 + 126 * (top - 2) <= 64 + 126 * (top - 1) <= c["kStackEntries"]
+        if top <= 3:
+            assert done
     # the closed forms are tight for a full top level
     assert _simulate(top, 64, False, budget)[0] == 64 + 63 * (top - 1)
     if top > 1:

@@ -2,7 +2,7 @@
 """A/B of two builds of the library on ONE box (box-to-box spread is 2-3 %, more than most kernel changes): bench.py's
 headline step, alternately with each .so (RAYJOIN_AMD_LIB), `rounds` times; prints the medians side by side.
 usage (on the GPU box): tools/ab_bench.py rayjoin_amd/variants/librj_base.so rayjoin_amd/librayjoin_amd.so [rounds] [extra bench flags ...]"""
-import json, os, statistics, subprocess, sys
+import json, os, statistics, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 libs = [os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2])]
 rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 3
@@ -11,15 +11,15 @@ keys = {"step": lambda d: d["ms_per_step"], "pipelined": lambda d: d.get("ms_per
         "dom_in_step": lambda d: d["roofline"]["kernel_ms"], "dom_alone": lambda d: d["roofline"].get("kernel_ms_alone"),
         "other_in_step": lambda d: d["roofline_other"]["kernel_ms"], "lsi_wall": lambda d: d["lsi_ms"], "pip_wall": lambda d: d["pip_ms"]}
 res = [{k: [] for k in keys}, {k: [] for k in keys}]
+detail = os.path.join(tempfile.mkdtemp(), "detail.json")  # (bench.py --full: stdout holds the compact line, the record goes here)
 for r in range(rounds):
     for i, lib in enumerate(libs):
         env = dict(os.environ, RAYJOIN_AMD_LIB=lib)
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-secondary", "--no-cpu-baseline"] + extra,
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-secondary", "--no-cpu-baseline", "--detail", detail] + extra,
                              env=env, capture_output=True, text=True, timeout=900)
-        line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
-        if not line:
+        if out.returncode != 0:
             print("run failed:", out.stderr[-2000:]); sys.exit(1)
-        d = json.loads(line[0])
+        d = json.load(open(detail))["headline"]
         for k, f in keys.items():
             v = f(d)
             if v is not None:

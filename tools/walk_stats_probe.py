@@ -9,7 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rayjoin_amd import _capi, maps, synth
 ap = argparse.ArgumentParser()
 ap.add_argument("--base", default="USCounty"); ap.add_argument("--query", default="BlockGroup")
-ap.add_argument("--scale", type=float, default=1.0); ap.add_argument("--walk-points", type=int, default=2)
+ap.add_argument("--scale", type=float, default=1.0)
 ap.add_argument("--cycles", action="store_true", help="cycle stamps of the phases instead of the event counts"); ap.add_argument("--max-blocks", type=int, default=0)
 a = ap.parse_args()
 ctx = maps.Context([synth.standin(a.base, a.scale), synth.standin(a.query, a.scale)]).load()
@@ -20,7 +20,6 @@ h.build_lbvh(0)
 n = q.n_points
 closest = h.alloc(4 * n); faces = h.alloc(4 * n)
 h.set_option("pip_walk", 2)
-h.set_option("pip_walk_points", a.walk_points)
 ms = []
 for _ in range(4):
     h.pip_query(0, 1, None, 0, n, closest, faces)
