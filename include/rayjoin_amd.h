@@ -83,6 +83,15 @@ const char* rj_version(void);
 int rj_upload_map(rj_handle h, int map_id, const int64_t* xy, uint64_t np,
                   const uint32_t* row_index, const int64_t* left, const int64_t* right,
                   uint64_t nc);
+/* extends: Map::LoadFrom -- rj_upload_map for a map that is already in device memory (an rj_overlay_map output, a map
+ * another library built there).  The same contract, but xy_dev[2 np], row_index_dev[nc + 1], left_dev[nc], right_dev[nc]
+ * (int32) are caller-owned device memory, copied device to device; they may be freed when the call returns.  What
+ * rj_upload_map checks in host loops -- row_index starts at 0, ends at np, every chain has at least 2 points, every
+ * coordinate lies in [-2^46, 2^46) -- one kernel checks here: RJ_E_INVALID with a message, and the map that was in
+ * place stays.  Resets the same handle state (index, grid, cached orders of map_id). */
+int rj_upload_map_dev(rj_handle h, int map_id, const int64_t* xy_dev, uint64_t np,
+                      const uint32_t* row_index_dev, const int32_t* left_dev, const int32_t* right_dev,
+                      uint64_t nc);
 int rj_map_num_edges(rj_handle h, int map_id, uint64_t* ne);
 int rj_map_num_points(rj_handle h, int map_id, uint64_t* np);
 /* device pointer to the uploaded scaled points (int64 x,y pairs), owned by the handle */
@@ -282,6 +291,39 @@ typedef struct {
 int rj_overlay_faces(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
                      const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev,
                      uint64_t capacity, rj_overlay_face* out_dev, uint64_t* n_faces);
+
+/* rj_overlay_map flags */
+#define RJ_OVM_DROP_DEGENERATE 1u /* leave out the pieces with fewer than two points, together with their points */
+
+typedef struct {
+  uint64_t n_chains, n_points, n_faces;
+} rj_overlay_map_counts;
+
+/* extends: WriteOutputChain (src/app/output_chain.h:42-205) -- the output map itself as device arrays, in scaled
+ * integers, so that it can be read without parsing a file or become an input map (rj_upload_map_dev) without leaving
+ * the GPU.  Inputs as rj_overlay_faces.
+ *   chains  the pieces the writer keeps, in its order: map 0's pieces in chain order, then map 1's.  A piece is kept when
+ *           its other-map face is nonzero and its chain has a nonzero face on at least one side.
+ *   points  of a piece: head cut point (x_num, y_num of the record), the chain's vertices inside it, tail cut point;
+ *           consecutive equal points once (equality of the integer coordinates; the text writer compares unscaled
+ *           doubles).  xy_dev: int64 x,y pairs; piece k = points [row_index_dev[k], row_index_dev[k + 1]).
+ *   faces   numbered from 1 by the ordered pair (face of map 0, face of map 1), ascending by
+ *           ((uint64)(uint32)f0 << 32) | (uint32)f1; face_pairs_dev[2 (k - 1)], [2 (k - 1) + 1] is the pair of face k:
+ *           row k - 1 of rj_overlay_faces on the same inputs.  left_dev / right_dev: the face on each side of a piece,
+ *           0 without one.  (Not the text writer's numbering, which numbers unordered pairs in order of first use.)
+ *   origin_dev[k] = (im << 31) | the chain of map im piece k was cut from; may be NULL.
+ * RJ_OVM_DROP_DEGENERATE leaves out the pieces with fewer than two points (a cut on a vertex of its own chain) and their
+ * points -- what rj_upload_map_dev needs; the faces and their numbers do not change with it.
+ * Caller-owned device memory: xy_dev[2 point_capacity], row_index_dev[chain_capacity + 1], left_dev, right_dev,
+ * origin_dev[chain_capacity], face_pairs_dev[2 face_capacity].  RJ_E_OVERFLOW when a count exceeds its capacity:
+ * *counts holds the three true counts and nothing beyond any capacity is written; all capacities 0 (arrays may be
+ * NULL) is the sizing call.  n == 0 is valid.  The points of both maps and four per record must number fewer than 2^32
+ * (row_index is 32-bit).  One host sync, at the end, to read the counts. */
+int rj_overlay_map(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                   const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint32_t flags,
+                   uint64_t chain_capacity, uint64_t point_capacity, uint64_t face_capacity,
+                   int64_t* xy_dev, uint32_t* row_index_dev, int32_t* left_dev, int32_t* right_dev,
+                   int32_t* face_pairs_dev, uint32_t* origin_dev, rj_overlay_map_counts* counts);
 
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {

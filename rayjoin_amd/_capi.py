@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("RAYJOIN_AMD_LIB") or os.path.join(HERE, "librayjoin_a
 
 RJ_OK, RJ_E_INVALID, RJ_E_HIP, RJ_E_OVERFLOW, RJ_E_NOMEM, RJ_E_INTERNAL = 0, 1, 2, 3, 4, 5
 RJ_EXCHANGE_HEAD_WORDS = 4
+RJ_OVM_DROP_DEGENERATE = 1  # rj_overlay_map flags
 RJ_T_BUILD, RJ_T_LSI_KERNEL, RJ_T_PIP_KERNEL, RJ_T_LSI_POINTS, RJ_T_SORT, RJ_T_ORDER = 0, 1, 2, 3, 4, 5
 RJ_T_BUILD_KEYS, RJ_T_BUILD_SORT, RJ_T_BUILD_LEAVES, RJ_T_BUILD_LEVELS, RJ_T_PIP_WALK, RJ_T_BUILD_RUNS = 6, 7, 8, 9, 10, 11
 MISS_EID = 0xFFFFFFFF
@@ -33,6 +34,7 @@ SYMBOLS = {
     "rj_last_error_string": (C.c_char_p, [_vp]),
     "rj_version": (C.c_char_p, []),
     "rj_upload_map": (_int, [_vp, _int, _vp, _u64, _vp, _vp, _vp, _u64]),
+    "rj_upload_map_dev": (_int, [_vp, _int, _vp, _u64, _vp, _vp, _vp, _u64]),
     "rj_scale_points": (_int, [_vp, _vp, _u64, _vp, _int]),
     "rj_map_num_edges": (_int, [_vp, _int, C.POINTER(_u64)]),
     "rj_map_num_points": (_int, [_vp, _int, C.POINTER(_u64)]),
@@ -64,6 +66,7 @@ SYMBOLS = {
     "rj_last_ms_all": (_int, [_vp, _vp, _int]),
     "rj_overlay_edge_xsects": (_int, [_vp, _int, _vp, _u64, _vp]),
     "rj_overlay_faces": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "rj_overlay_map": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -128,6 +131,14 @@ class RayJoinError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("rayjoin_amd error %d: %s" % (code, msg))
         self.code = code
+
+
+class MapOverflow(RayJoinError):
+    """RJ_E_OVERFLOW of rj_overlay_map: counts = (chains, points, faces), the true counts"""
+
+    def __init__(self, msg, counts):
+        super().__init__(RJ_E_OVERFLOW, msg)
+        self.counts = counts
 
 
 class QueueOverflow(RayJoinError):
@@ -272,6 +283,11 @@ class Handle:
         nc = left.shape[0]
         self._check(self.L.rj_upload_map(self.h, map_id, pts.ctypes.data, pts.shape[0],
                                          row_index.ctypes.data, left.ctypes.data, right.ctypes.data, nc))
+
+    def upload_map_dev(self, map_id, xy_dev, n_points, row_index_dev, left_dev, right_dev, n_chains):
+        """rj_upload_map_dev: the map from device arrays (int64 xy, uint32 row_index, int32 left / right)"""
+        self._check(self.L.rj_upload_map_dev(self.h, map_id, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), _ptr(left_dev),
+                                             _ptr(right_dev), int(n_chains)))
 
     def map_num_edges(self, map_id):
         n = _u64()
@@ -426,6 +442,20 @@ class Handle:
             raise QueueOverflow(self.L.rj_last_error_string(self.h).decode(), nf.value)
         self._check(rc)
         return nf.value
+
+    def overlay_map(self, xsects0_dev, xsects1_dev, n, vertex_face0_dev, vertex_face1_dev, flags, capacities, xy_dev, row_index_dev,
+                    left_dev, right_dev, face_pairs_dev, origin_dev=None):
+        """rj_overlay_map into the caller's device arrays; capacities = (chains, points, faces).  Returns the counts
+        (chains, points, faces); MapOverflow (with the true counts) past a capacity"""
+        counts = (_u64 * 3)()
+        cc, pc, fc = (int(v) for v in capacities)
+        rc = self.L.rj_overlay_map(self.h, _ptr(xsects0_dev), _ptr(xsects1_dev), n, _ptr(vertex_face0_dev), _ptr(vertex_face1_dev),
+                                   int(flags), cc, pc, fc, _ptr(xy_dev), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev),
+                                   _ptr(face_pairs_dev), _ptr(origin_dev), counts)
+        if rc == RJ_E_OVERFLOW:
+            raise MapOverflow(self.L.rj_last_error_string(self.h).decode(), tuple(counts))
+        self._check(rc)
+        return tuple(counts)
 
     def sort_pairs(self, pairs_dev, n):
         self._check(self.L.rj_sort_pairs(self.h, _ptr(pairs_dev), n))

@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <thread>
@@ -14,6 +15,7 @@
 
 #include "../../include/rayjoin_amd.h"
 #include "rj_kernels.h"
+#include "rj_overlay_dev.h"
 
 using namespace rj;
 
@@ -926,24 +928,21 @@ int rj_get_debug_option(rj_handle h, const char* name, int64_t* value) {
   return RJ_OK;
 }
 
-int rj_upload_map(rj_handle h, int map_id, const int64_t* xy, uint64_t np, const uint32_t* row_index,
-                  const int64_t* left, const int64_t* right, uint64_t nc) {
-  RJ_CHECK_H(h);
+// What an upload does to the handle before it looks at the map: the second stream joined, cached orders and what the
+// last walk left forgotten (rj_upload_map, rj_upload_map_dev).
+static int begin_upload(rj_handle h, int map_id) {
   if (map_id < 0 || map_id > 1) return fail(h, RJ_E_INVALID, "map_id must be 0 or 1");
   RJ_HIP(h, join_aux(h));
   co_reset(h);
   h->h_rest[0] = h->h_rest[1] = ~0ull;  // (what the last walk over another map left to k_pip says nothing about this one)
   h->walk_n[0] = h->walk_n[1] = 0;
-  if ((np && !xy) || (nc && (!row_index || !left || !right))) return fail(h, RJ_E_INVALID, "null input array");
-  if (np >= (1ull << 32) || nc > np) return fail(h, RJ_E_INVALID, "index_t is 32-bit: np < 2^32, nc <= np");
-  if (nc && (row_index[0] != 0 || row_index[nc] != np)) return fail(h, RJ_E_INVALID, "row_index must start at 0 and end at np");
-  for (uint64_t c = 0; c < nc; c++)
-    if (row_index[c + 1] < row_index[c] + 2)
-      return fail(h, RJ_E_INVALID, "chain %llu has fewer than 2 points (planar_graph.h:71)", (unsigned long long) c);
-  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "points without chains");
-  for (uint64_t i = 0; i < 2 * np; i++)
-    if (xy[i] < -((int64_t) 1 << 46) || xy[i] >= ((int64_t) 1 << 46))
-      return fail(h, RJ_E_INVALID, "coordinate %llu outside the scaled range [-2^46, 2^46)", (unsigned long long) i);
+  return RJ_OK;
+}
+
+// The tail both uploads share, after the map has been checked: the old map, its index, grid and cached orders go, the
+// arrays are allocated, fill(m) enqueues the copies of pts, edge_begin, left and right on the handle's stream, the
+// segments are built and the stream is drained (fill may read host memory that goes away).
+static int install_map(rj_handle h, int map_id, uint64_t np, uint64_t nc, const std::function<hipError_t(MapState&)>& fill) {
   if (int r = set_device(h)) return r;
   MapState& m = h->map[map_id];
   free_map(m);
@@ -952,9 +951,6 @@ int rj_upload_map(rj_handle h, int map_id, const int64_t* xy, uint64_t np, const
   h->coh[0][map_id].valid = h->coh[1][map_id].valid = false;
   h->ordc[0][map_id].valid = h->ordc[1][map_id].valid = false;
   m.np = np; m.nc = nc; m.ne = np - nc;
-  std::vector<uint32_t> eb(nc + 1), l32(nc), r32(nc);
-  for (uint64_t c = 0; c <= nc; c++) eb[c] = nc ? (uint32_t) (row_index[c] - c) : 0;
-  for (uint64_t c = 0; c < nc; c++) { l32[c] = (uint32_t) left[c]; r32[c] = (uint32_t) right[c]; }  // map.h:45
   int rc = RJ_OK;
   if (!rc) rc = dev_alloc(h, &m.pts, 2 * np + 2);
   if (!rc) rc = dev_alloc(h, &m.seg, m.ne);
@@ -965,12 +961,9 @@ int rj_upload_map(rj_handle h, int map_id, const int64_t* xy, uint64_t np, const
   if (!rc) rc = dev_alloc(h, &m.edge_begin, nc + 1);
   hipError_t e = hipSuccess;
   if (!rc) {
-    if (np) e = hipMemcpyAsync(m.pts, xy, 16 * np, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && nc) e = hipMemcpyAsync(m.edge_begin, eb.data(), 4 * (nc + 1), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && nc) e = hipMemcpyAsync(m.left, l32.data(), 4 * nc, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && nc) e = hipMemcpyAsync(m.right, r32.data(), 4 * nc, hipMemcpyHostToDevice, h->stream);
+    e = fill(m);
     if (e == hipSuccess) e = launch_build_segs(h->stream, m.pts, m.edge_begin, (uint32_t) nc, m.ne, m.seg, m.edge_chain, m.ccode);
-    // whatever was enqueued reads the host vectors: drain the stream before they go away
+    // whatever was enqueued may read the caller's host vectors: drain the stream before they go away
     const hipError_t es = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) e = es;
   }
@@ -979,6 +972,66 @@ int rj_upload_map(rj_handle h, int map_id, const int64_t* xy, uint64_t np, const
   RJ_HIP(h, e);
   m.present = true;
   return RJ_OK;
+}
+
+int rj_upload_map(rj_handle h, int map_id, const int64_t* xy, uint64_t np, const uint32_t* row_index,
+                  const int64_t* left, const int64_t* right, uint64_t nc) {
+  RJ_CHECK_H(h);
+  if (int r = begin_upload(h, map_id)) return r;
+  if ((np && !xy) || (nc && (!row_index || !left || !right))) return fail(h, RJ_E_INVALID, "null input array");
+  if (np >= (1ull << 32) || nc > np) return fail(h, RJ_E_INVALID, "index_t is 32-bit: np < 2^32, nc <= np");
+  if (nc && (row_index[0] != 0 || row_index[nc] != np)) return fail(h, RJ_E_INVALID, "row_index must start at 0 and end at np");
+  for (uint64_t c = 0; c < nc; c++)
+    if (row_index[c + 1] < row_index[c] + 2)
+      return fail(h, RJ_E_INVALID, "chain %llu has fewer than 2 points (planar_graph.h:71)", (unsigned long long) c);
+  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "points without chains");
+  for (uint64_t i = 0; i < 2 * np; i++)
+    if (xy[i] < -((int64_t) 1 << 46) || xy[i] >= ((int64_t) 1 << 46))
+      return fail(h, RJ_E_INVALID, "coordinate %llu outside the scaled range [-2^46, 2^46)", (unsigned long long) i);
+  std::vector<uint32_t> eb(nc + 1), l32(nc), r32(nc);
+  for (uint64_t c = 0; c <= nc; c++) eb[c] = nc ? (uint32_t) (row_index[c] - c) : 0;
+  for (uint64_t c = 0; c < nc; c++) { l32[c] = (uint32_t) left[c]; r32[c] = (uint32_t) right[c]; }  // map.h:45
+  return install_map(h, map_id, np, nc, [&](MapState& m) {
+    hipError_t e = hipSuccess;
+    if (np) e = hipMemcpyAsync(m.pts, xy, 16 * np, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && nc) e = hipMemcpyAsync(m.edge_begin, eb.data(), 4 * (nc + 1), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && nc) e = hipMemcpyAsync(m.left, l32.data(), 4 * nc, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && nc) e = hipMemcpyAsync(m.right, r32.data(), 4 * nc, hipMemcpyHostToDevice, h->stream);
+    return e;
+  });
+}
+
+int rj_upload_map_dev(rj_handle h, int map_id, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev,
+                      const int32_t* left_dev, const int32_t* right_dev, uint64_t nc) {
+  RJ_CHECK_H(h);
+  if (int r = begin_upload(h, map_id)) return r;
+  if ((np && !xy_dev) || (nc && (!row_index_dev || !left_dev || !right_dev))) return fail(h, RJ_E_INVALID, "null input array");
+  if (np >= (1ull << 32) || nc > np) return fail(h, RJ_E_INVALID, "index_t is 32-bit: np < 2^32, nc <= np");
+  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "points without chains");
+  if (int r = set_device(h)) return r;
+  // the checks rj_upload_map makes in host loops: one kernel, one status word (the map in place stays when they fail)
+  uint32_t* eb = nullptr;
+  if (nc) {
+    uint32_t status = 0;
+    if (int r = dev_alloc(h, &eb, nc + 2)) return r;  // (edge_begin[nc + 1], then the status word)
+    const hipError_t e = map_check_device(h->stream, xy_dev, np, row_index_dev, nc, eb, eb + nc + 1, &status);
+    if (e != hipSuccess || status) (void) hipFree(eb);
+    RJ_HIP(h, e);
+    if (status == kMapBadStart) return fail(h, RJ_E_INVALID, "row_index must start at 0");
+    if (status == kMapBadEnd) return fail(h, RJ_E_INVALID, "row_index must end at np");
+    if (status == kMapBadShortChain) return fail(h, RJ_E_INVALID, "a chain has fewer than 2 points (planar_graph.h:71)");
+    if (status) return fail(h, RJ_E_INVALID, "a coordinate lies outside the scaled range [-2^46, 2^46)");
+  }
+  const int rc = install_map(h, map_id, np, nc, [&](MapState& m) {
+    hipError_t e = hipSuccess;
+    if (np) e = hipMemcpyAsync(m.pts, xy_dev, 16 * np, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess && nc) e = hipMemcpyAsync(m.edge_begin, eb, 4 * (nc + 1), hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess && nc) e = hipMemcpyAsync(m.left, left_dev, 4 * nc, hipMemcpyDeviceToDevice, h->stream);  // (the same 32 bits)
+    if (e == hipSuccess && nc) e = hipMemcpyAsync(m.right, right_dev, 4 * nc, hipMemcpyDeviceToDevice, h->stream);
+    return e;
+  });
+  (void) hipFree(eb);
+  return rc;
 }
 
 int rj_scale_points(const double bb[4], const double* xy, uint64_t n, int64_t* out_xy, int fused) {
@@ -2554,6 +2607,46 @@ int rj_overlay_faces(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* x
   *n_faces = rows;
   if (rows > capacity)
     return fail(h, RJ_E_OVERFLOW, "rj_overlay_faces: %llu rows, capacity %llu", (unsigned long long) rows, (unsigned long long) capacity);
+  return RJ_OK;
+}
+
+int rj_overlay_map(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                   const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint32_t flags,
+                   uint64_t chain_capacity, uint64_t point_capacity, uint64_t face_capacity, int64_t* xy_dev,
+                   uint32_t* row_index_dev, int32_t* left_dev, int32_t* right_dev, int32_t* face_pairs_dev,
+                   uint32_t* origin_dev, rj_overlay_map_counts* counts) {
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_overlay_map: counts is null");
+  counts->n_chains = counts->n_points = counts->n_faces = 0;
+  if (flags & ~(uint32_t) RJ_OVM_DROP_DEGENERATE) return fail(h, RJ_E_INVALID, "rj_overlay_map: unknown flags 0x%x", flags);
+  if (!h->map[0].present || !h->map[1].present) return fail(h, RJ_E_INVALID, "rj_overlay_map: both maps must be uploaded");
+  if (n && (!xsects0_dev || !xsects1_dev)) return fail(h, RJ_E_INVALID, "rj_overlay_map: null records");
+  if ((h->map[0].np && !vertex_face0_dev) || (h->map[1].np && !vertex_face1_dev))
+    return fail(h, RJ_E_INVALID, "rj_overlay_map: null vertex faces");
+  if ((point_capacity && !xy_dev) || (chain_capacity && (!row_index_dev || !left_dev || !right_dev)) || (face_capacity && !face_pairs_dev))
+    return fail(h, RJ_E_INVALID, "rj_overlay_map: null output");
+  // (row_index is 32-bit: every point the maps could emit must have a slot below 2^32)
+  if (n >= (1ull << 32) || h->map[0].np + h->map[1].np + 4 * n >= (1ull << 32))
+    return fail(h, RJ_E_INVALID, "rj_overlay_map: too many points for a 32-bit row_index");
+  if (int r = set_device(h)) return r;
+  RJ_HIP(h, join_aux(h));
+  OverlayFacesMap m[2];
+  for (int im = 0; im < 2; im++) {
+    const MapState& s = h->map[im];
+    m[im] = OverlayFacesMap{s.pts, s.edge_chain, s.edge_begin, s.left, s.right, s.ne, s.nc};
+  }
+  const uint64_t np[2] = {h->map[0].np, h->map[1].np};
+  const rj_xsect* const xs[2] = {xsects0_dev, xsects1_dev};
+  const int32_t* const vf[2] = {vertex_face0_dev, vertex_face1_dev};
+  const OverlayMapOut out{xy_dev, row_index_dev, left_dev, right_dev, face_pairs_dev, origin_dev,
+                          chain_capacity, point_capacity, face_capacity};
+  uint64_t c[3] = {0, 0, 0};
+  RJ_HIP(h, overlay_map_device(h->stream, m, np, xs, n, vf, (flags & RJ_OVM_DROP_DEGENERATE) != 0, out, c, &h->arena, &h->arena_bytes));
+  counts->n_chains = c[0]; counts->n_points = c[1]; counts->n_faces = c[2];
+  if (c[0] > chain_capacity || c[1] > point_capacity || c[2] > face_capacity)
+    return fail(h, RJ_E_OVERFLOW, "rj_overlay_map: %llu chains, %llu points, %llu faces; capacities %llu, %llu, %llu", (unsigned long long) c[0],
+                (unsigned long long) c[1], (unsigned long long) c[2], (unsigned long long) chain_capacity,
+                (unsigned long long) point_capacity, (unsigned long long) face_capacity);
   return RJ_OK;
 }
 

@@ -18,6 +18,7 @@
 #include "../../include/rayjoin_amd.h"
 #include "rj_kernels.h"
 #include "rj_overlay.h"
+#include "rj_overlay_dev.h"
 
 namespace rj {
 
@@ -25,7 +26,6 @@ using namespace overlay;
 
 namespace {
 
-constexpr int kThreads = 256;
 static_assert(sizeof(Rec48) == sizeof(rj_xsect) && sizeof(Area2) == 16 && sizeof(rj_overlay_face) == 24, "layouts");
 
 struct Area2Sum {
@@ -38,22 +38,6 @@ __device__ __forceinline__ __int128 shfl_up128(__int128 v, int d) {
   const uint64_t lo2 = (uint64_t) __shfl_up((long long) lo, d, 64);
   const int64_t hi2 = (int64_t) __shfl_up((long long) hi, d, 64);
   return (__int128) (((unsigned __int128) (uint64_t) hi2 << 64) | lo2);
-}
-
-// first record whose eid[im] >= eid, found by the whole wave: 64 probes per step (a dependent load per 64x narrowing,
-// where one lane's binary search makes one per halving -- those serial loads were most of this pass).  Wave-uniform.
-__device__ __forceinline__ uint64_t wave_first_record(const Rec48* __restrict__ xs, uint64_t n, int im, uint64_t eid, int lane) {
-  uint64_t b = 0, e = n;  // the answer lies in [b, e]
-  while (e - b > 64) {
-    const uint64_t step = (e - b + 63) / 64, probe = b + (uint64_t) lane * step;
-    const bool below = probe < e && (uint64_t) xs[probe].eid[im] < eid;
-    const uint64_t k = (uint64_t) __popcll(__ballot(below));  // the probes below eid are a prefix
-    const uint64_t nb = k ? b + (k - 1) * step + 1 : b, ne = b + k * step < e ? b + k * step : e;
-    b = nb;
-    e = ne;
-  }
-  const bool below = b + lane < e && (uint64_t) xs[b + lane].eid[im] < eid;
-  return b + (uint64_t) __popcll(__ballot(below));
 }
 
 // one map's contributions (kWrite 0: what each wave stores, to wave_count; 1: store them from wave_base).  Every lane of a wave runs the loop body the same number of times (lanes beyond ne take part
@@ -162,23 +146,6 @@ __global__ __launch_bounds__(kThreads) void k_ovf_emit(const uint64_t* __restric
 }
 
 __global__ void k_ovf_noop() {}
-
-inline int grid_for(uint64_t threads, int cap_blocks) {
-  uint64_t b = (threads + kThreads - 1) / kThreads;
-  return (int) (b < 1 ? 1 : (b > (uint64_t) cap_blocks ? (uint64_t) cap_blocks : b));
-}
-
-struct Carve {
-  char* base = nullptr;
-  size_t used = 0;
-  template <typename T>
-  T* take(uint64_t count) {
-    used = (used + 255) & ~(size_t) 255;
-    T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
-    used += count * sizeof(T);
-    return p;
-  }
-};
 
 }  // namespace
 

@@ -6,7 +6,11 @@
 //   uniform grid; -check compares the LBVH results with the grid's, as run_overlay.cu:18-141 does.
 //   -face_table <path> (ours): the overlay's face table computed on the device from the same records
 //   (rj_overlay_faces) -- "f0 f1 area" per row, area in input units.
+//   -output_map <path> (ours): the output map computed on the device (rj_overlay_map) and written as a CDB file: the
+//   device map's chains and points (unscaled, "%.6f"), its ordered-pair face ids, end points numbered over the distinct
+//   scaled end points in order of first use.  -output stays the host writer's file.
 #include <iostream>
+#include <unordered_map>
 
 #include "context.h"
 #include "flags.h"
@@ -73,7 +77,7 @@ class MapOverlayLBVH {
       int rc = rj_overlay_edge_xsects(h, im, pairs_, n_xsects_, d);
       xsects_[im].resize(n_xsects_);
       if (rc == RJ_OK) rc = rj_memcpy_d2h(h, xsects_[im].data(), d, 48 * n_xsects_);
-      if (keep_xsects_) xsects_dev_[im] = d;  // (the face table reads them)
+      if (keep_xsects_) xsects_dev_[im] = d;  // (the face table and the output map read them)
       else rj_dev_free(h, d);
       rj_check(h, rc, "rj_overlay_edge_xsects");
     }
@@ -108,6 +112,57 @@ class MapOverlayLBVH {
     for (const rj_overlay_face& r : face_rows_) {
       const __int128 a2 = (__int128) (((unsigned __int128) (uint64_t) r.area2_hi << 64) | r.area2_lo);
       fprintf(fp, "%d %d %.17g\n", r.face[0], r.face[1], (double) a2 * k);
+    }
+    fclose(fp);
+  }
+  // the output map on the device (rj_overlay_map): a sizing call, then the arrays; to the host for the file
+  void ComputeOutputMap() {
+    rj_handle h = ctx_.handle();
+    rj_overlay_map_counts c;
+    int rc = rj_overlay_map(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], 0, 0, 0, 0, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, &c);
+    if (rc != RJ_E_OVERFLOW) rj_check(h, rc, "rj_overlay_map");
+    int64_t* xy = nullptr;
+    uint32_t* row = nullptr;
+    int32_t *left = nullptr, *right = nullptr, *pairs = nullptr;
+    rj_check(h, rj_dev_alloc(h, 16 * (c.n_points ? c.n_points : 1), (void**) &xy), "rj_dev_alloc");
+    rj_check(h, rj_dev_alloc(h, 4 * (c.n_chains + 1), (void**) &row), "rj_dev_alloc");
+    rj_check(h, rj_dev_alloc(h, 4 * (c.n_chains ? c.n_chains : 1), (void**) &left), "rj_dev_alloc");
+    rj_check(h, rj_dev_alloc(h, 4 * (c.n_chains ? c.n_chains : 1), (void**) &right), "rj_dev_alloc");
+    rj_check(h, rj_dev_alloc(h, 8 * (c.n_faces ? c.n_faces : 1), (void**) &pairs), "rj_dev_alloc");
+    rc = rj_overlay_map(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], 0, c.n_chains, c.n_points, c.n_faces, xy, row,
+                        left, right, pairs, nullptr, &c);
+    om_xy_.resize(2 * c.n_points);
+    om_row_.resize(c.n_chains + 1);
+    om_left_.resize(c.n_chains);
+    om_right_.resize(c.n_chains);
+    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_xy_.data(), xy, 16 * c.n_points);
+    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_row_.data(), row, 4 * (c.n_chains + 1));
+    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_left_.data(), left, 4 * c.n_chains);
+    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_right_.data(), right, 4 * c.n_chains);
+    rj_dev_free(h, xy); rj_dev_free(h, row); rj_dev_free(h, left); rj_dev_free(h, right); rj_dev_free(h, pairs);
+    rj_check(h, rc, "rj_overlay_map");
+    std::cerr << "Output map: " << c.n_chains << " chains, " << c.n_points << " points, " << c.n_faces << " faces" << std::endl;
+  }
+  // the device map as a CDB file: "id points first last left right", then the points
+  void WriteOutputMapFile(const char* path) const {
+    FILE* fp = fopen(path, "w");
+    if (!fp) throw std::runtime_error(std::string("Cannot open ") + path);
+    const Scaling& sc = ctx_.get_scaling();
+    struct Hash {
+      size_t operator()(const std::pair<int64_t, int64_t>& p) const {
+        return (size_t) (((uint64_t) p.first * 0x9E3779B97F4A7C15ull) ^ ((uint64_t) p.second + ((uint64_t) p.first >> 29)));
+      }
+    };
+    std::unordered_map<std::pair<int64_t, int64_t>, uint32_t, Hash> ids;
+    auto id_of = [&](uint32_t p) {
+      return ids.emplace(std::make_pair(om_xy_[2 * (size_t) p], om_xy_[2 * (size_t) p + 1]), (uint32_t) ids.size()).first->second;
+    };
+    for (size_t i = 0; i + 1 < om_row_.size(); i++) {
+      const uint32_t b = om_row_[i], e = om_row_[i + 1];
+      const uint32_t first = id_of(b), last = id_of(e - 1);
+      fprintf(fp, "%zu %u %u %u %d %d\n", i + 1, e - b, first, last, om_left_[i], om_right_[i]);
+      for (uint32_t p = b; p < e; p++) fprintf(fp, "%.6f %.6f\n", sc.UnscaleX(om_xy_[2 * (size_t) p]), sc.UnscaleY(om_xy_[2 * (size_t) p + 1]));
     }
     fclose(fp);
   }
@@ -164,6 +219,9 @@ class MapOverlayLBVH {
   size_t cap_ = 0, n_xsects_ = 0;
   rj_xsect* xsects_dev_[2] = {nullptr, nullptr};
   std::vector<rj_overlay_face> face_rows_;
+  std::vector<int64_t> om_xy_;  // the device output map on the host (-output_map)
+  std::vector<uint32_t> om_row_;
+  std::vector<int32_t> om_left_, om_right_;
   uint32_t* pairs_ = nullptr;
   uint32_t* closest_[2] = {nullptr, nullptr};
   int32_t* faces_[2] = {nullptr, nullptr};
@@ -179,7 +237,7 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
   auto g2 = load_from(f.poly2, f.serialize, f.v);
   tm.next("Create App");
   Context ctx({g1, g2}, f.device, f.scale_fma);
-  MapOverlayLBVH overlay(ctx, f.xsect_factor, f.mode == "grid", f.grid_size, !f.face_table.empty());
+  MapOverlayLBVH overlay(ctx, f.xsect_factor, f.mode == "grid", f.grid_size, !f.face_table.empty() || !f.output_map.empty());
   tm.next("Load Data");
   ctx.LoadToDevice();
   tm.next("Init");
@@ -198,6 +256,10 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
     tm.next("Compute face table");
     overlay.ComputeFaceTable();
   }
+  if (!f.output_map.empty()) {
+    tm.next("Compute output map");
+    overlay.ComputeOutputMap();
+  }
   if (f.check && f.mode != "grid") {  // run_overlay.cu:199-204: compare with -mode=grid
     tm.next("Check result");
     if (!overlay.CheckAgainstGrid(f.grid_size)) throw std::runtime_error("result differs from -mode=grid");
@@ -209,6 +271,10 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
   if (!f.face_table.empty()) {
     tm.next("Write face table");
     overlay.WriteFaceTable(f.face_table.c_str());
+  }
+  if (!f.output_map.empty()) {
+    tm.next("Write output map");
+    overlay.WriteOutputMapFile(f.output_map.c_str());
   }
   tm.end();
 }

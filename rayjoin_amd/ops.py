@@ -10,9 +10,10 @@
   LSIGrid / PIPGrid + DeviceContext.BuildGrid(grid_size): the uniform-grid operators
       -- src/app/lsi_grid.h:80-131, src/app/pip_grid.h:14-70, src/grid/uniform_grid.h:132-349
   MapOverlay(ctx).Init(); .BuildIndex(); .IntersectEdge(); .LocateVerticesInOtherMap(im);
-      .ComputeOutputPolygons(); .get_xsects(im); .FaceTable()
+      .ComputeOutputPolygons(); .get_xsects(im); .FaceTable(); .OutputMap()
       -- src/app/map_overlay.h:19-29, src/app/map_overlay_lbvh.h:25-265 (grid_size: MapOverlayGrid);
-         FaceTable is the overlay's answer computed on the device (rj_overlay_faces)
+         FaceTable is the overlay's answer computed on the device (rj_overlay_faces), OutputMap the output map as
+         device arrays (rj_overlay_map); DeviceContext.InstallMap makes one an input map again (rj_upload_map_dev)
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -33,14 +34,32 @@ class DeviceContext:
         self.handle = _capi.Handle(device_id)
         self.loaded = [False, False]
         self.indexed = [False, False]
+        self.installed = [None, None]  # maps that came from device memory (InstallMap) instead of ctx
 
     def LoadToDevice(self):
         for im in range(2):
             m = self.ctx.get_map(im)
             if m is not None:
                 self.handle.upload_map(im, m.pts, m.row_index, m.left, m.right)
+                self.installed[im] = None
                 self.loaded[im] = True
                 self.indexed[im] = False
+        return self
+
+    def InstallMap(self, im, output_map):
+        """An ops.DeviceOutputMap (MapOverlay.OutputMap(drop_degenerate=True)) becomes map `im` of this context without
+        leaving the GPU (rj_upload_map_dev), so that another MapOverlay can run: (A x B) x C.  The output map's faces
+        are the new map's faces.  Its coordinates are scaled integers: the caller is responsible for ONE Scaling over
+        all layers -- this context's Scaling must be the one the output map was computed under, and the other map of
+        this context must have been scaled by it too (maps.Context over every layer's bounding box).  The output map
+        may belong to another DeviceContext on the same device and can be freed afterwards.  get_map(im) then
+        returns the host image of the installed map (read back once, here)."""
+        om = output_map
+        self.handle.upload_map_dev(im, om.xy, om.n_points, om.row_index, om.left, om.right, om.n_chains)
+        self.installed[im] = om.to_host()[0]
+        self.installed[im].map_id = im
+        self.loaded[im] = True
+        self.indexed[im] = False
         return self
 
     def BuildIndex(self, base_map_id):
@@ -57,7 +76,7 @@ class DeviceContext:
         return ms
 
     def get_map(self, im):
-        return self.ctx.get_map(im)
+        return self.installed[im] if self.installed[im] is not None else self.ctx.get_map(im)
 
     def close(self):
         self.handle.close()
@@ -260,6 +279,54 @@ class MapOverlay:
         raw = out.to_host(_capi.FACE_DTYPE, n)
         out.free()
         return face_table_from_rows(raw, self.ctx_.ctx.scaling)
+
+    def OutputMap(self, drop_degenerate=False, capacities=None):
+        """The output map as a DeviceOutputMap (rj_overlay_map): the pieces the CDB writer keeps, in its order, in scaled
+        integers, faces numbered by the ordered pair (face of map 0, face of map 1) -- face k is row k - 1 of
+        FaceTable().  drop_degenerate leaves out the pieces with fewer than two points (what an input map may not have:
+        DeviceContext.InstallMap).  capacities = (chains, points, faces): MapOverflow with the true counts when one is
+        too small; left open, a sizing call finds them."""
+        if not (self.located[0] and self.located[1]) or self.xsects[0] is None:
+            raise RuntimeError("MapOverlay.OutputMap needs LocateVerticesInOtherMap(0), (1) and ComputeOutputPolygons() first")
+        flags = _capi.RJ_OVM_DROP_DEGENERATE if drop_degenerate else 0
+        args = (self.xsects[0], self.xsects[1], self.n_xsects, self.faces[0], self.faces[1], flags)
+        if capacities is None:
+            try:
+                capacities = self.h.overlay_map(*args, (0, 0, 0), None, None, None, None, None, None)
+            except _capi.MapOverflow as e:
+                capacities = e.counts
+        cc, pc, fc = (int(v) for v in capacities)
+        bufs = [self.h.alloc(16 * max(1, pc)), self.h.alloc(4 * (cc + 1)), self.h.alloc(4 * max(1, cc)), self.h.alloc(4 * max(1, cc)),
+                self.h.alloc(8 * max(1, fc)), self.h.alloc(4 * max(1, cc))]
+        try:
+            counts = self.h.overlay_map(*args, (cc, pc, fc), *bufs)
+        except _capi.RayJoinError:
+            for b in bufs:
+                b.free()
+            raise
+        return DeviceOutputMap(*bufs, counts, drop_degenerate)
+
+
+class DeviceOutputMap:
+    """The overlay's output map in device memory (rj_overlay_map): xy (int64 x,y pairs, scaled units), row_index
+    (uint32, n_chains + 1), left / right (int32 output face ids), face_pairs (int32 pairs: face k is face_pairs[k - 1])
+    and origin (uint32: (im << 31) | source chain) as DeviceBuffers, and the counts."""
+
+    def __init__(self, xy, row_index, left, right, face_pairs, origin, counts, drop_degenerate):
+        self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin = xy, row_index, left, right, face_pairs, origin
+        self.n_chains, self.n_points, self.n_faces = (int(v) for v in counts)
+        self.drop_degenerate = bool(drop_degenerate)
+
+    def to_host(self):
+        """-> (maps.ScaledMap of the output map, face_pairs int32 [n_faces, 2], origin uint32 [n_chains])"""
+        from .maps import ScaledMap
+        m = ScaledMap(0, self.xy.to_host(np.int64, 2 * self.n_points).reshape(-1, 2), self.row_index.to_host(np.uint32, self.n_chains + 1),
+                      self.left.to_host(np.int32, self.n_chains).astype(np.int64), self.right.to_host(np.int32, self.n_chains).astype(np.int64))
+        return m, self.face_pairs.to_host(np.int32, 2 * self.n_faces).reshape(-1, 2), self.origin.to_host(np.uint32, self.n_chains)
+
+    def free(self):
+        for b in (self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin):
+            b.free()
 
 
 def face_table_from_rows(raw, scaling):
