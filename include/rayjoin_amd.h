@@ -325,6 +325,42 @@ int rj_overlay_map(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xse
                    int64_t* xy_dev, uint32_t* row_index_dev, int32_t* left_dev, int32_t* right_dev,
                    int32_t* face_pairs_dev, uint32_t* origin_dev, rj_overlay_map_counts* counts);
 
+/* ---- overlay operations: union, difference, symmetric difference, identity; dissolved forms (clip) ------------ */
+/* extends: rj_overlay_faces / rj_overlay_map know one operation, the intersection (what the reference's CDB writer
+ * keeps).  A side of a piece has the ordered pair (f0, f1) = (face of map 0, face of map 1): the chain's face on that
+ * side and the piece's label.  `how` says which pairs are faces of the result: */
+#define RJ_OV_INTERSECTION 0u /* f0 != 0 and f1 != 0 */
+#define RJ_OV_UNION        1u /* f0 != 0 or  f1 != 0 */
+#define RJ_OV_DIFFERENCE   2u /* f0 != 0 and f1 == 0: map 0 minus map 1 */
+#define RJ_OV_SYMDIFF      3u /* (f0 != 0) != (f1 != 0) */
+#define RJ_OV_IDENTITY     4u /* f0 != 0: all of map 0, split by map 1 */
+/* `by` says what names a face: */
+#define RJ_OV_BY_PAIR 0u /* (f0, f1) */
+#define RJ_OV_BY_MAP0 1u /* (f0, 0): map 1's boundaries inside a face of map 0 dissolve (INTERSECTION + BY_MAP0 = clip) */
+#define RJ_OV_BY_MAP1 2u /* (0, f1) */
+/* A side's key is by(f0, f1) when the pair is selected and the key is not (0, 0), else "no face".  A piece is kept when
+ * the keys of its two sides differ (so at least one side has a face; a piece with the same face on both sides after a
+ * dissolve is dropped).  Adjacent kept pieces of one chain are not merged.  Everything else is as the call without _op
+ * documents: piece order, points, duplicate removal, faces numbered from 1 ascending by ((uint32)f0 << 32) | (uint32)f1
+ * of the KEY, RJ_OVM_DROP_DEGENERATE, RJ_E_OVERFLOW with the true counts, the sizing call, n == 0.
+ * The face table: a kept piece adds +cross per point pair to its left key and -cross to its right key; one row per key
+ * with a contribution, face[] holding the key -- so a face id may be 0 here: (f0, 0) is "f0 outside map 1" under
+ * BY_PAIR and "the selected part of f0" under BY_MAP0.  Under (RJ_OV_UNION, RJ_OV_BY_PAIR) the rows (f, *) sum to
+ * twice the area of face f of map 0 over its cut boundary, and the rows (*, g) to that of face g of map 1.
+ * (RJ_OV_INTERSECTION, RJ_OV_BY_PAIR) gives what the call without _op gives on maps whose chains have different faces
+ * on their two sides (a chain with one nonzero face on both sides is kept there and dropped here).
+ * An unknown `how` or `by` is RJ_E_INVALID.  Same cost class as the calls without _op: the same passes over the same
+ * edges, the operation being a kernel argument. */
+int rj_overlay_faces_op(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                        const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev,
+                        uint64_t capacity, rj_overlay_face* out_dev, uint64_t* n_faces, uint32_t how, uint32_t by);
+int rj_overlay_map_op(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                      const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint32_t flags,
+                      uint64_t chain_capacity, uint64_t point_capacity, uint64_t face_capacity,
+                      int64_t* xy_dev, uint32_t* row_index_dev, int32_t* left_dev, int32_t* right_dev,
+                      int32_t* face_pairs_dev, uint32_t* origin_dev, rj_overlay_map_counts* counts,
+                      uint32_t how, uint32_t by);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

@@ -14,6 +14,12 @@ LIB_PATH = os.environ.get("RAYJOIN_AMD_LIB") or os.path.join(HERE, "librayjoin_a
 RJ_OK, RJ_E_INVALID, RJ_E_HIP, RJ_E_OVERFLOW, RJ_E_NOMEM, RJ_E_INTERNAL = 0, 1, 2, 3, 4, 5
 RJ_EXCHANGE_HEAD_WORDS = 4
 RJ_OVM_DROP_DEGENERATE = 1  # rj_overlay_map flags
+# rj_overlay_faces_op / rj_overlay_map_op: which (face of map 0, face of map 1) pairs are faces, and what names a face
+RJ_OV_INTERSECTION, RJ_OV_UNION, RJ_OV_DIFFERENCE, RJ_OV_SYMDIFF, RJ_OV_IDENTITY = 0, 1, 2, 3, 4
+RJ_OV_BY_PAIR, RJ_OV_BY_MAP0, RJ_OV_BY_MAP1 = 0, 1, 2
+OVERLAY_HOW = {"intersection": RJ_OV_INTERSECTION, "union": RJ_OV_UNION, "difference": RJ_OV_DIFFERENCE,
+               "symmetric_difference": RJ_OV_SYMDIFF, "identity": RJ_OV_IDENTITY}
+OVERLAY_BY = {"pair": RJ_OV_BY_PAIR, "map0": RJ_OV_BY_MAP0, "map1": RJ_OV_BY_MAP1}
 RJ_T_BUILD, RJ_T_LSI_KERNEL, RJ_T_PIP_KERNEL, RJ_T_LSI_POINTS, RJ_T_SORT, RJ_T_ORDER = 0, 1, 2, 3, 4, 5
 RJ_T_BUILD_KEYS, RJ_T_BUILD_SORT, RJ_T_BUILD_LEAVES, RJ_T_BUILD_LEVELS, RJ_T_PIP_WALK, RJ_T_BUILD_RUNS = 6, 7, 8, 9, 10, 11
 MISS_EID = 0xFFFFFFFF
@@ -67,6 +73,9 @@ SYMBOLS = {
     "rj_overlay_edge_xsects": (_int, [_vp, _int, _vp, _u64, _vp]),
     "rj_overlay_faces": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
     "rj_overlay_map": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rj_overlay_faces_op": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64), C.c_uint32, C.c_uint32]),
+    "rj_overlay_map_op": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32,
+                                 C.c_uint32]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -433,25 +442,27 @@ class Handle:
     def overlay_edge_xsects(self, im, pairs_dev, n, xsects_dev):
         self._check(self.L.rj_overlay_edge_xsects(self.h, im, _ptr(pairs_dev), n, _ptr(xsects_dev)))
 
-    def overlay_faces(self, xsects0_dev, xsects1_dev, n, vertex_face0_dev, vertex_face1_dev, capacity, out_dev):
-        """rows of the face table into out_dev (FACE_DTYPE); returns the row count, QueueOverflow past capacity"""
+    def overlay_faces(self, xsects0_dev, xsects1_dev, n, vertex_face0_dev, vertex_face1_dev, capacity, out_dev, op=None):
+        """rows of the face table into out_dev (FACE_DTYPE); returns the row count, QueueOverflow past capacity.
+        op = (how, by): rj_overlay_faces_op; None: rj_overlay_faces"""
         nf = _u64()
-        rc = self.L.rj_overlay_faces(self.h, _ptr(xsects0_dev), _ptr(xsects1_dev), n, _ptr(vertex_face0_dev),
-                                     _ptr(vertex_face1_dev), capacity, _ptr(out_dev), C.byref(nf))
+        args = (self.h, _ptr(xsects0_dev), _ptr(xsects1_dev), n, _ptr(vertex_face0_dev), _ptr(vertex_face1_dev), capacity, _ptr(out_dev),
+                C.byref(nf))
+        rc = self.L.rj_overlay_faces(*args) if op is None else self.L.rj_overlay_faces_op(*args, int(op[0]), int(op[1]))
         if rc == RJ_E_OVERFLOW:
             raise QueueOverflow(self.L.rj_last_error_string(self.h).decode(), nf.value)
         self._check(rc)
         return nf.value
 
     def overlay_map(self, xsects0_dev, xsects1_dev, n, vertex_face0_dev, vertex_face1_dev, flags, capacities, xy_dev, row_index_dev,
-                    left_dev, right_dev, face_pairs_dev, origin_dev=None):
+                    left_dev, right_dev, face_pairs_dev, origin_dev=None, op=None):
         """rj_overlay_map into the caller's device arrays; capacities = (chains, points, faces).  Returns the counts
-        (chains, points, faces); MapOverflow (with the true counts) past a capacity"""
+        (chains, points, faces); MapOverflow (with the true counts) past a capacity.  op = (how, by): rj_overlay_map_op"""
         counts = (_u64 * 3)()
         cc, pc, fc = (int(v) for v in capacities)
-        rc = self.L.rj_overlay_map(self.h, _ptr(xsects0_dev), _ptr(xsects1_dev), n, _ptr(vertex_face0_dev), _ptr(vertex_face1_dev),
-                                   int(flags), cc, pc, fc, _ptr(xy_dev), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev),
-                                   _ptr(face_pairs_dev), _ptr(origin_dev), counts)
+        args = (self.h, _ptr(xsects0_dev), _ptr(xsects1_dev), n, _ptr(vertex_face0_dev), _ptr(vertex_face1_dev), int(flags), cc, pc, fc,
+                _ptr(xy_dev), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev), _ptr(face_pairs_dev), _ptr(origin_dev), counts)
+        rc = self.L.rj_overlay_map(*args) if op is None else self.L.rj_overlay_map_op(*args, int(op[0]), int(op[1]))
         if rc == RJ_E_OVERFLOW:
             raise MapOverflow(self.L.rj_last_error_string(self.h).decode(), tuple(counts))
         self._check(rc)

@@ -16,6 +16,7 @@
 #include "../../include/rayjoin_amd.h"
 #include "rj_kernels.h"
 #include "rj_overlay_dev.h"
+#include "rj_overlay_ops.h"
 
 using namespace rj;
 
@@ -2581,18 +2582,19 @@ int rj_overlay_edge_xsects(rj_handle h, int im, const uint32_t* pairs_dev, uint6
   return RJ_OK;
 }
 
-int rj_overlay_faces(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
-                     const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint64_t capacity,
-                     rj_overlay_face* out_dev, uint64_t* n_faces) {
+// rj_overlay_faces (op == null: the intersection's own kernels) and rj_overlay_faces_op
+static int overlay_faces_call(rj_handle h, const char* name, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                              const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint64_t capacity,
+                              rj_overlay_face* out_dev, uint64_t* n_faces, const OverlayOp* op) {
   RJ_CHECK_H(h);
-  if (!n_faces) return fail(h, RJ_E_INVALID, "rj_overlay_faces: n_faces is null");
+  if (!n_faces) return fail(h, RJ_E_INVALID, "%s: n_faces is null", name);
   *n_faces = 0;
-  if (!h->map[0].present || !h->map[1].present) return fail(h, RJ_E_INVALID, "rj_overlay_faces: both maps must be uploaded");
-  if (n && (!xsects0_dev || !xsects1_dev)) return fail(h, RJ_E_INVALID, "rj_overlay_faces: null records");
+  if (!h->map[0].present || !h->map[1].present) return fail(h, RJ_E_INVALID, "%s: both maps must be uploaded", name);
+  if (n && (!xsects0_dev || !xsects1_dev)) return fail(h, RJ_E_INVALID, "%s: null records", name);
   if ((h->map[0].np && !vertex_face0_dev) || (h->map[1].np && !vertex_face1_dev))
-    return fail(h, RJ_E_INVALID, "rj_overlay_faces: null vertex faces");
-  if (capacity && !out_dev) return fail(h, RJ_E_INVALID, "rj_overlay_faces: null output");
-  if (n >= (1ull << 32)) return fail(h, RJ_E_INVALID, "rj_overlay_faces: too many intersections");
+    return fail(h, RJ_E_INVALID, "%s: null vertex faces", name);
+  if (capacity && !out_dev) return fail(h, RJ_E_INVALID, "%s: null output", name);
+  if (n >= (1ull << 32)) return fail(h, RJ_E_INVALID, "%s: too many intersections", name);
   if (int r = set_device(h)) return r;
   RJ_HIP(h, join_aux(h));
   OverlayFacesMap m[2];
@@ -2603,31 +2605,32 @@ int rj_overlay_faces(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* x
   const rj_xsect* const xs[2] = {xsects0_dev, xsects1_dev};
   const int32_t* const vf[2] = {vertex_face0_dev, vertex_face1_dev};
   uint64_t rows = 0;
-  RJ_HIP(h, overlay_faces_device(h->stream, m, xs, n, vf, capacity, out_dev, &rows, &h->arena, &h->arena_bytes));
+  RJ_HIP(h, overlay_faces_device(h->stream, m, xs, n, vf, capacity, out_dev, &rows, &h->arena, &h->arena_bytes, op));
   *n_faces = rows;
   if (rows > capacity)
-    return fail(h, RJ_E_OVERFLOW, "rj_overlay_faces: %llu rows, capacity %llu", (unsigned long long) rows, (unsigned long long) capacity);
+    return fail(h, RJ_E_OVERFLOW, "%s: %llu rows, capacity %llu", name, (unsigned long long) rows, (unsigned long long) capacity);
   return RJ_OK;
 }
 
-int rj_overlay_map(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
-                   const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint32_t flags,
-                   uint64_t chain_capacity, uint64_t point_capacity, uint64_t face_capacity, int64_t* xy_dev,
-                   uint32_t* row_index_dev, int32_t* left_dev, int32_t* right_dev, int32_t* face_pairs_dev,
-                   uint32_t* origin_dev, rj_overlay_map_counts* counts) {
+// rj_overlay_map (op == null: the intersection's own kernels) and rj_overlay_map_op
+static int overlay_map_call(rj_handle h, const char* name, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                            const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint32_t flags,
+                            uint64_t chain_capacity, uint64_t point_capacity, uint64_t face_capacity, int64_t* xy_dev,
+                            uint32_t* row_index_dev, int32_t* left_dev, int32_t* right_dev, int32_t* face_pairs_dev,
+                            uint32_t* origin_dev, rj_overlay_map_counts* counts, const OverlayOp* op) {
   RJ_CHECK_H(h);
-  if (!counts) return fail(h, RJ_E_INVALID, "rj_overlay_map: counts is null");
+  if (!counts) return fail(h, RJ_E_INVALID, "%s: counts is null", name);
   counts->n_chains = counts->n_points = counts->n_faces = 0;
-  if (flags & ~(uint32_t) RJ_OVM_DROP_DEGENERATE) return fail(h, RJ_E_INVALID, "rj_overlay_map: unknown flags 0x%x", flags);
-  if (!h->map[0].present || !h->map[1].present) return fail(h, RJ_E_INVALID, "rj_overlay_map: both maps must be uploaded");
-  if (n && (!xsects0_dev || !xsects1_dev)) return fail(h, RJ_E_INVALID, "rj_overlay_map: null records");
+  if (flags & ~(uint32_t) RJ_OVM_DROP_DEGENERATE) return fail(h, RJ_E_INVALID, "%s: unknown flags 0x%x", name, flags);
+  if (!h->map[0].present || !h->map[1].present) return fail(h, RJ_E_INVALID, "%s: both maps must be uploaded", name);
+  if (n && (!xsects0_dev || !xsects1_dev)) return fail(h, RJ_E_INVALID, "%s: null records", name);
   if ((h->map[0].np && !vertex_face0_dev) || (h->map[1].np && !vertex_face1_dev))
-    return fail(h, RJ_E_INVALID, "rj_overlay_map: null vertex faces");
+    return fail(h, RJ_E_INVALID, "%s: null vertex faces", name);
   if ((point_capacity && !xy_dev) || (chain_capacity && (!row_index_dev || !left_dev || !right_dev)) || (face_capacity && !face_pairs_dev))
-    return fail(h, RJ_E_INVALID, "rj_overlay_map: null output");
+    return fail(h, RJ_E_INVALID, "%s: null output", name);
   // (row_index is 32-bit: every point the maps could emit must have a slot below 2^32)
   if (n >= (1ull << 32) || h->map[0].np + h->map[1].np + 4 * n >= (1ull << 32))
-    return fail(h, RJ_E_INVALID, "rj_overlay_map: too many points for a 32-bit row_index");
+    return fail(h, RJ_E_INVALID, "%s: too many points for a 32-bit row_index", name);
   if (int r = set_device(h)) return r;
   RJ_HIP(h, join_aux(h));
   OverlayFacesMap m[2];
@@ -2641,13 +2644,61 @@ int rj_overlay_map(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xse
   const OverlayMapOut out{xy_dev, row_index_dev, left_dev, right_dev, face_pairs_dev, origin_dev,
                           chain_capacity, point_capacity, face_capacity};
   uint64_t c[3] = {0, 0, 0};
-  RJ_HIP(h, overlay_map_device(h->stream, m, np, xs, n, vf, (flags & RJ_OVM_DROP_DEGENERATE) != 0, out, c, &h->arena, &h->arena_bytes));
+  RJ_HIP(h, overlay_map_device(h->stream, m, np, xs, n, vf, (flags & RJ_OVM_DROP_DEGENERATE) != 0, out, c, &h->arena, &h->arena_bytes, op));
   counts->n_chains = c[0]; counts->n_points = c[1]; counts->n_faces = c[2];
   if (c[0] > chain_capacity || c[1] > point_capacity || c[2] > face_capacity)
-    return fail(h, RJ_E_OVERFLOW, "rj_overlay_map: %llu chains, %llu points, %llu faces; capacities %llu, %llu, %llu", (unsigned long long) c[0],
+    return fail(h, RJ_E_OVERFLOW, "%s: %llu chains, %llu points, %llu faces; capacities %llu, %llu, %llu", name, (unsigned long long) c[0],
                 (unsigned long long) c[1], (unsigned long long) c[2], (unsigned long long) chain_capacity,
                 (unsigned long long) point_capacity, (unsigned long long) face_capacity);
   return RJ_OK;
+}
+
+// how / by of the _op calls: RJ_E_INVALID for a value the header does not define
+static int overlay_op(rj_handle h, const char* name, uint32_t how, uint32_t by, OverlayOp* op) {
+  RJ_CHECK_H(h);
+  if (how >= overlay::kHowCount) return fail(h, RJ_E_INVALID, "%s: unknown how %u", name, how);
+  if (by >= overlay::kByCount) return fail(h, RJ_E_INVALID, "%s: unknown by %u", name, by);
+  *op = OverlayOp{how, by};
+  return RJ_OK;
+}
+
+int rj_overlay_faces(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                     const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint64_t capacity,
+                     rj_overlay_face* out_dev, uint64_t* n_faces) {
+  return overlay_faces_call(h, "rj_overlay_faces", xsects0_dev, xsects1_dev, n, vertex_face0_dev, vertex_face1_dev, capacity, out_dev,
+                            n_faces, nullptr);
+}
+
+int rj_overlay_faces_op(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                        const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint64_t capacity,
+                        rj_overlay_face* out_dev, uint64_t* n_faces, uint32_t how, uint32_t by) {
+  OverlayOp op;
+  if (n_faces) *n_faces = 0;
+  if (int r = overlay_op(h, "rj_overlay_faces_op", how, by, &op)) return r;
+  return overlay_faces_call(h, "rj_overlay_faces_op", xsects0_dev, xsects1_dev, n, vertex_face0_dev, vertex_face1_dev, capacity, out_dev,
+                            n_faces, &op);
+}
+
+int rj_overlay_map(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                   const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint32_t flags,
+                   uint64_t chain_capacity, uint64_t point_capacity, uint64_t face_capacity, int64_t* xy_dev,
+                   uint32_t* row_index_dev, int32_t* left_dev, int32_t* right_dev, int32_t* face_pairs_dev,
+                   uint32_t* origin_dev, rj_overlay_map_counts* counts) {
+  return overlay_map_call(h, "rj_overlay_map", xsects0_dev, xsects1_dev, n, vertex_face0_dev, vertex_face1_dev, flags, chain_capacity,
+                          point_capacity, face_capacity, xy_dev, row_index_dev, left_dev, right_dev, face_pairs_dev, origin_dev, counts,
+                          nullptr);
+}
+
+int rj_overlay_map_op(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                      const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint32_t flags,
+                      uint64_t chain_capacity, uint64_t point_capacity, uint64_t face_capacity, int64_t* xy_dev,
+                      uint32_t* row_index_dev, int32_t* left_dev, int32_t* right_dev, int32_t* face_pairs_dev,
+                      uint32_t* origin_dev, rj_overlay_map_counts* counts, uint32_t how, uint32_t by) {
+  OverlayOp op;
+  if (counts) counts->n_chains = counts->n_points = counts->n_faces = 0;
+  if (int r = overlay_op(h, "rj_overlay_map_op", how, by, &op)) return r;
+  return overlay_map_call(h, "rj_overlay_map_op", xsects0_dev, xsects1_dev, n, vertex_face0_dev, vertex_face1_dev, flags, chain_capacity,
+                          point_capacity, face_capacity, xy_dev, row_index_dev, left_dev, right_dev, face_pairs_dev, origin_dev, counts, &op);
 }
 
 int rj_last_ms(rj_handle h, int which, float* ms) {

@@ -189,10 +189,15 @@ struct OverlayFacesMap {
   const uint32_t *edge_chain, *edge_begin, *left, *right;
   uint64_t ne, nc;
 };
+// An overlay operation (RJ_OV_* of include/rayjoin_amd.h; rj_overlay_ops.h has the semantics), already validated.
+struct OverlayOp {
+  uint32_t how, by;
+};
 // rows (face 0, face 1, int128 area2) ascending by key into out[<= capacity]; *n_rows = the true row count (read back
-// with the stream's one sync).  Scratch: the caller's grow-only block.
+// with the stream's one sync).  Scratch: the caller's grow-only block.  op == null: the intersection's own kernels
+// (rj_overlay_faces); else the operation's (rj_overlay_faces_op) -- every other stage is shared.
 hipError_t overlay_faces_device(hipStream_t st, const OverlayFacesMap maps[2], const rj_xsect* const xsects[2], uint64_t n,
                                 const int32_t* const vertex_face[2], uint64_t capacity, rj_overlay_face* out, uint64_t* n_rows,
-                                char** scratch, size_t* scratch_bytes);
+                                char** scratch, size_t* scratch_bytes, const OverlayOp* op = nullptr);
 
 }  // namespace rj

@@ -8,6 +8,8 @@
 //                     max_contributions() entries per map, pre-filled with a key that sorts last.
 //   2. rocPRIM radix sort of the 64-bit (face 0, face 1) keys carrying the int128 as two limbs.
 //   3. rocPRIM reduce_by_key (integer sums: exact, any order gives the same bits) and k_ovf_emit: the rows, the count.
+// rj_overlay_faces_op runs the same passes with k_ovf_contrib_op: the body of k_ovf_contrib with the selection and the face
+// keys of an overlay operation (rj_overlay_ops.h) in place of the intersection's; the operation is a kernel argument.
 // No host loop over edges, pieces or records; the host reads one word at the end.
 #include <hip/hip_runtime.h>
 
@@ -19,6 +21,7 @@
 #include "rj_kernels.h"
 #include "rj_overlay.h"
 #include "rj_overlay_dev.h"
+#include "rj_overlay_ops.h"
 
 namespace rj {
 
@@ -40,19 +43,36 @@ __device__ __forceinline__ __int128 shfl_up128(__int128 v, int d) {
   return (__int128) (((unsigned __int128) (uint64_t) hi2 << 64) | lo2);
 }
 
+// which sub-segments contribute, and to which keys: the intersection's hard-wired rule (rj_overlay.h) for rj_overlay_faces,
+// an operation (rj_overlay_ops.h) for rj_overlay_faces_op.  The operation lives in scalar registers: wave-uniform.
+struct RuleIntersection {
+  __device__ __forceinline__ int sides(int, int32_t l, int32_t r, int32_t label) const { return overlay::sides(label, l, r); }
+  template <class F>
+  __device__ __forceinline__ void emit(int im, int32_t l, int32_t r, int32_t label, __int128 v, F&& f) const {
+    overlay::emit_sides(im, l, r, label, v, f);
+  }
+};
+struct RuleOp {
+  Op op;
+  __device__ __forceinline__ int sides(int im, int32_t l, int32_t r, int32_t label) const { return overlay::sides(im, l, r, label, op); }
+  template <class F>
+  __device__ __forceinline__ void emit(int im, int32_t l, int32_t r, int32_t label, __int128 v, F&& f) const {
+    overlay::emit_sides(im, l, r, label, v, op, f);
+  }
+};
+
 // one map's contributions (kWrite 0: what each wave stores, to wave_count; 1: store them from wave_base).  Every lane of a wave runs the loop body the same number of times (lanes beyond ne take part
 // in the shuffles as empty segments).
-template <bool kWrite>
-__global__ __launch_bounds__(kThreads) void k_ovf_contrib(int im, const int64_t* __restrict__ pts, const uint32_t* __restrict__ edge_chain,
-                                                          const uint32_t* __restrict__ edge_begin, const int32_t* __restrict__ left,
-                                                          const int32_t* __restrict__ right, uint64_t ne, const Rec48* __restrict__ xs,
-                                                          uint64_t n, const int32_t* __restrict__ vertex_face, uint64_t* __restrict__ keys,
-                                                          Area2* __restrict__ vals, uint32_t* __restrict__ wave_count,
-                                                          const uint64_t* __restrict__ wave_base, uint64_t cap) {
+// (nwaves, wave0, wstride come from the kernel: with blockDim / gridDim read here the compiler fetched the launch
+//  geometry the generic way and the intersection's kernels lost 0.1 ms of 1.56 on 30.8 M edges)
+template <bool kWrite, class Rule>
+__device__ __forceinline__ void ovf_contrib(const Rule rule, uint64_t nwaves, uint64_t wave0, uint64_t wstride, int im,
+                                            const int64_t* __restrict__ pts, const uint32_t* __restrict__ edge_chain,
+                                            const uint32_t* __restrict__ edge_begin, const int32_t* __restrict__ left,
+                                            const int32_t* __restrict__ right, uint64_t ne, const Rec48* __restrict__ xs, uint64_t n,
+                                            const int32_t* __restrict__ vertex_face, uint64_t* __restrict__ keys, Area2* __restrict__ vals,
+                                            uint32_t* __restrict__ wave_count, const uint64_t* __restrict__ wave_base, uint64_t cap) {
   const int lane = threadIdx.x & 63;
-  const uint64_t nwaves = (ne + 63) / 64;
-  const uint64_t wave0 = (blockIdx.x * (uint64_t) blockDim.x + threadIdx.x) / 64;
-  const uint64_t wstride = (uint64_t) gridDim.x * blockDim.x / 64;
   for (uint64_t w = wave0; w < nwaves; w += wstride) {
     const uint64_t e0 = w * 64, e_end = e0 + 64 < ne ? e0 + 64 : ne;
     const uint64_t e = e0 + lane;
@@ -91,11 +111,11 @@ __global__ __launch_bounds__(kThreads) void k_ovf_contrib(int im, const int64_t*
     uint32_t m = 0;
     int32_t head = 0;
     if (valid) {
-      if (emit_open) m += sides(tail, l, r);
+      if (emit_open) m += rule.sides(im, l, r, tail);
       if (lo < hi) {
         head = head_label(e, c, vertex_face);
-        m += sides(head, l, r);
-        for (uint64_t k = lo; k + 1 < hi; k++) m += sides(xs[k].mid, l, r);
+        m += rule.sides(im, l, r, head);
+        for (uint64_t k = lo; k + 1 < hi; k++) m += rule.sides(im, l, r, xs[k].mid);
       }
     }
     uint32_t incl = m;
@@ -116,13 +136,42 @@ __global__ __launch_bounds__(kThreads) void k_ovf_contrib(int im, const int64_t*
       slot++;
     };
     if (m) {
-      if (emit_open) emit_sides(im, l, r, tail, s, store);
+      if (emit_open) rule.emit(im, l, r, tail, s, store);
       if (lo < hi) {
-        emit_sides(im, l, r, head, head_part(pts, e, c, xs[lo]), store);
-        for (uint64_t k = lo; k + 1 < hi; k++) emit_sides(im, l, r, xs[k].mid, middle_part(xs[k], xs[k + 1]), store);
+        rule.emit(im, l, r, head, head_part(pts, e, c, xs[lo]), store);
+        for (uint64_t k = lo; k + 1 < hi; k++) rule.emit(im, l, r, xs[k].mid, middle_part(xs[k], xs[k + 1]), store);
       }
     }
   }
+}
+
+template <bool kWrite>
+__global__ __launch_bounds__(kThreads) void k_ovf_contrib(int im, const int64_t* __restrict__ pts, const uint32_t* __restrict__ edge_chain,
+                                                          const uint32_t* __restrict__ edge_begin, const int32_t* __restrict__ left,
+                                                          const int32_t* __restrict__ right, uint64_t ne, const Rec48* __restrict__ xs,
+                                                          uint64_t n, const int32_t* __restrict__ vertex_face, uint64_t* __restrict__ keys,
+                                                          Area2* __restrict__ vals, uint32_t* __restrict__ wave_count,
+                                                          const uint64_t* __restrict__ wave_base, uint64_t cap) {
+  const uint64_t nwaves = (ne + 63) / 64;
+  const uint64_t wave0 = (blockIdx.x * (uint64_t) blockDim.x + threadIdx.x) / 64;
+  const uint64_t wstride = (uint64_t) gridDim.x * blockDim.x / 64;
+  ovf_contrib<kWrite>(RuleIntersection{}, nwaves, wave0, wstride, im, pts, edge_chain, edge_begin, left, right, ne, xs, n, vertex_face,
+                      keys, vals, wave_count, wave_base, cap);
+}
+
+// the same pass under an operation (rj_overlay_faces_op): how / by are kernel arguments
+template <bool kWrite>
+__global__ __launch_bounds__(kThreads) void k_ovf_contrib_op(int im, const int64_t* __restrict__ pts, const uint32_t* __restrict__ edge_chain,
+                                                             const uint32_t* __restrict__ edge_begin, const int32_t* __restrict__ left,
+                                                             const int32_t* __restrict__ right, uint64_t ne, const Rec48* __restrict__ xs,
+                                                             uint64_t n, const int32_t* __restrict__ vertex_face, uint64_t* __restrict__ keys,
+                                                             Area2* __restrict__ vals, uint32_t* __restrict__ wave_count,
+                                                             const uint64_t* __restrict__ wave_base, uint64_t cap, uint32_t how, uint32_t by) {
+  const uint64_t nwaves = (ne + 63) / 64;
+  const uint64_t wave0 = (blockIdx.x * (uint64_t) blockDim.x + threadIdx.x) / 64;
+  const uint64_t wstride = (uint64_t) gridDim.x * blockDim.x / 64;
+  ovf_contrib<kWrite>(RuleOp{make_op(how, by)}, nwaves, wave0, wstride, im, pts, edge_chain, edge_begin, left, right, ne, xs, n, vertex_face,
+                      keys, vals, wave_count, wave_base, cap);
 }
 
 // rows out: the unique keys but the trailing kNoKey run, at most `capacity` of them; the true count to *n_rows
@@ -156,7 +205,7 @@ hipError_t warm_overlay_kernels(hipStream_t st) {
 
 hipError_t overlay_faces_device(hipStream_t st, const OverlayFacesMap maps[2], const rj_xsect* const xsects[2], uint64_t n,
                                 const int32_t* const vertex_face[2], uint64_t capacity, rj_overlay_face* out, uint64_t* n_rows,
-                                char** scratch, size_t* scratch_bytes) {
+                                char** scratch, size_t* scratch_bytes, const OverlayOp* op) {
   uint64_t total = 0;
   for (int im = 0; im < 2; im++) total += max_contributions(maps[im].ne, maps[im].nc, n);
   size_t sort_bytes = 0, rbk_bytes = 0;
@@ -212,16 +261,26 @@ hipError_t overlay_faces_device(hipStream_t st, const OverlayFacesMap maps[2], c
     if (m.ne) {
       const uint64_t waves = (m.ne + 63) / 64;
       const dim3 grid(grid_for(64 * waves, 8192));
-      hipLaunchKernelGGL(k_ovf_contrib<false>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin, (const int32_t*) m.left,
-                         (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im], kin + at, vin + at, wcount,
-                         (const uint64_t*) nullptr, part);
+      if (op)
+        hipLaunchKernelGGL(k_ovf_contrib_op<false>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin,
+                           (const int32_t*) m.left, (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im], kin + at,
+                           vin + at, wcount, (const uint64_t*) nullptr, part, op->how, op->by);
+      else
+        hipLaunchKernelGGL(k_ovf_contrib<false>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin, (const int32_t*) m.left,
+                           (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im], kin + at, vin + at, wcount,
+                           (const uint64_t*) nullptr, part);
       if ((e = hipGetLastError()) != hipSuccess) return e;
       size_t sb = temp_bytes;
       if ((e = rocprim::exclusive_scan(temp, sb, wcount, wbase, (uint64_t) 0, (size_t) waves, rocprim::plus<uint64_t>(), st)) != hipSuccess)
         return e;
-      hipLaunchKernelGGL(k_ovf_contrib<true>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin, (const int32_t*) m.left,
-                         (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im], kin + at, vin + at, wcount,
-                         (const uint64_t*) wbase, part);
+      if (op)
+        hipLaunchKernelGGL(k_ovf_contrib_op<true>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin,
+                           (const int32_t*) m.left, (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im], kin + at,
+                           vin + at, wcount, (const uint64_t*) wbase, part, op->how, op->by);
+      else
+        hipLaunchKernelGGL(k_ovf_contrib<true>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin, (const int32_t*) m.left,
+                           (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im], kin + at, vin + at, wcount,
+                           (const uint64_t*) wbase, part);
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     at += part;

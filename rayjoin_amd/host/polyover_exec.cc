@@ -9,6 +9,10 @@
 //   -output_map <path> (ours): the output map computed on the device (rj_overlay_map) and written as a CDB file: the
 //   device map's chains and points (unscaled, "%.6f"), its ordered-pair face ids, end points numbered over the distinct
 //   scaled end points in order of first use.  -output stays the host writer's file.
+//   -how intersection|union|difference|symmetric_difference|identity, -by pair|map0|map1 (ours): the overlay operation
+//   of -face_table and -output_map (rj_overlay_faces_op / rj_overlay_map_op): which (face of map 0, face of map 1) pairs
+//   are faces of the result and what names a face; a face id in the files may then be 0 ("outside that map").  Without
+//   either flag the two files are the intersection's (the calls without _op), byte for byte what they were.
 #include <iostream>
 #include <unordered_map>
 
@@ -25,6 +29,20 @@ class MapOverlayLBVH {
  public:
   MapOverlayLBVH(Context& ctx, double xsect_factor, bool grid = false, int grid_size = 2048, bool keep_xsects = false)
       : ctx_(ctx), xsect_factor_(xsect_factor), grid_(grid), grid_size_(grid_size), keep_xsects_(keep_xsects) {}
+  // -how / -by: the files of -face_table / -output_map come from the _op calls
+  void SetOperation(const std::string& how, const std::string& by) {
+    static const char* hows[] = {"intersection", "union", "difference", "symmetric_difference", "identity"};
+    static const char* bys[] = {"pair", "map0", "map1"};
+    auto index = [](const std::string& v, const char* const* names, int n, const char* flag) {
+      if (v.empty()) return 0u;
+      for (int i = 0; i < n; i++)
+        if (v == names[i]) return (uint32_t) i;
+      throw std::invalid_argument(std::string("bad value '") + v + "' for -" + flag);
+    };
+    how_ = index(how, hows, 5, "how");
+    by_ = index(by, bys, 3, "by");
+    use_op_ = !how.empty() || !by.empty();
+  }
   ~MapOverlayLBVH() {
     rj_handle h = ctx_.handle();
     if (pairs_) rj_dev_free(h, pairs_);
@@ -90,7 +108,8 @@ class MapOverlayLBVH {
     for (int attempt = 0; attempt < 2; attempt++) {
       rj_overlay_face* d = nullptr;
       rj_check(h, rj_dev_alloc(h, sizeof(rj_overlay_face) * cap, (void**) &d), "rj_dev_alloc");
-      int rc = rj_overlay_faces(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], cap, d, &n);
+      int rc = use_op_ ? rj_overlay_faces_op(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], cap, d, &n, how_, by_)
+                       : rj_overlay_faces(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], cap, d, &n);
       if (rc == RJ_E_OVERFLOW && attempt == 0) {
         rj_dev_free(h, d);
         cap = n;
@@ -119,8 +138,14 @@ class MapOverlayLBVH {
   void ComputeOutputMap() {
     rj_handle h = ctx_.handle();
     rj_overlay_map_counts c;
-    int rc = rj_overlay_map(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], 0, 0, 0, 0, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, nullptr, &c);
+    auto overlay_map = [&](uint64_t cc, uint64_t pc, uint64_t fc, int64_t* xy, uint32_t* row, int32_t* left, int32_t* right,
+                           int32_t* pairs) {
+      return use_op_ ? rj_overlay_map_op(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], 0, cc, pc, fc, xy, row, left,
+                                         right, pairs, nullptr, &c, how_, by_)
+                     : rj_overlay_map(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], 0, cc, pc, fc, xy, row, left, right,
+                                      pairs, nullptr, &c);
+    };
+    int rc = overlay_map(0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
     if (rc != RJ_E_OVERFLOW) rj_check(h, rc, "rj_overlay_map");
     int64_t* xy = nullptr;
     uint32_t* row = nullptr;
@@ -130,8 +155,7 @@ class MapOverlayLBVH {
     rj_check(h, rj_dev_alloc(h, 4 * (c.n_chains ? c.n_chains : 1), (void**) &left), "rj_dev_alloc");
     rj_check(h, rj_dev_alloc(h, 4 * (c.n_chains ? c.n_chains : 1), (void**) &right), "rj_dev_alloc");
     rj_check(h, rj_dev_alloc(h, 8 * (c.n_faces ? c.n_faces : 1), (void**) &pairs), "rj_dev_alloc");
-    rc = rj_overlay_map(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], 0, c.n_chains, c.n_points, c.n_faces, xy, row,
-                        left, right, pairs, nullptr, &c);
+    rc = overlay_map(c.n_chains, c.n_points, c.n_faces, xy, row, left, right, pairs);
     om_xy_.resize(2 * c.n_points);
     om_row_.resize(c.n_chains + 1);
     om_left_.resize(c.n_chains);
@@ -216,6 +240,8 @@ class MapOverlayLBVH {
   bool grid_;
   int grid_size_;
   bool keep_xsects_;
+  bool use_op_ = false;
+  uint32_t how_ = 0, by_ = 0;
   size_t cap_ = 0, n_xsects_ = 0;
   rj_xsect* xsects_dev_[2] = {nullptr, nullptr};
   std::vector<rj_overlay_face> face_rows_;
@@ -238,6 +264,7 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
   tm.next("Create App");
   Context ctx({g1, g2}, f.device, f.scale_fma);
   MapOverlayLBVH overlay(ctx, f.xsect_factor, f.mode == "grid", f.grid_size, !f.face_table.empty() || !f.output_map.empty());
+  overlay.SetOperation(f.how, f.by);
   tm.next("Load Data");
   ctx.LoadToDevice();
   tm.next("Init");
@@ -284,7 +311,9 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
 int main(int argc, char* argv[]) {
   if (argc == 1) {
     std::cerr << "Usage: " << argv[0] << " -poly1 <map0.cdb> -poly2 <map1.cdb> -mode lbvh|grid [-grid_size 2048] [-output <result.cdb>]\n"
-              << "  [-serialize <dir>] [-xsect_factor 0.2] [-check] [-device 0] [-v 1]\n";
+              << "  [-serialize <dir>] [-xsect_factor 0.2] [-check] [-device 0] [-v 1]\n"
+              << "  [-face_table <rows.txt>] [-output_map <map.cdb>] [-how intersection|union|difference|symmetric_difference|identity]\n"
+              << "  [-by pair|map0|map1]\n";
     return 1;
   }
   Flags f;

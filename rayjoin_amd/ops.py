@@ -13,7 +13,8 @@
       .ComputeOutputPolygons(); .get_xsects(im); .FaceTable(); .OutputMap()
       -- src/app/map_overlay.h:19-29, src/app/map_overlay_lbvh.h:25-265 (grid_size: MapOverlayGrid);
          FaceTable is the overlay's answer computed on the device (rj_overlay_faces), OutputMap the output map as
-         device arrays (rj_overlay_map); DeviceContext.InstallMap makes one an input map again (rj_upload_map_dev)
+         device arrays (rj_overlay_map); DeviceContext.InstallMap makes one an input map again (rj_upload_map_dev);
+         how= / by= on both choose another overlay operation: union, difference, ..., clip (rj_overlay_*_op)
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -260,16 +261,21 @@ class MapOverlay:
     def get_vertex_faces(self, im):
         return self.faces[im].to_host(np.int32, self.ctx_.get_map(im).n_points)
 
-    def FaceTable(self, capacity=None):
+    def FaceTable(self, capacity=None, how="intersection", by="pair"):
         """rows (face0, face1, area2, area) ascending by (face0, face1): area2 is twice the overlap's signed area in
-        scaled units^2, exact (a Python int); area is in input units (area2 / 2 * rrx * rry of the context's Scaling)."""
+        scaled units^2, exact (a Python int); area is in input units (area2 / 2 * rrx * rry of the context's Scaling).
+        how ("intersection", "union", "difference", "symmetric_difference", "identity") selects the (face of map 0, face
+        of map 1) pairs that are faces of the result, by ("pair", "map0", "map1") what names a face (rj_overlay_faces_op):
+        with another how a row's face may be 0 ("outside that map"), with by="map0" face1 is always 0.  The defaults
+        are rj_overlay_faces."""
         if not (self.located[0] and self.located[1]) or self.xsects[0] is None:
             raise RuntimeError("MapOverlay.FaceTable needs LocateVerticesInOtherMap(0), (1) and ComputeOutputPolygons() first")
+        op = overlay_op(how, by)
         cap = int(capacity) if capacity is not None else max(64, 2 * self.n_xsects + 64)
         while True:
             out = self.h.alloc(_capi.FACE_DTYPE.itemsize * max(1, cap))
             try:
-                n = self.h.overlay_faces(self.xsects[0], self.xsects[1], self.n_xsects, self.faces[0], self.faces[1], cap, out)
+                n = self.h.overlay_faces(self.xsects[0], self.xsects[1], self.n_xsects, self.faces[0], self.faces[1], cap, out, op)
                 break
             except _capi.QueueOverflow as e:
                 if capacity is not None:
@@ -280,26 +286,29 @@ class MapOverlay:
         out.free()
         return face_table_from_rows(raw, self.ctx_.ctx.scaling)
 
-    def OutputMap(self, drop_degenerate=False, capacities=None):
+    def OutputMap(self, drop_degenerate=False, capacities=None, how="intersection", by="pair"):
         """The output map as a DeviceOutputMap (rj_overlay_map): the pieces the CDB writer keeps, in its order, in scaled
         integers, faces numbered by the ordered pair (face of map 0, face of map 1) -- face k is row k - 1 of
         FaceTable().  drop_degenerate leaves out the pieces with fewer than two points (what an input map may not have:
         DeviceContext.InstallMap).  capacities = (chains, points, faces): MapOverflow with the true counts when one is
-        too small; left open, a sizing call finds them."""
+        too small; left open, a sizing call finds them.  how / by as FaceTable (rj_overlay_map_op): a piece is kept
+        when the faces on its two sides differ; how="intersection", by="map0" clips map 0 to where map 1 covers and
+        keeps map 0's face ids (face_pairs[k - 1] = (f0, 0)); adjacent pieces of one chain are not merged."""
         if not (self.located[0] and self.located[1]) or self.xsects[0] is None:
             raise RuntimeError("MapOverlay.OutputMap needs LocateVerticesInOtherMap(0), (1) and ComputeOutputPolygons() first")
         flags = _capi.RJ_OVM_DROP_DEGENERATE if drop_degenerate else 0
+        op = overlay_op(how, by)
         args = (self.xsects[0], self.xsects[1], self.n_xsects, self.faces[0], self.faces[1], flags)
         if capacities is None:
             try:
-                capacities = self.h.overlay_map(*args, (0, 0, 0), None, None, None, None, None, None)
+                capacities = self.h.overlay_map(*args, (0, 0, 0), None, None, None, None, None, None, op=op)
             except _capi.MapOverflow as e:
                 capacities = e.counts
         cc, pc, fc = (int(v) for v in capacities)
         bufs = [self.h.alloc(16 * max(1, pc)), self.h.alloc(4 * (cc + 1)), self.h.alloc(4 * max(1, cc)), self.h.alloc(4 * max(1, cc)),
                 self.h.alloc(8 * max(1, fc)), self.h.alloc(4 * max(1, cc))]
         try:
-            counts = self.h.overlay_map(*args, (cc, pc, fc), *bufs)
+            counts = self.h.overlay_map(*args, (cc, pc, fc), *bufs, op=op)
         except _capi.RayJoinError:
             for b in bufs:
                 b.free()
@@ -327,6 +336,17 @@ class DeviceOutputMap:
     def free(self):
         for b in (self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin):
             b.free()
+
+
+def overlay_op(how, by):
+    """(how, by) names -> the RJ_OV_* pair of the _op calls; None for the defaults (the calls without _op)"""
+    if how not in _capi.OVERLAY_HOW:
+        raise ValueError("how must be one of %s, not %r" % (sorted(_capi.OVERLAY_HOW), how))
+    if by not in _capi.OVERLAY_BY:
+        raise ValueError("by must be one of %s, not %r" % (sorted(_capi.OVERLAY_BY), by))
+    if how == "intersection" and by == "pair":
+        return None
+    return _capi.OVERLAY_HOW[how], _capi.OVERLAY_BY[by]
 
 
 def face_table_from_rows(raw, scaling):
