@@ -3,6 +3,7 @@
 Beside that test's loop it draws the round-6 knobs at random -- the second order of steep leaf blocks on / off, one or two
 query segments per lane, the column index auto / off / forced, and a small "lazy_columns_min" so that an incoherent vertex
 set builds the index at its first query -- and checks LSI pairs, closest edges and face ids against the brute-force oracle.
+The overlay on random pairs has a sibling of its own: tests/overlay_fuzz_more.py.
 Test infrastructure (it imports oracle/): not collected by pytest, not part of the product."""
 import os
 import sys

@@ -11,10 +11,11 @@ from rayjoin_amd import _capi, maps, synth
 pytestmark = pytest.mark.gpu
 
 
-def _maps(rng):
-    """a generator's output that is a planar graph the loader accepts (chains of >= 2 points: planar_graph.h:71)"""
+def _maps(rng, draw=None):
+    """a generator's output that is a planar graph the loader accepts (chains of >= 2 points: planar_graph.h:71);
+    draw: another draw of the same kinds (tests/test_gpu_overlay_fuzz.py draws them smaller)"""
     while True:
-        g = _draw(rng)
+        g = (draw or _draw)(rng)
         probe = maps.Context([g]).load().maps[0]
         if probe.n_edges > 0 and np.all(np.diff(probe.row_index) >= 2) and np.all(np.isfinite(probe.pts.astype(np.float64))):
             return g
