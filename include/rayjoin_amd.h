@@ -417,6 +417,10 @@ int rj_last_stats(rj_handle h, uint64_t stats[16]);
  *                                             own where the tree walk first sorts the points and still shares little (8.4 M
  *                                             random points: 1.07 -> 0.70 ms USCounty, 1.9 -> 0.43 LakesNA; that query pays the
  *                                             build).  rj_get_plan's index[].columns_why says which rule applied.
+ *                                             A map with a segment over more than 1024 strips (an edge as long as the
+ *                                             domain) gets no column index, under 1 too: the build returns RJ_OK, the
+ *                                             tree serves the map alone, "pip_columns_used" reads 0 and columns_why
+ *                                             says "wanted, not built".
  *                                             (Environment RJ_PIP_COLUMNS=0/1 changes the default: A/B runs.)
  * "leaf_ysort"       1 / 0                    the order inside a leaf block on the NEXT rj_build_lbvh.  Blocks lie sorted by x0 with
  *                                             a bucket table on x (what an upward ray needs).  1: a block TALLER than wide also gets

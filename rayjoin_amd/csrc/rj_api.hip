@@ -1236,7 +1236,7 @@ static int build_strips(rj_handle h, BvhState& b, bool with_sky) {
   if (with_sky) RJ_HIP(h, hipMemsetAsync(b.sky, 0, ((size_t) kSkyBuckets + 1) * 4, h->stream));
   RJ_HIP(h, launch_strip_fill(h->stream, b.box0, b.seid, b.sface, cnt, offs, b.n0p, shift, total, key, slot_sorted, key_tmp, slot_tmp, tall_tmp,
                               b.strip_ytab, b.strip_box, b.strip_info, b.strip_tall, with_sky ? b.sky : nullptr, temp, tb));
-  b.use_sky = with_sky;
+  if (with_sky) b.use_sky = true;  // (the lazy build at a query passes false: a skyline the map's build filled stays in use)
   b.strip_shift = shift;
   b.strip_entries = total;
   b.strips_built = true;

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""More seeds of tests/test_gpu_fuzz.py's generator, by hand (GPU box):  python tests/fuzz_more.py [first_seed [count]]
+"""More seeds of tests/test_gpu_fuzz.py's generator, by hand (GPU box):  python tests/fuzz_more.py [--skewed] [first_seed [count]]
+--skewed runs tests/test_gpu_skewed.py's generator instead: each map 2-4 parts in random disjoint boxes whose areas span two
+orders of magnitude, a frame around the domain one time in three (three pairs per seed, against brute force).
 Beside that test's loop it draws the round-6 knobs at random -- the second order of steep leaf blocks on / off, one or two
 query segments per lane, the column index auto / off / forced, and a small "lazy_columns_min" so that an incoherent vertex
 set builds the index at its first query -- and checks LSI pairs, closest edges and face ids against the brute-force oracle.
@@ -16,10 +18,19 @@ from oracle import rjoracle as oracle  # noqa: E402
 from rayjoin_amd import _capi, maps  # noqa: E402
 from test_gpu_fuzz import _maps  # noqa: E402
 
-first = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
-count = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+args = [a for a in sys.argv[1:] if a != "--skewed"]
+first = int(args[0]) if len(args) > 0 else 1000
+count = int(args[1]) if len(args) > 1 else 20
 oracle.lib().rjo_set_num_threads(16)
 done = 0
+if "--skewed" in sys.argv[1:]:
+    from test_gpu_skewed import fuzz_one
+    for seed in range(first, first + count):
+        rng = np.random.default_rng(seed)
+        for k in range(3):
+            print("seed %d pair %d: (edges, edges, intersections, maps with a frame) = %s" % (seed, k, fuzz_one(oracle, rng, (seed, k))), flush=True)
+    print("all %d seeds ok" % count)
+    sys.exit(0)
 for seed in range(first, first + count):
     rng = np.random.default_rng(seed)
     for _ in range(3):

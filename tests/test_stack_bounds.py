@@ -140,6 +140,27 @@ def test_partial_child_subsets_stay_below_the_bound(pop_two):
     assert 64 + per(64) * (c["kMaxTop"] - 1) <= (c["kStackEntries"] if pop_two else c["kPipStack"])
 
 
+def test_lsi_start_one_level_lower_stays_within_the_stack():
+    """DeviceBvh::lsi_root: where the top level holds at most 4 nodes the LSI traversals start from the <= 128 entries of
+    level top - 1, two pops per step.  For EVERY top a tree may have: fewer start entries than 128 with all children pushed,
+    arbitrary subsets of the children from 128 by random search, and -- the same start scaled to a small fanout, 2 f entries -- every
+    subset choice exhaustively.  The peak stays within kStackEntries and within the bound the header derives."""
+    import random
+    c = _consts()
+    rng = random.Random(11)
+    for top in range(2, c["kMaxTop"] + 1):
+        bound = 128 + 126 * (top - 2)
+        assert bound <= 64 + 126 * (top - 1) <= c["kStackEntries"]
+        for k_start in (1, 2, 65, 127):   # (128 itself, all children pushed: test_stack_capacities_cover_the_worst_case)
+            peak, done = _simulate(top - 1, k_start, True, 400_000)
+            assert peak <= k_start + 126 * (top - 2) <= bound, (top, k_start, peak)
+            assert done or top > 3
+        for _ in range(8):
+            assert _simulate_partial(top - 1, 128, True, 64, rng, 20000) <= bound, top
+    for fanout, top in ((2, 2), (2, 3), (2, 4), (2, 5), (3, 3), (3, 4)):
+        assert _exhaustive_partial(top - 1, 2 * fanout, True, fanout) <= 2 * fanout + (2 * fanout - 2) * (top - 2), (fanout, top)
+
+
 def test_lds_budget_keeps_the_occupancy():
     """k_lsi: stack + 2 x 128 pair buffers per wave; k_pip: 16-byte entries + candidate lists
     (+ the block's four 8-byte chunk ranges).
