@@ -294,6 +294,7 @@ int rj_overlay_faces(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* x
 
 /* rj_overlay_map flags */
 #define RJ_OVM_DROP_DEGENERATE 1u /* leave out the pieces with fewer than two points, together with their points */
+#define RJ_OVM_MERGE_PIECES    2u /* adjacent pieces of one source chain with equal faces that touch leave as one chain */
 
 typedef struct {
   uint64_t n_chains, n_points, n_faces;
@@ -314,6 +315,17 @@ typedef struct {
  *   origin_dev[k] = (im << 31) | the chain of map im piece k was cut from; may be NULL.
  * RJ_OVM_DROP_DEGENERATE leaves out the pieces with fewer than two points (a cut on a vertex of its own chain) and their
  * points -- what rj_upload_map_dev needs; the faces and their numbers do not change with it.
+ * RJ_OVM_MERGE_PIECES returns merge(M), M being the map the same call returns without the flag (so
+ * RJ_OVM_DROP_DEGENERATE, when set, is applied first).  Chain k > 0 of M JOINS chain k - 1 when origin[k] == origin[k - 1],
+ * left[k] == left[k - 1], right[k] == right[k - 1] and the last point of chain k - 1 equals the first point of chain k
+ * (both integer coordinates).  A rule on M's arrays: two kept pieces with a dropped piece between them merge exactly when
+ * they touch.  The chains of merge(M) are the maximal runs of joined chains, in M's order; a run's points are its chains'
+ * points in order without the first point of every joining chain (the duplicate of the point before it); left, right,
+ * origin are the run's common values; face_pairs, n_faces and the face numbers do not change; counts holds the merged
+ * n_chains and n_points (also in the sizing call and with RJ_E_OVERFLOW).  Without RJ_OVM_DROP_DEGENERATE one-point
+ * pieces take part by the same rule (a run of them on one point becomes a one-point chain); with both flags no chain has
+ * fewer than two points.  NOT merged: the last piece of a closed source chain with its first (the seam stays a chain
+ * boundary), and pieces of different source chains, whatever their faces.  Another flag bit is RJ_E_INVALID.
  * Caller-owned device memory: xy_dev[2 point_capacity], row_index_dev[chain_capacity + 1], left_dev, right_dev,
  * origin_dev[chain_capacity], face_pairs_dev[2 face_capacity].  RJ_E_OVERFLOW when a count exceeds its capacity:
  * *counts holds the three true counts and nothing beyond any capacity is written; all capacities 0 (arrays may be
@@ -340,9 +352,9 @@ int rj_overlay_map(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* xse
 #define RJ_OV_BY_MAP1 2u /* (0, f1) */
 /* A side's key is by(f0, f1) when the pair is selected and the key is not (0, 0), else "no face".  A piece is kept when
  * the keys of its two sides differ (so at least one side has a face; a piece with the same face on both sides after a
- * dissolve is dropped).  Adjacent kept pieces of one chain are not merged.  Everything else is as the call without _op
+ * dissolve is dropped).  Adjacent kept pieces of one chain stay apart unless RJ_OVM_MERGE_PIECES is set.  Everything else is as the call without _op
  * documents: piece order, points, duplicate removal, faces numbered from 1 ascending by ((uint32)f0 << 32) | (uint32)f1
- * of the KEY, RJ_OVM_DROP_DEGENERATE, RJ_E_OVERFLOW with the true counts, the sizing call, n == 0.
+ * of the KEY, RJ_OVM_DROP_DEGENERATE, RJ_OVM_MERGE_PIECES, RJ_E_OVERFLOW with the true counts, the sizing call, n == 0.
  * The face table: a kept piece adds +cross per point pair to its left key and -cross to its right key; one row per key
  * with a contribution, face[] holding the key -- so a face id may be 0 here: (f0, 0) is "f0 outside map 1" under
  * BY_PAIR and "the selected part of f0" under BY_MAP0.  Under (RJ_OV_UNION, RJ_OV_BY_PAIR) the rows (f, *) sum to

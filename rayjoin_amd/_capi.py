@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("RAYJOIN_AMD_LIB") or os.path.join(HERE, "librayjoin_a
 RJ_OK, RJ_E_INVALID, RJ_E_HIP, RJ_E_OVERFLOW, RJ_E_NOMEM, RJ_E_INTERNAL = 0, 1, 2, 3, 4, 5
 RJ_EXCHANGE_HEAD_WORDS = 4
 RJ_OVM_DROP_DEGENERATE = 1  # rj_overlay_map flags
+RJ_OVM_MERGE_PIECES = 2
 # rj_overlay_faces_op / rj_overlay_map_op: which (face of map 0, face of map 1) pairs are faces, and what names a face
 RJ_OV_INTERSECTION, RJ_OV_UNION, RJ_OV_DIFFERENCE, RJ_OV_SYMDIFF, RJ_OV_IDENTITY = 0, 1, 2, 3, 4
 RJ_OV_BY_PAIR, RJ_OV_BY_MAP0, RJ_OV_BY_MAP1 = 0, 1, 2

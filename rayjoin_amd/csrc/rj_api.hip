@@ -2621,7 +2621,7 @@ static int overlay_map_call(rj_handle h, const char* name, const rj_xsect* xsect
   RJ_CHECK_H(h);
   if (!counts) return fail(h, RJ_E_INVALID, "%s: counts is null", name);
   counts->n_chains = counts->n_points = counts->n_faces = 0;
-  if (flags & ~(uint32_t) RJ_OVM_DROP_DEGENERATE) return fail(h, RJ_E_INVALID, "%s: unknown flags 0x%x", name, flags);
+  if (flags & ~(uint32_t) (RJ_OVM_DROP_DEGENERATE | RJ_OVM_MERGE_PIECES)) return fail(h, RJ_E_INVALID, "%s: unknown flags 0x%x", name, flags);
   if (!h->map[0].present || !h->map[1].present) return fail(h, RJ_E_INVALID, "%s: both maps must be uploaded", name);
   if (n && (!xsects0_dev || !xsects1_dev)) return fail(h, RJ_E_INVALID, "%s: null records", name);
   if ((h->map[0].np && !vertex_face0_dev) || (h->map[1].np && !vertex_face1_dev))
@@ -2644,7 +2644,8 @@ static int overlay_map_call(rj_handle h, const char* name, const rj_xsect* xsect
   const OverlayMapOut out{xy_dev, row_index_dev, left_dev, right_dev, face_pairs_dev, origin_dev,
                           chain_capacity, point_capacity, face_capacity};
   uint64_t c[3] = {0, 0, 0};
-  RJ_HIP(h, overlay_map_device(h->stream, m, np, xs, n, vf, (flags & RJ_OVM_DROP_DEGENERATE) != 0, out, c, &h->arena, &h->arena_bytes, op));
+  RJ_HIP(h, overlay_map_device(h->stream, m, np, xs, n, vf, (flags & RJ_OVM_DROP_DEGENERATE) != 0, (flags & RJ_OVM_MERGE_PIECES) != 0, out, c,
+                               &h->arena, &h->arena_bytes, op));
   counts->n_chains = c[0]; counts->n_points = c[1]; counts->n_faces = c[2];
   if (c[0] > chain_capacity || c[1] > point_capacity || c[2] > face_capacity)
     return fail(h, RJ_E_OVERFLOW, "%s: %llu chains, %llu points, %llu faces; capacities %llu, %llu, %llu", name, (unsigned long long) c[0],

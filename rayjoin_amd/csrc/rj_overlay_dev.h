@@ -58,11 +58,12 @@ struct OverlayMapOut {
   uint64_t chain_cap, point_cap, face_cap;
 };
 // np[im]: points of map im; counts = {chains, points, faces}, the true counts (read back with the stream's one sync);
-// nothing is written beyond a capacity.  drop: leave out the pieces with fewer than two points.  op == null: the
+// nothing is written beyond a capacity.  drop: leave out the pieces with fewer than two points.  merge: adjacent pieces
+// that join (pieces_join, rj_overlay_map.h) leave as one chain, after drop.  op == null: the
 // intersection's own emit kernels (rj_overlay_map); else the operation's (rj_overlay_map_op) -- every other stage is shared.
 hipError_t overlay_map_device(hipStream_t st, const OverlayFacesMap maps[2], const uint64_t np[2], const rj_xsect* const xsects[2], uint64_t n,
-                              const int32_t* const vertex_face[2], bool drop, const OverlayMapOut& out, uint64_t counts[3], char** scratch,
-                              size_t* scratch_bytes, const OverlayOp* op = nullptr);
+                              const int32_t* const vertex_face[2], bool drop, bool merge, const OverlayMapOut& out, uint64_t counts[3],
+                              char** scratch, size_t* scratch_bytes, const OverlayOp* op = nullptr);
 
 // rj_upload_map_dev's checks in one kernel (nc > 0): *status = 0 or the first failure in rj_upload_map's order; also
 // fills edge_begin[nc + 1] (row_index[c] - c), valid when *status == 0.  Synchronises the stream.

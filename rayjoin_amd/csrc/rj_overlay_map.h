@@ -65,6 +65,18 @@ RJ_OHD void edge_emit(int im, uint64_t e, uint32_t c, uint64_t lo, uint64_t hi, 
 // the two face keys of a kept piece (kNoKey: no face on that side)
 RJ_OHD uint64_t side_key(int im, int32_t mine, int32_t label) { return mine != 0 ? face_key(im, mine, label) : kNoKey; }
 
+// RJ_OVM_MERGE_PIECES, the join rule: chain b of the (unmerged) output map joins chain a, the chain before it, when
+// both were cut from the same source chain (origin), have the same face on either side and b begins on the point a
+// ends on (integer equality).  A rule on the arrays alone: whether a and b were neighbours on the source chain does not
+// enter.  Side: a face id of the output map, or the face key it is the rank of (equal keys <=> equal ids).
+// last_a / first_b: x, y of a's last and b's first point.
+// This function is the source both k_ovm_join and the host twin (tests/hosttwin/overlay_merge_twin.cc) run.
+template <class Side>
+RJ_OHD bool pieces_join(uint32_t origin_a, Side left_a, Side right_a, const int64_t* last_a, uint32_t origin_b, Side left_b, Side right_b,
+                        const int64_t* first_b) {
+  return origin_a == origin_b && left_a == left_b && right_a == right_b && last_a[0] == first_b[0] && last_a[1] == first_b[1];
+}
+
 // what one map can emit at most: a piece per chain and per record, every vertex and every cut point twice
 RJ_OHD uint64_t max_pieces(uint64_t nc, uint64_t n) { return nc + n; }
 RJ_OHD uint64_t max_points(uint64_t np, uint64_t n) { return np + 2 * n; }

@@ -9,6 +9,10 @@
 //   5. k_ovm_label        left / right of every piece by binary search, face_pairs, the counts.
 // RJ_OVM_DROP_DEGENERATE: 3 stores into scratch (with the piece of every point), k_ovm_keep flags the pieces with at
 // least two points, a second scan gives the kept pieces their slots, k_ovm_label / k_ovm_compact_points move them out.
+// RJ_OVM_MERGE_PIECES (rj_overlay_map.h: pieces_join) takes the same staging: k_ovm_join gives every staged piece
+// (points it adds, 1 when it starts a chain) -- with RJ_OVM_DROP_DEGENERATE against the kept piece before it, which a
+// max-scan of the kept pieces' indices finds --, one scan of those gives a piece its chain and its first point slot,
+// k_ovm_merge_label / k_ovm_merge_points move the run starts and the points out: once, whether or not pieces are dropped.
 // rj_overlay_map_op runs the same passes with k_ovm_emit_op: the body of k_ovm_emit with the pieces and the face keys of an
 // overlay operation (rj_overlay_ops.h) in place of the intersection's; the operation is a kernel argument.
 // No host loop over edges, pieces or records; the host reads the three counts at the end.
@@ -17,6 +21,9 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
+#include <rocprim/functional.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 #include "../../include/rayjoin_amd.h"
 #include "rj_kernels.h"
@@ -239,6 +246,98 @@ __global__ __launch_bounds__(kThreads) void k_ovm_compact_points(const int64_t* 
   }
 }
 
+// ---- RJ_OVM_MERGE_PIECES ------------------------------------------------------------------------------------------
+// staged piece i -> i + 1 when RJ_OVM_DROP_DEGENERATE keeps it, else 0: the exclusive max-scan of these is, per piece,
+// 1 + the kept piece before it (0: none)
+struct KeptIndex {
+  const uint32_t* row;
+  const Slots* totals;
+  __host__ __device__ uint32_t operator()(uint32_t i) const {
+    return (uint64_t) i < totals->chains && row[i + 1] - row[i] >= 2 ? i + 1 : 0;
+  }
+};
+using KeptIndexIt = rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, KeptIndex, uint32_t>;
+
+// per staged piece: (the points it adds, 1 when it starts a chain of the merged map).  A piece that joins the one before
+// it (pieces_join, rj_overlay_map.h) adds its points but the first and starts nothing; kDrop: a piece with fewer than two
+// points adds nothing, and "before" is prev_kept[i] - 1.  Zeros beyond the pieces.
+// (a piece has at least one point, so (0 or more points, no start) always means: leave out the piece's first point)
+template <bool kDrop>
+__global__ __launch_bounds__(kThreads) void k_ovm_join(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ row,
+                                                       const uint32_t* __restrict__ origin, const int64_t* __restrict__ xy,
+                                                       const uint32_t* __restrict__ prev_kept, const Slots* __restrict__ totals,
+                                                       uint64_t bound, Slots* __restrict__ adds) {
+  const uint64_t nch = totals->chains;
+  for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < bound; i += (uint64_t) gridDim.x * blockDim.x) {
+    Slots s{0, 0};
+    if (i < nch) {
+      const uint32_t first = row[i];
+      const uint64_t len = (uint64_t) (row[i + 1] - first);
+      if (!kDrop || len >= 2) {
+        const uint64_t before = kDrop ? (uint64_t) prev_kept[i] : i;  // 1 + the piece before; 0: none
+        bool join = false;
+        if (before) {
+          const uint64_t a = before - 1;
+          const uint64_t last = (uint64_t) row[a + 1] - 1;
+          join = pieces_join(origin[a], keys[2 * a], keys[2 * a + 1], xy + 2 * last, origin[i], keys[2 * i], keys[2 * i + 1],
+                             xy + 2 * (uint64_t) first);
+        }
+        s = join ? Slots{len - 1, 0} : Slots{len, 1};
+      }
+    }
+    adds[i] = s;
+  }
+}
+
+// k_ovm_label for the merged map: the pieces that start a chain carry its row_index entry, faces and origin
+__global__ __launch_bounds__(kThreads) void k_ovm_merge_label(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ ukeys,
+                                                               const uint64_t* __restrict__ n_unique, const Slots* __restrict__ totals,
+                                                               const uint32_t* __restrict__ staged_origin, const Slots* __restrict__ adds,
+                                                               const Slots* __restrict__ adds_base, OverlayMapOut out,
+                                                               uint64_t* __restrict__ counts) {
+  const uint64_t nf = face_count(ukeys, *n_unique), nch = totals->chains;
+  const uint64_t i0 = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x, stride = (uint64_t) gridDim.x * blockDim.x;
+  if (i0 == 0) {
+    const Slots t = nch ? SlotsSum()(adds_base[nch - 1], adds[nch - 1]) : Slots{0, 0};
+    if (out.row_index && t.chains <= out.chain_cap) out.row_index[t.chains] = (uint32_t) t.points;
+    counts[0] = t.chains;
+    counts[1] = t.points;
+    counts[2] = nf;
+  }
+  for (uint64_t i = i0; i < nch; i += stride) {
+    if (!adds[i].chains) continue;
+    const uint64_t to = adds_base[i].chains;
+    if (to >= out.chain_cap) continue;
+    out.left[to] = face_id(ukeys, nf, keys[2 * i]);
+    out.right[to] = face_id(ukeys, nf, keys[2 * i + 1]);
+    out.row_index[to] = (uint32_t) adds_base[i].points;
+    if (out.origin) out.origin[to] = staged_origin[i];
+  }
+  const uint64_t lim = nf < out.face_cap ? nf : out.face_cap;
+  for (uint64_t i = i0; i < lim; i += stride) {
+    out.face_pairs[2 * i] = (int32_t) (uint32_t) (ukeys[i] >> 32);
+    out.face_pairs[2 * i + 1] = (int32_t) (uint32_t) ukeys[i];
+  }
+}
+
+// the staged points to their places in the merged map: a lane per point, its 16 bytes in one load and one store,
+// consecutive lanes on consecutive points (of a run: consecutive slots too).  The first point of a piece that starts no
+// chain stays behind: the duplicate of the point before it, or the one point of a dropped piece.
+typedef long long Point16 __attribute__((ext_vector_type(2), aligned(8)));  // (the caller's xy is an int64 array)
+__global__ __launch_bounds__(kThreads) void k_ovm_merge_points(const int64_t* __restrict__ staged_xy, const uint32_t* __restrict__ staged_row,
+                                                               const uint32_t* __restrict__ point_piece, const Slots* __restrict__ totals,
+                                                               const Slots* __restrict__ adds, const Slots* __restrict__ adds_base,
+                                                               int64_t* __restrict__ xy, uint64_t point_cap) {
+  const uint64_t np = totals->points;
+  for (uint64_t j = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; j < np; j += (uint64_t) gridDim.x * blockDim.x) {
+    const uint32_t i = point_piece[j];
+    const uint64_t at = j - staged_row[i], skip = adds[i].chains ? 0 : 1;
+    if (at < skip) continue;
+    const uint64_t to = adds_base[i].points + at - skip;
+    if (to < point_cap) *reinterpret_cast<Point16*>(xy + 2 * to) = *reinterpret_cast<const Point16*>(staged_xy + 2 * j);
+  }
+}
+
 // rj_upload_map_dev: what rj_upload_map checks in host loops, and edge_begin[c] = row_index[c] - c.  *status = the
 // largest kMapBad* code met (0: the map is fine; the order rj_upload_map checks in); edge_begin is only meaningful then.
 __global__ __launch_bounds__(kThreads) void k_map_check(const int64_t* __restrict__ xy, uint64_t np, const uint32_t* __restrict__ row_index,
@@ -271,8 +370,8 @@ hipError_t map_check_device(hipStream_t st, const int64_t* xy, uint64_t np, cons
 }
 
 hipError_t overlay_map_device(hipStream_t st, const OverlayFacesMap maps[2], const uint64_t np[2], const rj_xsect* const xsects[2], uint64_t n,
-                              const int32_t* const vertex_face[2], bool drop, const OverlayMapOut& o, uint64_t counts[3], char** scratch,
-                              size_t* scratch_bytes, const OverlayOp* op) {
+                              const int32_t* const vertex_face[2], bool drop, bool merge, const OverlayMapOut& o, uint64_t counts[3],
+                              char** scratch, size_t* scratch_bytes, const OverlayOp* op) {
   const uint64_t waves[2] = {(maps[0].ne + 63) / 64, (maps[1].ne + 63) / 64}, nwaves = waves[0] + waves[1];
   const uint64_t piece_bound = max_pieces(maps[0].nc, n) + max_pieces(maps[1].nc, n);
   const uint64_t point_bound = max_points(np[0], n) + max_points(np[1], n);
@@ -291,10 +390,18 @@ hipError_t overlay_map_device(hipStream_t st, const OverlayFacesMap maps[2], con
   size_t temp_bytes = sort_bytes > uniq_bytes ? sort_bytes : uniq_bytes;
   if (scan_bytes > temp_bytes) temp_bytes = scan_bytes;
   if (scan2_bytes > temp_bytes) temp_bytes = scan2_bytes;
+  if (merge && drop) {
+    size_t scan3_bytes = 0;
+    e = rocprim::exclusive_scan(nullptr, scan3_bytes, KeptIndexIt(rocprim::counting_iterator<uint32_t>(0), KeptIndex{nullptr, nullptr}),
+                                (uint32_t*) nullptr, 0u, (size_t) (piece_bound + 1), rocprim::maximum<uint32_t>(), st);
+    if (e != hipSuccess) return e;
+    if (scan3_bytes > temp_bytes) temp_bytes = scan3_bytes;
+  }
+  const bool staged = drop || merge;
   Slots *wcount, *wbase, *totals, *kept = nullptr, *kept_base = nullptr;
   uint64_t *keys, *sorted, *ukeys, *nu, *counts_dev;
   int64_t* staged_xy = nullptr;
-  uint32_t *staged_row = nullptr, *staged_origin = nullptr, *point_piece = nullptr;
+  uint32_t *staged_row = nullptr, *staged_origin = nullptr, *point_piece = nullptr, *prev_kept = nullptr;
   void* temp;
   Carve A;
   auto carve = [&]() {
@@ -308,7 +415,7 @@ hipError_t overlay_map_device(hipStream_t st, const OverlayFacesMap maps[2], con
     sorted = A.take<uint64_t>(nkeys + 2);
     ukeys = A.take<uint64_t>(nkeys + 2);
     temp = A.take<char>(temp_bytes);
-    if (drop) {
+    if (staged) {  // (kept, kept_base: with merge, what the pieces add and where)
       kept = A.take<Slots>(piece_bound + 1);
       kept_base = A.take<Slots>(piece_bound + 1);
       staged_xy = A.take<int64_t>(2 * point_bound + 2);
@@ -316,6 +423,7 @@ hipError_t overlay_map_device(hipStream_t st, const OverlayFacesMap maps[2], con
       staged_origin = A.take<uint32_t>(piece_bound + 1);
       point_piece = A.take<uint32_t>(point_bound + 1);
     }
+    if (merge && drop) prev_kept = A.take<uint32_t>(piece_bound + 1);
   };
   carve();
   const size_t need = A.used;
@@ -328,7 +436,7 @@ hipError_t overlay_map_device(hipStream_t st, const OverlayFacesMap maps[2], con
   A.base = *scratch;
   carve();
   Stage stage;
-  if (drop) stage = Stage{staged_xy, staged_row, staged_origin, point_piece, keys, point_bound, piece_bound};
+  if (staged) stage = Stage{staged_xy, staged_row, staged_origin, point_piece, keys, point_bound, piece_bound};
   else stage = Stage{o.xy, o.row_index, o.origin, nullptr, keys, o.point_cap, o.chain_cap};
   if ((e = hipMemsetAsync(keys, 0xFF, 8 * nkeys, st)) != hipSuccess) return e;
   for (int pass = 0; pass < 2; pass++) {
@@ -372,7 +480,36 @@ hipError_t overlay_map_device(hipStream_t st, const OverlayFacesMap maps[2], con
   } else if ((e = hipMemsetAsync(nu, 0, 8, st)) != hipSuccess) {
     return e;
   }
-  if (drop) {
+  if (merge) {
+    if (drop && piece_bound) {
+      tb = temp_bytes;
+      e = rocprim::exclusive_scan(temp, tb, KeptIndexIt(rocprim::counting_iterator<uint32_t>(0), KeptIndex{staged_row, totals}), prev_kept, 0u,
+                                  (size_t) piece_bound, rocprim::maximum<uint32_t>(), st);
+      if (e != hipSuccess) return e;
+    }
+    const dim3 grid(grid_for(piece_bound, 4096));
+    if (drop)
+      hipLaunchKernelGGL(k_ovm_join<true>, grid, dim3(kThreads), 0, st, (const uint64_t*) keys, (const uint32_t*) staged_row,
+                         (const uint32_t*) staged_origin, (const int64_t*) staged_xy, (const uint32_t*) prev_kept, (const Slots*) totals,
+                         piece_bound, kept);
+    else
+      hipLaunchKernelGGL(k_ovm_join<false>, grid, dim3(kThreads), 0, st, (const uint64_t*) keys, (const uint32_t*) staged_row,
+                         (const uint32_t*) staged_origin, (const int64_t*) staged_xy, (const uint32_t*) nullptr, (const Slots*) totals,
+                         piece_bound, kept);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (piece_bound) {
+      tb = temp_bytes;
+      if ((e = rocprim::exclusive_scan(temp, tb, kept, kept_base, Slots{0, 0}, (size_t) piece_bound, SlotsSum(), st)) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_ovm_merge_points, dim3(grid_for(point_bound, 8192)), dim3(kThreads), 0, st, (const int64_t*) staged_xy,
+                       (const uint32_t*) staged_row, (const uint32_t*) point_piece, (const Slots*) totals, (const Slots*) kept,
+                       (const Slots*) kept_base, o.xy, o.point_cap);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ovm_merge_label, dim3(grid_for(piece_bound > nkeys ? piece_bound : nkeys, 4096)), dim3(kThreads), 0, st,
+                       (const uint64_t*) keys, (const uint64_t*) ukeys, (const uint64_t*) nu, (const Slots*) totals,
+                       (const uint32_t*) staged_origin, (const Slots*) kept, (const Slots*) kept_base, o, counts_dev);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  } else if (drop) {
     hipLaunchKernelGGL(k_ovm_keep, dim3(grid_for(piece_bound, 4096)), dim3(kThreads), 0, st, (const uint32_t*) staged_row,
                        (const Slots*) totals, piece_bound, kept);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -385,11 +522,13 @@ hipError_t overlay_map_device(hipStream_t st, const OverlayFacesMap maps[2], con
                        (const Slots*) kept_base, o.xy, o.point_cap);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(k_ovm_label, dim3(grid_for(piece_bound > nkeys ? piece_bound : nkeys, 4096)), dim3(kThreads), 0, st,
-                     (const uint64_t*) keys, (const uint64_t*) ukeys, (const uint64_t*) nu, (const Slots*) totals,
-                     (const uint32_t*) staged_row, (const uint32_t*) staged_origin, (const Slots*) kept, (const Slots*) kept_base, o,
-                     counts_dev);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (!merge) {
+    hipLaunchKernelGGL(k_ovm_label, dim3(grid_for(piece_bound > nkeys ? piece_bound : nkeys, 4096)), dim3(kThreads), 0, st,
+                       (const uint64_t*) keys, (const uint64_t*) ukeys, (const uint64_t*) nu, (const Slots*) totals,
+                       (const uint32_t*) staged_row, (const uint32_t*) staged_origin, (const Slots*) kept, (const Slots*) kept_base, o,
+                       counts_dev);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
   // the one read-back: the three counts
   if ((e = hipMemcpyAsync(counts, counts_dev, 24, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
   return hipStreamSynchronize(st);

@@ -15,8 +15,9 @@
 // A side's key is by(f0, f1) when the pair is selected and by(f0, f1) != (0, 0), else kNoKey ("no face").  A piece is
 // KEPT WHEN ITS TWO SIDES' KEYS DIFFER, which subsumes "at least one side has a face": under BY_MAP0 a piece of map 1
 // with the same map-0 face on both sides is dropped (the dissolve), under UNION / SYMDIFF a piece with label 0 is kept.
-// Adjacent kept pieces of one chain are NOT merged: a chain of map 0 that map 1 cuts stays cut under BY_MAP0 although
-// both pieces then carry the same two faces (merging is a pass of its own, not done here).
+// Adjacent kept pieces of one chain are not merged HERE: a chain of map 0 that map 1 cuts leaves the emit pass cut under
+// BY_MAP0 although both pieces then carry the same two faces; RJ_OVM_MERGE_PIECES joins them in a pass of its own over the
+// staged pieces (pieces_join, rj_overlay_map.h).
 // The face table: a kept piece adds +cross per point pair to its left key and -cross to its right key (a kNoKey side
 // adds nothing); a row per key with a contribution, the row's face[] holding the key -- (f0, 0) is "f0 outside map 1"
 // under BY_PAIR and "the selected part of f0" under BY_MAP0.

@@ -13,6 +13,8 @@
 //   of -face_table and -output_map (rj_overlay_faces_op / rj_overlay_map_op): which (face of map 0, face of map 1) pairs
 //   are faces of the result and what names a face; a face id in the files may then be 0 ("outside that map").  Without
 //   either flag the two files are the intersection's (the calls without _op), byte for byte what they were.
+//   -merge (ours): -output_map with RJ_OVM_MERGE_PIECES: adjacent pieces of one source chain that have the same two
+//   faces and touch are written as one chain (what a dissolve leaves of a chain the other map cut).
 #include <iostream>
 #include <unordered_map>
 
@@ -43,6 +45,7 @@ class MapOverlayLBVH {
     by_ = index(by, bys, 3, "by");
     use_op_ = !how.empty() || !by.empty();
   }
+  void SetMerge(bool merge) { map_flags_ = merge ? RJ_OVM_MERGE_PIECES : 0; }
   ~MapOverlayLBVH() {
     rj_handle h = ctx_.handle();
     if (pairs_) rj_dev_free(h, pairs_);
@@ -140,10 +143,10 @@ class MapOverlayLBVH {
     rj_overlay_map_counts c;
     auto overlay_map = [&](uint64_t cc, uint64_t pc, uint64_t fc, int64_t* xy, uint32_t* row, int32_t* left, int32_t* right,
                            int32_t* pairs) {
-      return use_op_ ? rj_overlay_map_op(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], 0, cc, pc, fc, xy, row, left,
-                                         right, pairs, nullptr, &c, how_, by_)
-                     : rj_overlay_map(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], 0, cc, pc, fc, xy, row, left, right,
-                                      pairs, nullptr, &c);
+      return use_op_ ? rj_overlay_map_op(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], map_flags_, cc, pc, fc, xy, row,
+                                         left, right, pairs, nullptr, &c, how_, by_)
+                     : rj_overlay_map(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], map_flags_, cc, pc, fc, xy, row, left,
+                                      right, pairs, nullptr, &c);
     };
     int rc = overlay_map(0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
     if (rc != RJ_E_OVERFLOW) rj_check(h, rc, "rj_overlay_map");
@@ -241,7 +244,7 @@ class MapOverlayLBVH {
   int grid_size_;
   bool keep_xsects_;
   bool use_op_ = false;
-  uint32_t how_ = 0, by_ = 0;
+  uint32_t how_ = 0, by_ = 0, map_flags_ = 0;
   size_t cap_ = 0, n_xsects_ = 0;
   rj_xsect* xsects_dev_[2] = {nullptr, nullptr};
   std::vector<rj_overlay_face> face_rows_;
@@ -265,6 +268,7 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
   Context ctx({g1, g2}, f.device, f.scale_fma);
   MapOverlayLBVH overlay(ctx, f.xsect_factor, f.mode == "grid", f.grid_size, !f.face_table.empty() || !f.output_map.empty());
   overlay.SetOperation(f.how, f.by);
+  overlay.SetMerge(f.merge);
   tm.next("Load Data");
   ctx.LoadToDevice();
   tm.next("Init");
@@ -313,7 +317,7 @@ int main(int argc, char* argv[]) {
     std::cerr << "Usage: " << argv[0] << " -poly1 <map0.cdb> -poly2 <map1.cdb> -mode lbvh|grid [-grid_size 2048] [-output <result.cdb>]\n"
               << "  [-serialize <dir>] [-xsect_factor 0.2] [-check] [-device 0] [-v 1]\n"
               << "  [-face_table <rows.txt>] [-output_map <map.cdb>] [-how intersection|union|difference|symmetric_difference|identity]\n"
-              << "  [-by pair|map0|map1]\n";
+              << "  [-by pair|map0|map1] [-merge]\n";
     return 1;
   }
   Flags f;

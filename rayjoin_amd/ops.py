@@ -286,17 +286,20 @@ class MapOverlay:
         out.free()
         return face_table_from_rows(raw, self.ctx_.ctx.scaling)
 
-    def OutputMap(self, drop_degenerate=False, capacities=None, how="intersection", by="pair"):
+    def OutputMap(self, drop_degenerate=False, capacities=None, how="intersection", by="pair", merge=False):
         """The output map as a DeviceOutputMap (rj_overlay_map): the pieces the CDB writer keeps, in its order, in scaled
         integers, faces numbered by the ordered pair (face of map 0, face of map 1) -- face k is row k - 1 of
         FaceTable().  drop_degenerate leaves out the pieces with fewer than two points (what an input map may not have:
         DeviceContext.InstallMap).  capacities = (chains, points, faces): MapOverflow with the true counts when one is
         too small; left open, a sizing call finds them.  how / by as FaceTable (rj_overlay_map_op): a piece is kept
         when the faces on its two sides differ; how="intersection", by="map0" clips map 0 to where map 1 covers and
-        keeps map 0's face ids (face_pairs[k - 1] = (f0, 0)); adjacent pieces of one chain are not merged."""
+        keeps map 0's face ids (face_pairs[k - 1] = (f0, 0)).  merge (RJ_OVM_MERGE_PIECES) joins adjacent pieces of one
+        source chain that have the same two faces and touch into one chain, after drop_degenerate: a chain that forty
+        dissolved boundaries cut leaves as one chain again; the faces and their numbers do not change.  Without it every
+        piece is a chain of its own."""
         if not (self.located[0] and self.located[1]) or self.xsects[0] is None:
             raise RuntimeError("MapOverlay.OutputMap needs LocateVerticesInOtherMap(0), (1) and ComputeOutputPolygons() first")
-        flags = _capi.RJ_OVM_DROP_DEGENERATE if drop_degenerate else 0
+        flags = (_capi.RJ_OVM_DROP_DEGENERATE if drop_degenerate else 0) | (_capi.RJ_OVM_MERGE_PIECES if merge else 0)
         op = overlay_op(how, by)
         args = (self.xsects[0], self.xsects[1], self.n_xsects, self.faces[0], self.faces[1], flags)
         if capacities is None:
@@ -313,18 +316,20 @@ class MapOverlay:
             for b in bufs:
                 b.free()
             raise
-        return DeviceOutputMap(*bufs, counts, drop_degenerate)
+        return DeviceOutputMap(*bufs, counts, drop_degenerate, merge)
 
 
 class DeviceOutputMap:
     """The overlay's output map in device memory (rj_overlay_map): xy (int64 x,y pairs, scaled units), row_index
     (uint32, n_chains + 1), left / right (int32 output face ids), face_pairs (int32 pairs: face k is face_pairs[k - 1])
-    and origin (uint32: (im << 31) | source chain) as DeviceBuffers, and the counts."""
+    and origin (uint32: (im << 31) | source chain) as DeviceBuffers, the counts, and the flags it was computed under
+    (drop_degenerate, merged)."""
 
-    def __init__(self, xy, row_index, left, right, face_pairs, origin, counts, drop_degenerate):
+    def __init__(self, xy, row_index, left, right, face_pairs, origin, counts, drop_degenerate, merged=False):
         self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin = xy, row_index, left, right, face_pairs, origin
         self.n_chains, self.n_points, self.n_faces = (int(v) for v in counts)
         self.drop_degenerate = bool(drop_degenerate)
+        self.merged = bool(merged)
 
     def to_host(self):
         """-> (maps.ScaledMap of the output map, face_pairs int32 [n_faces, 2], origin uint32 [n_chains])"""
