@@ -373,6 +373,58 @@ int rj_overlay_map_op(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* 
                       int32_t* face_pairs_dev, uint32_t* origin_dev, rj_overlay_map_counts* counts,
                       uint32_t how, uint32_t by);
 
+/* ---- face rings -------------------------------------------------------------------------- */
+/* rj_map_rings flags */
+#define RJ_RINGS_SKIP_FACE0 1u /* leave out the rings whose face is 0, with their half-chains and points */
+#define RJ_RINGS_NO_POINTS  2u /* ring_row_dev / ring_xy_dev are not written and point_capacity is ignored; n_points is still counted */
+/* rj_ring flags */
+#define RJ_RING_MIXED 1u /* some half-chain of the ring has another face than the ring's */
+
+typedef struct {
+  int32_t face;
+  uint32_t flags;
+  uint32_t leader;
+  uint32_t _pad;
+  uint64_t area2_lo; /* twice the signed area, a two's-complement int128 like rj_overlay_face's */
+  int64_t area2_hi;
+} rj_ring; /* 32 bytes */
+
+typedef struct {
+  uint64_t n_rings, n_halves, n_points, n_mixed, n_skipped;
+} rj_rings_counts;
+
+/* extends: the polygons of a chain map -- the closed boundaries (rings) that the chains form, computed on the device
+ * from a map in caller-owned device memory with the contract of rj_upload_map_dev (an rj_overlay_map output, an input
+ * map): xy_dev[2 np], row_index_dev[nc + 1], left_dev[nc], right_dev[nc]; left is the face on the left of a chain walked
+ * from its first point to its last, y up (the convention under which rj_overlay_faces' areas are positive).
+ * nc < 2^31, np < 2^32 and 2 (np - nc) < 2^32.  The definition, in full in rayjoin_amd/csrc/rj_rings.h:
+ *   half-chain h = 2 c is chain c walked forward (face left[c]), h = 2 c + 1 chain c walked backward (face right[c]),
+ *   h ^ 1 its twin; a chain whose points are all equal is skipped (n_skipped) and belongs to no ring.  Incidence h is the
+ *   start vertex of h with the direction to the first different point of the chain.  The incidences on one point are
+ *   ordered counter-clockwise from the positive x axis, exactly (int128 cross products), equal directions by ascending h;
+ *   h arrives at the junction of h ^ 1 and goes on with the clockwise neighbour of h ^ 1 there (h ^ 1 itself at a dead
+ *   end), which keeps the face on the left.  The cycles of that permutation are the rings.
+ *   A ring: leader = its smallest h; face = the leader's face; RJ_RING_MIXED when a half-chain of it has another face
+ *   (only where chains overlap or the map's labels are inconsistent); its half-chains in walk order from the leader; its
+ *   points = every half-chain's points in its direction without the last (as many points as edges, the first point is
+ *   not repeated); area2 = the sum of cross(a, b) over consecutive points including the closing pair, exact: positive
+ *   for a counter-clockwise ring (the outer boundary of its face), negative for a hole of its face or a boundary of
+ *   face 0.  Rings ascend by ((uint64)(uint32)face << 32) | leader: the rings of a face are contiguous.
+ * Output, all caller-owned device memory: rings_dev[ring_capacity]; ring_first_dev[ring_capacity + 1], the CSR of the
+ * rings into ring_half_dev[half_capacity]; ring_row_dev[ring_capacity + 1], the CSR into ring_xy_dev[2 point_capacity].
+ * RJ_E_OVERFLOW when a count exceeds its capacity: *counts holds the true counts and nothing beyond any capacity is
+ * written; all capacities 0 (arrays may be NULL) is the sizing call.  nc == 0 is valid.  A malformed map (the checks of
+ * rj_upload_map_dev, but a chain may have a single point: an output map without RJ_OVM_DROP_DEGENERATE has such
+ * chains, they are skipped) and an unknown flag bit are RJ_E_INVALID; RJ_E_INTERNAL when a round budget runs out (33 doubling
+ * steps: cannot happen below 2^32 half-chains).  Runs on the handle's stream with one host sync, at the end, to read
+ * the counts; scratch (352 bytes per chain plus the sorts' temporary storage) is allocated per call and freed; no
+ * state of the handle (maps, indexes, plans) changes. */
+int rj_map_rings(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev,
+                 const int32_t* left_dev, const int32_t* right_dev, uint64_t nc, uint32_t flags,
+                 uint64_t ring_capacity, uint64_t half_capacity, uint64_t point_capacity,
+                 rj_ring* rings_dev, uint32_t* ring_first_dev, uint32_t* ring_half_dev, uint32_t* ring_row_dev,
+                 int64_t* ring_xy_dev, rj_rings_counts* counts);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

@@ -21,6 +21,9 @@ RJ_OV_BY_PAIR, RJ_OV_BY_MAP0, RJ_OV_BY_MAP1 = 0, 1, 2
 OVERLAY_HOW = {"intersection": RJ_OV_INTERSECTION, "union": RJ_OV_UNION, "difference": RJ_OV_DIFFERENCE,
                "symmetric_difference": RJ_OV_SYMDIFF, "identity": RJ_OV_IDENTITY}
 OVERLAY_BY = {"pair": RJ_OV_BY_PAIR, "map0": RJ_OV_BY_MAP0, "map1": RJ_OV_BY_MAP1}
+RJ_RINGS_SKIP_FACE0 = 1  # rj_map_rings flags
+RJ_RINGS_NO_POINTS = 2
+RJ_RING_MIXED = 1  # rj_ring flags
 RJ_T_BUILD, RJ_T_LSI_KERNEL, RJ_T_PIP_KERNEL, RJ_T_LSI_POINTS, RJ_T_SORT, RJ_T_ORDER = 0, 1, 2, 3, 4, 5
 RJ_T_BUILD_KEYS, RJ_T_BUILD_SORT, RJ_T_BUILD_LEAVES, RJ_T_BUILD_LEVELS, RJ_T_PIP_WALK, RJ_T_BUILD_RUNS = 6, 7, 8, 9, 10, 11
 MISS_EID = 0xFFFFFFFF
@@ -30,6 +33,9 @@ XSECT_DTYPE = np.dtype(
      ("eid", "<u4", (2,)), ("mid_point_polygon_id", "<i4"), ("_pad", "<i4")])
 # rj_overlay_face: (face of map 0, face of map 1), twice the overlap's signed area as a two's-complement int128
 FACE_DTYPE = np.dtype([("face", "<i4", (2,)), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
+# rj_ring: a closed boundary of a chain map -- its face, RJ_RING_MIXED, its smallest half-chain, twice its signed area
+RING_DTYPE = np.dtype([("face", "<i4"), ("flags", "<u4"), ("leader", "<u4"), ("_pad", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
+RINGS_COUNTS = ("n_rings", "n_halves", "n_points", "n_mixed", "n_skipped")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
 _vp, _u64, _i64, _int = C.c_void_p, C.c_uint64, C.c_int64, C.c_int
@@ -77,6 +83,7 @@ SYMBOLS = {
     "rj_overlay_faces_op": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64), C.c_uint32, C.c_uint32]),
     "rj_overlay_map_op": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32,
                                  C.c_uint32]),
+    "rj_map_rings": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -145,6 +152,14 @@ class RayJoinError(RuntimeError):
 
 class MapOverflow(RayJoinError):
     """RJ_E_OVERFLOW of rj_overlay_map: counts = (chains, points, faces), the true counts"""
+
+    def __init__(self, msg, counts):
+        super().__init__(RJ_E_OVERFLOW, msg)
+        self.counts = counts
+
+
+class RingsOverflow(RayJoinError):
+    """RJ_E_OVERFLOW of rj_map_rings: counts = dict(n_rings, n_halves, n_points, n_mixed, n_skipped), the true counts"""
 
     def __init__(self, msg, counts):
         super().__init__(RJ_E_OVERFLOW, msg)
@@ -468,6 +483,21 @@ class Handle:
             raise MapOverflow(self.L.rj_last_error_string(self.h).decode(), tuple(counts))
         self._check(rc)
         return tuple(counts)
+
+    def map_rings(self, xy_dev, n_points, row_index_dev, left_dev, right_dev, n_chains, flags, capacities, rings_dev, ring_first_dev,
+                  ring_half_dev, ring_row_dev, ring_xy_dev):
+        """rj_map_rings of a chain map in device memory into the caller's device arrays; capacities = (rings, half-chains,
+        points).  Returns the counts as a dict (RINGS_COUNTS); RingsOverflow (with the true counts) past a capacity."""
+        counts = (_u64 * 5)()
+        rc_, hc, pc = (int(v) for v in capacities)
+        rc = self.L.rj_map_rings(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev), int(n_chains),
+                                 int(flags), rc_, hc, pc, _ptr(rings_dev), _ptr(ring_first_dev), _ptr(ring_half_dev), _ptr(ring_row_dev),
+                                 _ptr(ring_xy_dev), counts)
+        named = dict(zip(RINGS_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise RingsOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        self._check(rc)
+        return named
 
     def sort_pairs(self, pairs_dev, n):
         self._check(self.L.rj_sort_pairs(self.h, _ptr(pairs_dev), n))

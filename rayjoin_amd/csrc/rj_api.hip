@@ -17,6 +17,7 @@
 #include "rj_kernels.h"
 #include "rj_overlay_dev.h"
 #include "rj_overlay_ops.h"
+#include "rj_rings.h"
 
 using namespace rj;
 
@@ -2700,6 +2701,42 @@ int rj_overlay_map_op(rj_handle h, const rj_xsect* xsects0_dev, const rj_xsect* 
   if (int r = overlay_op(h, "rj_overlay_map_op", how, by, &op)) return r;
   return overlay_map_call(h, "rj_overlay_map_op", xsects0_dev, xsects1_dev, n, vertex_face0_dev, vertex_face1_dev, flags, chain_capacity,
                           point_capacity, face_capacity, xy_dev, row_index_dev, left_dev, right_dev, face_pairs_dev, origin_dev, counts, &op);
+}
+
+int rj_map_rings(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, const int32_t* left_dev,
+                 const int32_t* right_dev, uint64_t nc, uint32_t flags, uint64_t ring_capacity, uint64_t half_capacity,
+                 uint64_t point_capacity, rj_ring* rings_dev, uint32_t* ring_first_dev, uint32_t* ring_half_dev, uint32_t* ring_row_dev,
+                 int64_t* ring_xy_dev, rj_rings_counts* counts) {
+  static_assert(sizeof(rj_ring) == 32 && sizeof(rings::Ring) == 32 && sizeof(rj_rings_counts) == sizeof(rings::Counts), "layouts");
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_map_rings: counts is null");
+  memset(counts, 0, sizeof(*counts));
+  if (flags & ~(uint32_t) (RJ_RINGS_SKIP_FACE0 | RJ_RINGS_NO_POINTS)) return fail(h, RJ_E_INVALID, "rj_map_rings: unknown flags 0x%x", flags);
+  const bool points = !(flags & RJ_RINGS_NO_POINTS);
+  if (!points) point_capacity = 0;
+  if ((np && !xy_dev) || (nc && (!row_index_dev || !left_dev || !right_dev))) return fail(h, RJ_E_INVALID, "rj_map_rings: null input array");
+  if (nc >= (1ull << 31) || np >= (1ull << 32) || nc > np || 2 * (np - nc) >= (1ull << 32))
+    return fail(h, RJ_E_INVALID, "rj_map_rings: nc < 2^31, nc <= np < 2^32 and 2 (np - nc) < 2^32");
+  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_rings: points without chains");
+  if ((ring_capacity && (!rings_dev || !ring_first_dev || (points && !ring_row_dev))) || (half_capacity && !ring_half_dev) ||
+      (point_capacity && !ring_xy_dev))
+    return fail(h, RJ_E_INVALID, "rj_map_rings: null output");
+  if (int r = set_device(h)) return r;
+  const rings::Out out{reinterpret_cast<rings::Ring*>(rings_dev), ring_first_dev, ring_half_dev, ring_row_dev, ring_xy_dev,
+                       ring_capacity, half_capacity, point_capacity};
+  rings::Meta m;
+  RJ_HIP(h, map_rings_device(h->stream, xy_dev, np, row_index_dev, left_dev, right_dev, nc, flags, out, &m));
+  if (m.bad_map == rings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_rings: row_index must start at 0");
+  if (m.bad_map == rings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_rings: row_index must end at np");
+  if (m.bad_map == rings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_rings: row_index must ascend (a chain has no point)");
+  if (m.bad_map) return fail(h, RJ_E_INVALID, "rj_map_rings: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  if (m.unfinished) return fail(h, RJ_E_INTERNAL, "rj_map_rings: a ring was not closed within %d doubling steps", rings::kMaxRounds);
+  memcpy(counts, &m.counts, sizeof(*counts));
+  if (counts->n_rings > ring_capacity || counts->n_halves > half_capacity || (points && counts->n_points > point_capacity))
+    return fail(h, RJ_E_OVERFLOW, "rj_map_rings: %llu rings, %llu half-chains, %llu points; capacities %llu, %llu, %llu",
+                (unsigned long long) counts->n_rings, (unsigned long long) counts->n_halves, (unsigned long long) counts->n_points,
+                (unsigned long long) ring_capacity, (unsigned long long) half_capacity, (unsigned long long) point_capacity);
+  return RJ_OK;
 }
 
 int rj_last_ms(rj_handle h, int which, float* ms) {

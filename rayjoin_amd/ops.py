@@ -15,6 +15,9 @@
          FaceTable is the overlay's answer computed on the device (rj_overlay_faces), OutputMap the output map as
          device arrays (rj_overlay_map); DeviceContext.InstallMap makes one an input map again (rj_upload_map_dev);
          how= / by= on both choose another overlay operation: union, difference, ..., clip (rj_overlay_*_op)
+  face_rings(handle, ...) / DeviceOutputMap.Rings(handle) / DeviceContext.Rings(im) -> DeviceRings; .polygons()
+      -- the closed boundaries of a chain map's faces, stitched on the device (rj_map_rings): what a consumer of an
+         output map needs to draw or export a face
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -78,6 +81,20 @@ class DeviceContext:
 
     def get_map(self, im):
         return self.installed[im] if self.installed[im] is not None else self.ctx.get_map(im)
+
+    def Rings(self, im, **kw):
+        """face_rings of input map `im` (its host image goes to temporaries on the device): the boundaries of its faces"""
+        m = self.get_map(im)
+        h = self.handle
+        bufs = [h.alloc(16 * max(1, m.n_points)).from_host(np.ascontiguousarray(m.pts, dtype=np.int64)),
+                h.alloc(4 * (m.n_chains + 1)).from_host(np.ascontiguousarray(m.row_index, dtype=np.uint32)),
+                h.alloc(4 * max(1, m.n_chains)).from_host(np.ascontiguousarray(m.left, dtype=np.int32)),
+                h.alloc(4 * max(1, m.n_chains)).from_host(np.ascontiguousarray(m.right, dtype=np.int32))]
+        try:
+            return face_rings(h, bufs[0], m.n_points, bufs[1], bufs[2], bufs[3], m.n_chains, **kw)
+        finally:
+            for b in bufs:
+                b.free()
 
     def close(self):
         self.handle.close()
@@ -338,9 +355,82 @@ class DeviceOutputMap:
                       self.left.to_host(np.int32, self.n_chains).astype(np.int64), self.right.to_host(np.int32, self.n_chains).astype(np.int64))
         return m, self.face_pairs.to_host(np.int32, 2 * self.n_faces).reshape(-1, 2), self.origin.to_host(np.uint32, self.n_chains)
 
+    def Rings(self, handle, **kw):
+        """face_rings of this map: the closed boundaries of its faces (face k is row k - 1 of FaceTable()), on the device"""
+        return face_rings(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, **kw)
+
     def free(self):
         for b in (self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin):
             b.free()
+
+
+def face_rings(handle, xy, n_points, row_index, left, right, n_chains, skip_face0=False, points=True, capacities=None):
+    """The rings of a chain map in device memory (rj_map_rings; the arrays as rj_upload_map_dev takes them: int64 xy,
+    uint32 row_index, int32 left / right) as a DeviceRings.  skip_face0 leaves out the rings of face 0 (the outside);
+    points=False leaves out the points (ring_row, ring_xy).  capacities = (rings, half-chains, points): RingsOverflow with
+    the true counts when one is too small; left open, a sizing call finds them."""
+    flags = (_capi.RJ_RINGS_SKIP_FACE0 if skip_face0 else 0) | (0 if points else _capi.RJ_RINGS_NO_POINTS)
+    args = (xy, n_points, row_index, left, right, n_chains, flags)
+    if capacities is None:
+        try:
+            c = handle.map_rings(*args, (0, 0, 0), None, None, None, None, None)
+        except _capi.RingsOverflow as e:
+            c = e.counts
+        capacities = (c["n_rings"], c["n_halves"], c["n_points"])
+    rc, hc, pc = (int(v) for v in capacities)
+    bufs = [handle.alloc(_capi.RING_DTYPE.itemsize * max(1, rc)), handle.alloc(4 * (rc + 1)), handle.alloc(4 * max(1, hc)),
+            handle.alloc(4 * (rc + 1)) if points else None, handle.alloc(16 * max(1, pc)) if points else None]
+    try:
+        counts = handle.map_rings(*args, (rc, hc, pc), *bufs)
+    except _capi.RayJoinError:
+        for b in bufs:
+            if b is not None:
+                b.free()
+        raise
+    return DeviceRings(*bufs, counts)
+
+
+class DeviceRings:
+    """The rings of a chain map in device memory (rj_map_rings): rings (RING_DTYPE rows, ascending by (face, leader)),
+    ring_first (uint32 CSR of the rings into ring_half), ring_half (uint32 half-chains: 2 c = chain c forward, 2 c + 1
+    backward), ring_row (uint32 CSR into ring_xy) and ring_xy (int64 x,y pairs, scaled units) as DeviceBuffers -- the last
+    two None without points -- and the counts n_rings, n_halves, n_points, n_mixed, n_skipped."""
+
+    def __init__(self, rings, ring_first, ring_half, ring_row, ring_xy, counts):
+        self.rings, self.ring_first, self.ring_half, self.ring_row, self.ring_xy = rings, ring_first, ring_half, ring_row, ring_xy
+        self.counts = dict(counts)
+        for name in _capi.RINGS_COUNTS:
+            setattr(self, name, int(counts[name]))
+
+    def to_host(self):
+        """-> dict(rings, ring_first, ring_half, ring_row, ring_xy [n_points, 2], counts); ring_row / ring_xy None without points"""
+        n = self.n_rings
+        return dict(rings=self.rings.to_host(_capi.RING_DTYPE, n), ring_first=self.ring_first.to_host(np.uint32, n + 1),
+                    ring_half=self.ring_half.to_host(np.uint32, self.n_halves),
+                    ring_row=self.ring_row.to_host(np.uint32, n + 1) if self.ring_row is not None else None,
+                    ring_xy=self.ring_xy.to_host(np.int64, 2 * self.n_points).reshape(-1, 2) if self.ring_xy is not None else None,
+                    counts=dict(self.counts))
+
+    def polygons(self, scaling=None):
+        """{face: [(area2, points[n, 2]), ...]} on the host, the rings of a face in ring order: area2 exact (a Python int, in
+        scaled units^2; positive = outer boundary, negative = hole), the points scaled integers, or input coordinates
+        when the map's maps.Scaling is given"""
+        if self.ring_xy is None:
+            raise RuntimeError("DeviceRings.polygons needs the points (points=True)")
+        host = self.to_host()
+        out = {}
+        row = host["ring_row"].astype(np.int64)
+        for k, g in enumerate(host["rings"]):
+            pts = host["ring_xy"][row[k]:row[k + 1]]
+            if scaling is not None:
+                pts = scaling.unscale(pts)
+            out.setdefault(int(g["face"]), []).append(((int(g["area2_hi"]) << 64) | int(g["area2_lo"]), pts))
+        return out
+
+    def free(self):
+        for b in (self.rings, self.ring_first, self.ring_half, self.ring_row, self.ring_xy):
+            if b is not None:
+                b.free()
 
 
 def overlay_op(how, by):

@@ -1,0 +1,276 @@
+"""Face rings on the device (rj_map_rings, ops.face_rings, DeviceOutputMap.Rings, DeviceContext.Rings) against the
+plain-Python definition (tests/rings_ref.py), array for array: the hand cases and necklaces of tests/rings_cases.py, the
+device's OWN output maps of the overlay tests' pairs (five calls, drop and merge on and off), the lattice pair's clip;
+against the host twin on the lattice pair's full intersection map (too large for the Python walk; tests/test_rings.py
+holds twin and definition equal); the exact area invariant against the device's own face table; overflow with canaries,
+the sizing call, the flags, an empty and a malformed map.  The CPU side is tests/test_rings.py."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from rayjoin_amd import _capi, maps, ops, synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import rings_cases as K  # noqa: E402
+import rings_ref as D  # noqa: E402
+from test_gpu_overlay_map import host_arrays  # noqa: E402
+from test_gpu_overlay_merge import CALLS, DROP, MERGE, overlay_of, raw_map  # noqa: E402
+from test_overlay_map import pair  # noqa: E402
+from test_rings import NOPTS, SKIP0, as_map, twin_lib, twin_rings  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def handle():
+    h = _capi.Handle(0)
+    yield h
+    h.close()
+
+
+class DeviceMap:
+    """a chain map (xy, row_index, left, right) in device buffers"""
+
+    def __init__(self, h, m):
+        xy, row, left, right = m
+        self.n_points, self.n_chains = len(xy), len(left)
+        self.bufs = [h.alloc(16 * max(1, len(xy))).from_host(np.ascontiguousarray(xy, np.int64)),
+                     h.alloc(4 * (len(left) + 1)).from_host(np.ascontiguousarray(row, np.uint32)),
+                     h.alloc(4 * max(1, len(left))).from_host(np.ascontiguousarray(left, np.int32)),
+                     h.alloc(4 * max(1, len(left))).from_host(np.ascontiguousarray(right, np.int32))]
+
+    def args(self):
+        xy, row, left, right = self.bufs
+        return (xy, self.n_points, row, left, right, self.n_chains)
+
+    def free(self):
+        for b in self.bufs:
+            b.free()
+
+
+def device_rings(h, m, flags=0):
+    dm = DeviceMap(h, m)
+    try:
+        r = ops.face_rings(h, *dm.args(), skip_face0=bool(flags & SKIP0), points=not flags & NOPTS)
+        got = r.to_host()
+        r.free()
+        return got
+    finally:
+        dm.free()
+
+
+def rings_of_output_map(h, om, **kw):
+    r = om.Rings(h, **kw)
+    got = r.to_host()
+    r.free()
+    return got
+
+
+# ---- device against the definition -----------------------------------------------------------------------------------
+def test_hand_cases_and_necklaces_equal_the_definition(handle):
+    for name, m in K.all_cases().items():
+        for flags in ((0, SKIP0, NOPTS, SKIP0 | NOPTS) if name in K.HAND else (0,)):
+            got = device_rings(handle, m, flags)
+            D.assert_same_rings(got, D.rings_ref(*m, skip_face0=bool(flags & SKIP0), points=not flags & NOPTS), (name, flags))
+    star = device_rings(handle, K.star(40))
+    assert star["counts"]["n_rings"] == 1 and star["counts"]["n_halves"] == 80 and D.area2_of(star["rings"]) == [0]
+    for n in K.NECKLACE_SIZES:
+        m, area2 = K.necklace(n)
+        got = device_rings(handle, m)
+        assert got["ring_first"].tolist() == [0, n, 2 * n] and D.area2_of(got["rings"]) == [-area2, area2], n
+
+
+@pytest.mark.parametrize("name", ["sample", "rings", "nested"])
+def test_own_output_maps_equal_the_definition(name):
+    """the device's own output maps: the five calls, drop on and off, merge on and off.  On the pairs in general position no
+    ring is mixed and the rings of face k sum to row k - 1 of the device's own face table, exactly."""
+    gs, _ = pair(name)
+    dctx, ov = overlay_of(maps.Context(gs).load(), None)
+    try:
+        for call in CALLS:
+            how, by = call if call is not None else ("intersection", "pair")
+            table = ov.FaceTable(how=how, by=by)
+            for flags in (0, DROP, MERGE, DROP | MERGE):
+                what = (name, call, flags)
+                om = raw_map(ov, call, flags)
+                m = as_map(host_arrays(om))
+                got = rings_of_output_map(ov.h, om)
+                om.free()
+                D.assert_same_rings(got, D.rings_ref(*m), what)
+                if name == "nested":
+                    continue
+                assert got["counts"]["n_mixed"] == 0, what
+                sums = {}
+                for f, a2 in zip(got["rings"]["face"].tolist(), D.area2_of(got["rings"])):
+                    sums[f] = sums.get(f, 0) + a2
+                sums.pop(0, None)
+                assert [sums[k + 1] for k in range(len(table))] == [int(a) for a in table["area2"]] and len(sums) == len(table), what
+        if name == "nested":  # coincident chains of both maps: direction ties, mixed rings -- as the definition has them
+            om = raw_map(ov, None, 0)
+            got = rings_of_output_map(ov.h, om)
+            om.free()
+            assert got["counts"]["n_mixed"] > 0
+    finally:
+        dctx.close()
+
+
+@pytest.fixture(scope="module")
+def lattice():
+    gs, _ = pair("lattice")
+    dctx, ov = overlay_of(maps.Context(gs).load(), None)
+    yield ov
+    dctx.close()
+
+
+def test_lattice_clip_equals_the_definition(lattice):
+    """3 785 chains, 10 rings, the longest of 1 727 half-chains: 11 doubling rounds"""
+    om = raw_map(lattice, ("intersection", "map0"), 0)
+    m = as_map(host_arrays(om))
+    got = rings_of_output_map(lattice.h, om)
+    om.free()
+    want = D.rings_ref(*m)
+    D.assert_same_rings(got, want)
+    assert len(m[2]) == 3785 and want["counts"]["n_rings"] == 10 and int(np.diff(want["ring_first"].astype(np.int64)).max()) == 1727
+
+
+def test_lattice_intersection_equals_the_host_twin_and_the_face_table(lattice):
+    """309 839 chains, 154 487 rings: every array against the host twin; no mixed ring; the rings of face k sum to row k - 1
+    of the device's face table"""
+    om = raw_map(lattice, None, 0)
+    m = as_map(host_arrays(om))
+    got = rings_of_output_map(lattice.h, om)
+    om.free()
+    rc, want, _ = twin_rings(twin_lib(), m, caps=tuple(got["counts"][k] for k in ("n_rings", "n_halves", "n_points")))
+    assert rc == 0
+    D.assert_same_rings(got, want)
+    assert len(m[2]) == 309839 and got["counts"]["n_rings"] == 154487 and got["counts"]["n_mixed"] == 0
+    table = lattice.FaceTable()
+    a2 = np.array(D.area2_of(got["rings"]), dtype=object)
+    face = got["rings"]["face"].astype(np.int64)
+    keep = face != 0
+    first = np.flatnonzero(np.r_[True, face[keep][1:] != face[keep][:-1]])
+    assert face[keep][first].tolist() == list(range(1, len(table) + 1))
+    assert np.add.reduceat(a2[keep], first).tolist() == [int(a) for a in table["area2"]]
+
+
+# ---- the contract of the call ------------------------------------------------------------------------------------------
+def test_each_capacity_one_short_overflows_and_writes_nothing_beyond(handle):
+    m = K.necklace(129)[0]
+    want = D.rings_ref(*m)
+    true = tuple(want["counts"][k] for k in ("n_rings", "n_halves", "n_points"))
+    dm = DeviceMap(handle, m)
+    try:
+        with pytest.raises(_capi.RingsOverflow) as e:  # the sizing call
+            handle.map_rings(*dm.args(), 0, (0, 0, 0), None, None, None, None, None)
+        assert e.value.counts == want["counts"] and e.value.code == _capi.RJ_E_OVERFLOW
+        canary = np.full(4, 0x5A5A5A5A, np.uint32)
+        for short in range(3):
+            rc_, hc, pc = (v - (1 if i == short else 0) for i, v in enumerate(true))
+            bufs = []
+            for nbytes in (32 * rc_, 4 * (rc_ + 1), 4 * hc, 4 * (rc_ + 1), 16 * pc):
+                b = handle.alloc(nbytes + 16)
+                handle._check(_capi.load().rj_memcpy_h2d(handle.h, b.ptr + nbytes, canary.ctypes.data, 16))
+                bufs.append((b, nbytes))
+            with pytest.raises(_capi.RingsOverflow) as e:
+                handle.map_rings(*dm.args(), 0, (rc_, hc, pc), *[b for b, _ in bufs])
+            assert e.value.counts == want["counts"], short
+            for b, nbytes in bufs:
+                assert np.array_equal(b.to_host(np.uint32, nbytes // 4 + 4)[-4:], canary), short
+                b.free()
+            with pytest.raises(_capi.RingsOverflow):
+                ops.face_rings(handle, *dm.args(), capacities=(rc_, hc, pc))
+        exact = ops.face_rings(handle, *dm.args(), capacities=true)
+        D.assert_same_rings(exact.to_host(), want)
+        exact.free()
+        # without points the point capacity does not count and nothing is written to the point arrays
+        bufs = [handle.alloc(32 * true[0]), handle.alloc(4 * (true[0] + 1)), handle.alloc(4 * true[1])]
+        guard = handle.alloc(16).from_host(canary)
+        c = handle.map_rings(*dm.args(), NOPTS, (true[0], true[1], 0), *bufs, guard, guard)
+        assert c == want["counts"] and np.array_equal(guard.to_host(np.uint32, 4), canary)
+        for b in bufs + [guard]:
+            b.free()
+    finally:
+        dm.free()
+
+
+def test_unknown_flags_empty_and_malformed_maps(handle):
+    m = K.square_with_hole()
+    dm = DeviceMap(handle, m)
+    try:
+        for flags in (4, 4 | SKIP0, 0x80000000):
+            with pytest.raises(_capi.RayJoinError) as e:
+                handle.map_rings(*dm.args(), flags, (0, 0, 0), None, None, None, None, None)
+            assert e.value.code == _capi.RJ_E_INVALID and "unknown flags" in str(e.value) and not isinstance(e.value, _capi.RingsOverflow)
+        # nc == 0: no rings, the CSRs' one entry
+        first, rrow = handle.alloc(4).from_host(np.array([7], np.uint32)), handle.alloc(4).from_host(np.array([7], np.uint32))
+        c = handle.map_rings(None, 0, None, None, None, 0, 0, (0, 0, 0), None, first, None, rrow, None)
+        assert c == dict.fromkeys(D.COUNTS, 0) and first.to_host(np.uint32, 1).tolist() == [0] and rrow.to_host(np.uint32, 1).tolist() == [0]
+        empty = ops.face_rings(handle, None, 0, None, None, None, 0)
+        assert empty.n_rings == 0 and empty.polygons() == {}
+        empty.free()
+        # a row_index that does not ascend, one that does not end at np, a coordinate out of range
+        for row, xy in (([0, 5, 4, 10], m[0]), ([0, 5, 9], m[0]), ([0, 5, 10], np.where(m[0] == 10, 1 << 46, m[0]))):
+            left, right = np.ones(len(row) - 1, np.int32), np.zeros(len(row) - 1, np.int32)
+            bad = DeviceMap(handle, (xy, np.array(row, np.uint32), left, right))
+            try:
+                with pytest.raises(_capi.RayJoinError) as e:
+                    ops.face_rings(handle, *bad.args())
+                assert e.value.code == _capi.RJ_E_INVALID and not isinstance(e.value, _capi.RingsOverflow), row
+            finally:
+                bad.free()
+        got = ops.face_rings(handle, *dm.args())  # the handle still works
+        D.assert_same_rings(got.to_host(), D.rings_ref(*m))
+        got.free()
+    finally:
+        dm.free()
+
+
+def test_rings_of_an_input_map():
+    """60 isolated closed chains: every one is the outer ring of its face and a hole of face 0"""
+    g = synth.ring_map(60, 900, seed=63)
+    ctx = maps.Context([g, synth.lattice_map(6, 30, 64)]).load()
+    dctx = ops.DeviceContext(ctx).LoadToDevice()
+    try:
+        r = dctx.Rings(0)
+        host = r.to_host()
+        a2 = D.area2_of(host["rings"])
+        assert r.n_rings == 120 and sum(1 for a in a2 if a > 0) == 60 and r.n_mixed == 0 and r.n_skipped == 0
+        assert host["rings"]["face"][:60].tolist() == [0] * 60 and all(a < 0 for a in a2[:60])
+        m0 = ctx.maps[0]
+        D.assert_same_rings(host, D.rings_ref(m0.pts, m0.row_index, m0.left.astype(np.int32), m0.right.astype(np.int32)))
+        inner = dctx.Rings(0, skip_face0=True, points=False)
+        assert inner.n_rings == 60 and inner.ring_xy is None and inner.n_points == r.n_points // 2
+        inner.free()
+        r.free()
+    finally:
+        dctx.close()
+
+
+def test_polygons_of_an_output_map():
+    gs, _ = pair("sample")
+    ctx = maps.Context(gs).load()
+    dctx, ov = overlay_of(ctx, None)
+    try:
+        om = ov.OutputMap(drop_degenerate=True, merge=True)
+        table = ov.FaceTable()
+        r = om.Rings(ov.h, skip_face0=True)
+        polys = r.polygons()
+        assert sorted(polys) == list(range(1, om.n_faces + 1))
+        for k, parts in polys.items():
+            assert sum(a2 for a2, _ in parts) == int(table["area2"][k - 1])
+            for a2, pts in parts:  # the points are the ring: their shoelace sum is its area2
+                x, y = pts[:, 0].astype(object), pts[:, 1].astype(object)
+                assert int((x * np.roll(y, -1) - np.roll(x, -1) * y).sum()) == a2 and pts.dtype == np.int64
+        unscaled = r.polygons(ctx.scaling)
+        k = next(iter(polys))
+        assert unscaled[k][0][0] == polys[k][0][0] and unscaled[k][0][1].dtype == np.float64
+        assert np.allclose(unscaled[k][0][1], ctx.scaling.unscale(polys[k][0][1]))
+        bb = ctx.scaling.unscale(polys[k][0][1])
+        assert bb[:, 0].min() >= -180.0 and bb[:, 0].max() <= 180.0
+        r.free()
+        om.free()
+    finally:
+        dctx.close()
