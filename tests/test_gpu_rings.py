@@ -3,7 +3,12 @@ plain-Python definition (tests/rings_ref.py), array for array: the hand cases an
 device's OWN output maps of the overlay tests' pairs (five calls, drop and merge on and off), the lattice pair's clip;
 against the host twin on the lattice pair's full intersection map (too large for the Python walk; tests/test_rings.py
 holds twin and definition equal); the exact area invariant against the device's own face table; overflow with canaries,
-the sizing call, the flags, an empty and a malformed map.  The CPU side is tests/test_rings.py."""
+the sizing call, the flags, an empty and a malformed map.  On the generated maps of tests/rings_planar.py: random planar
+subdivisions (also against faces and areas from a union-find over lattice triangles), junctions of thousands of incidences
+(several blocks of the one merge sort), one ring of exactly 2^k half-chains, chains of 100 000 points, face ids outside
+[0, 2^31), 1 060 000 half-chains (the second trip of every grid-stride loop; against the host twin); the rings of the output
+maps of fuzzed overlays (tests/test_gpu_overlay_fuzz.py's draw).  tests/rings_fuzz_more.py runs more seeds by hand.  The CPU
+side is tests/test_rings.py."""
 import os
 import sys
 
@@ -14,12 +19,18 @@ from rayjoin_amd import _capi, maps, ops, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import overlay_hard_pairs as H  # noqa: E402
 import rings_cases as K  # noqa: E402
+import rings_planar as P  # noqa: E402
 import rings_ref as D  # noqa: E402
+import test_gpu_overlay_fuzz as FZ  # noqa: E402
+from test_gpu_overlay_hard import run_overlay  # noqa: E402
 from test_gpu_overlay_map import host_arrays  # noqa: E402
 from test_gpu_overlay_merge import CALLS, DROP, MERGE, overlay_of, raw_map  # noqa: E402
 from test_overlay_map import pair  # noqa: E402
-from test_rings import NOPTS, SKIP0, as_map, twin_lib, twin_rings  # noqa: E402
+from test_overlay_ops import OPS  # noqa: E402
+from test_rings import (FIELD, NOPTS, PLANAR_GPU_SEEDS, SKIP0, as_map, check_face_order, check_shoelace, check_triangle_field, fan_walk,  # noqa: E402
+                        generated_case, planar_case, twin_lib, twin_rings)
 
 pytestmark = pytest.mark.gpu
 
@@ -274,3 +285,138 @@ def test_polygons_of_an_output_map():
         om.free()
     finally:
         dctx.close()
+
+
+# ---- generated maps (tests/rings_planar.py; tests/test_rings.py holds the conditions on the seeds) ---------------------------
+@pytest.mark.parametrize("seed", PLANAR_GPU_SEEDS)
+def test_planar_maps_equal_the_definition_and_the_union_find(handle, seed):
+    """a random planar subdivision, sheared or stretched over the whole coordinate range: the definition array for array, and
+    per face det x the number of lattice triangles the union-find gave it (an answer that does not come from the rings)"""
+    m, info, want, want_skip = planar_case(seed)
+    for flags, ref in ((0, want), (SKIP0 | NOPTS, want_skip)):
+        got = device_rings(handle, m, flags)
+        D.assert_same_rings(got, ref, (seed, flags))
+        P.assert_planar_answer(got, info, skip_face0=bool(flags & SKIP0), what=(seed, flags))
+
+
+@pytest.mark.parametrize("name", ["fan-3000", "sliver-fan-3000", "tie-fan-1500"])
+def test_one_junction_of_thousands_of_incidences(handle, name):
+    """5 999 directions of length 2^47 one unit apart; 3 000 whose cross products are a few units between products of 2^94;
+    1 500 equal directions that h alone orders (and a ring that mixes faces): 12 000, 6 000 and 7 200 incidences, several
+    blocks of the merge sort"""
+    m, want = generated_case(name)
+    got = device_rings(handle, m)
+    D.assert_same_rings(got, want, name)
+    if name == "fan-3000":
+        assert got["ring_half"].tolist() == fan_walk(3000) and D.area2_of(got["rings"]) == [0] and got["counts"]["n_rings"] == 1
+    if name == "tie-fan-1500":
+        assert got["counts"]["n_mixed"] == 1 and sorted(got["rings"]["flags"].tolist()) == [0, 1]
+        for flags in (SKIP0, NOPTS):
+            D.assert_same_rings(device_rings(handle, m, flags), D.rings_ref(*m, skip_face0=bool(flags & SKIP0), points=not flags & NOPTS), (name, flags))
+
+
+@pytest.mark.parametrize("n", [64, 65, 32768, 32769])
+def test_path_is_one_ring_within_the_round_budget(handle, n):
+    """one ring of exactly 2 n half-chains: for 2 n a power of two the doubling needs every round of its budget (an
+    exhausted budget is RJ_E_INTERNAL, which device_rings raises)"""
+    m, want = generated_case("path-%d" % n)
+    got = device_rings(handle, m)
+    assert got["counts"]["n_rings"] == 1 and got["counts"]["n_halves"] == 2 * n
+    D.assert_same_rings(got, want, n)
+
+
+def test_long_chains(handle):
+    """chains of 100 003 and 50 000 points under eight lanes each, odd h reversed; 74 and 79 zero-length edges at a chain's
+    end; the shoelace sum of every ring's points is its area2"""
+    m, want = generated_case("long-chains")
+    got = device_rings(handle, m)
+    D.assert_same_rings(got, want)
+    check_shoelace(got)
+
+
+def test_faces_outside_31_bits_sort_as_unsigned(handle):
+    m, want = generated_case("odd-faces")
+    for flags in (0, SKIP0, NOPTS, SKIP0 | NOPTS):
+        got = device_rings(handle, m, flags)
+        D.assert_same_rings(got, D.rings_ref(*m, skip_face0=bool(flags & SKIP0), points=not flags & NOPTS) if flags else want, flags)
+        check_face_order(got, bool(flags & SKIP0))
+
+
+def test_triangle_field_of_a_million_half_chains_equals_the_host_twin(handle):
+    """1 060 000 half-chains, more than the 1 048 576 threads of the largest grid: every grid-stride loop makes a second
+    trip.  Too large for the Python walk: every array against the host twin, and the closed forms"""
+    m = P.triangle_field(FIELD)
+    assert 2 * FIELD > 4096 * 256
+    got = device_rings(handle, m)
+    rc, want, _ = twin_rings(twin_lib(), m)
+    assert rc == 0
+    D.assert_same_rings(got, want)
+    check_triangle_field(got, FIELD)
+    face = got["rings"]["face"].astype(np.int64)
+    start = np.flatnonzero(np.r_[True, face[1:] != face[:-1]])
+    assert face[start].tolist() == list(range(1, 1001))  # the rings of a face are contiguous ...
+    assert (np.diff(got["rings"]["leader"].astype(np.int64))[face[1:] == face[:-1]] > 0).all()  # ... in leader order
+
+
+# ---- the rings of fuzzed overlays ---------------------------------------------------------------------------------------------
+FUZZ_EDGE_CAP = 4000  # edges of a pair: the output maps stay at a few thousand chains, the Python walk at a second or two
+# four pairs of kind "float" that ARE in general position (a lattice and a ring map) and two integer pairs.  Not every
+# "float" draw is: the cell walls of a ring map and the lines of a refined lattice can coincide (seed 325), and two lattices
+# (seeds 301, 305, 307) overlap along chains -- there the definition itself finds mixed rings (3 and 56 on the
+# (intersection, pair) maps of seeds 325 and 301), and the ring sums are not the face table's.
+FUZZ_SEEDS = [303, 306, 317, 320, 322, 330]
+
+
+def check_rings_of_a_fuzzed_overlay(oracle, seed):
+    """one pair of tests/test_gpu_overlay_fuzz.py's draw through the overlay; the rings of the device's output maps of
+    (intersection, pair) and of one more operation, drop and merge on and off, against the definition on the map read
+    back.  On a map of a "float" pair in which no ring is mixed, the rings of face k sum to row k - 1 of the device's own
+    face table.  Integer pairs ("ties") have overlapping chains and mixed rings, as the definition has them: equality only.
+    -> (kind, chains of all maps, maps, maps without a mixed ring)"""
+    cap, FZ.EDGE_CAP = FZ.EDGE_CAP, FUZZ_EDGE_CAP
+    try:
+        rng = np.random.default_rng(seed)
+        ctx, kind = FZ.draw_pair(rng)
+    finally:
+        FZ.EDGE_CAP = cap
+    use_grid = bool(rng.integers(0, 2))
+    gsize = int(rng.choice(FZ.GSIZES))
+    drawn = [None, OPS[int(rng.integers(1, len(OPS)))]]
+    om = H.oracle_maps(oracle, ctx)
+    pairs = oracle.lsi_grid(om[0], om[1], gsize)["eid"] if use_grid else oracle.lsi_brute(om[0], om[1])
+    dctx = ops.DeviceContext(ctx).LoadToDevice()
+    chains = n_maps = unmixed = 0
+    try:
+        ov = run_overlay(dctx, gsize if use_grid else None, len(pairs))
+        for call in drawn:
+            how, by = call if call is not None else ("intersection", "pair")
+            table = ov.FaceTable(how=how, by=by)
+            for flags in (0, DROP, MERGE, DROP | MERGE):
+                what = (seed, kind, how, by, flags)
+                omap = raw_map(ov, call, flags)
+                m = as_map(host_arrays(omap))
+                got = rings_of_output_map(ov.h, omap)
+                omap.free()
+                chains += len(m[2])
+                n_maps += 1
+                D.assert_same_rings(got, D.rings_ref(*m), what)
+                if got["counts"]["n_mixed"] == 0:
+                    unmixed += 1
+                    if kind == "float":
+                        sums = P.face_sums(got)
+                        sums.pop(0, None)
+                        assert [sums[k + 1] for k in range(len(table))] == [int(a) for a in table["area2"]] and len(sums) == len(table), what
+    finally:
+        dctx.close()
+    return kind, chains, n_maps, unmixed
+
+
+@pytest.mark.parametrize("seed", FUZZ_SEEDS)
+def test_rings_of_fuzzed_overlays_equal_the_definition(oracle, seed):
+    kind, chains, n_maps, unmixed = check_rings_of_a_fuzzed_overlay(oracle, seed)
+    print(seed, kind, chains, n_maps, unmixed)
+    assert n_maps == 8 and chains > 500 and kind == ("ties" if seed in (303, 306) else "float")
+    if kind == "float":  # general position: n_mixed == 0 on every map, and every map went through the face table check
+        assert unmixed == n_maps
+    else:
+        assert unmixed < n_maps

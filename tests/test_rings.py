@@ -2,7 +2,11 @@
 answers written out; the host twin of the device's per-element functions (tests/hosttwin/rings_twin.cc compiling
 rayjoin_amd/csrc/rj_rings.h) against that definition, every array and every count, on the hand cases, on the helper
 output maps of the overlay tests' pairs for every operation, and on the lattice pair's clip; the exact invariants that tie
-the rings to the face table.  The GPU side is tests/test_gpu_rings.py."""
+the rings to the face table.  On the generated maps of tests/rings_planar.py: random planar subdivisions whose faces and
+areas are known without the rings (union-find over lattice triangles), one junction of thousands of incidences, one ring of
+exactly 2^k half-chains, chains of 100 000 points, face ids outside [0, 2^31), more than 2^20 half-chains.  The GPU side is
+tests/test_gpu_rings.py."""
+import functools
 import ctypes as C
 import os
 import subprocess
@@ -18,6 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import overlay_merge_ref as G  # noqa: E402
 import overlay_ops_ref as R  # noqa: E402
 import rings_cases as K  # noqa: E402
+import rings_planar as P  # noqa: E402
 import rings_ref as D  # noqa: E402
 from test_overlay_map import records as pair_records  # noqa: E402
 from test_overlay_ops import OPS, records  # noqa: E402
@@ -300,3 +305,197 @@ def test_symbol_record_and_flags():
     assert _capi.RING_DTYPE == D.RING_DTYPE and _capi.RING_DTYPE.itemsize == 32
     assert (_capi.RJ_RINGS_SKIP_FACE0, _capi.RJ_RINGS_NO_POINTS, _capi.RJ_RING_MIXED) == (1, 2, 1)
     assert _capi.RINGS_COUNTS == D.COUNTS
+
+
+# ---- generated maps (tests/rings_planar.py) ------------------------------------------------------------------------------
+# the planar seeds the GPU test runs, and a dozen more for the twin
+PLANAR_GPU_SEEDS = (4, 5, 6, 7, 9, 13, 18, 28)
+PLANAR_SEEDS = PLANAR_GPU_SEEDS + (1, 2, 3, 8, 10, 11, 12, 14, 15, 16, 17, 19)
+GENERATED = {"fan-300": lambda: P.fan(300), "fan-3000": lambda: P.fan(3000), "sliver-fan-300": lambda: P.sliver_fan(300),
+             "sliver-fan-3000": lambda: P.sliver_fan(3000), "tie-fan-200": lambda: P.tie_fan(200), "tie-fan-1500": lambda: P.tie_fan(1500),
+             "long-chains": P.long_chains, "odd-faces": P.odd_faces}
+GENERATED.update({"path-%d" % n: functools.partial(P.path, n) for n in (64, 65, 32768, 32769)})
+
+
+@functools.lru_cache(maxsize=None)
+def planar_case(seed):
+    """-> (map, info, the definition's answer, the definition's answer under SKIP0 | NOPTS): computed once, shared, left unchanged"""
+    m, info = P.draw_planar(seed)
+    return m, info, D.rings_ref(*m), D.rings_ref(*m, skip_face0=True, points=False)
+
+
+@functools.lru_cache(maxsize=None)
+def generated_case(name):
+    """-> (map, the definition's answer): computed once, shared, left unchanged"""
+    m = GENERATED[name]()
+    return m, D.rings_ref(*m)
+
+
+def fan_walk(n):
+    """the one ring of P.fan(n), written out: chain c < n is the spoke to (T, T - c), chain n - 1 + k the spoke to (T - k, T);
+    counter-clockwise at the hub the chains are n - 1, ..., 0, n, ..., 2 n - 2.  The walk leaves the hub along chain 0, comes
+    back, and takes the clockwise neighbour each time: chains 0, 1, ..., n - 1, 2 n - 2, ..., n.  An even chain is digitised
+    from the hub (2 c leaves it), an odd one towards it (2 c + 1 leaves it)."""
+    out = []
+    for c in list(range(n)) + list(range(2 * n - 2, n - 1, -1)):
+        out.extend([2 * c, 2 * c + 1] if c % 2 == 0 else [2 * c + 1, 2 * c])
+    return out
+
+
+@pytest.mark.parametrize("seed", PLANAR_SEEDS)
+def test_planar_maps_have_the_faces_and_areas_of_the_union_find(twin, seed):
+    """the definition and the twin on a random planar subdivision, against an answer that does not come from the rings:
+    per face, det x the number of lattice triangles the union-find gave it"""
+    m, info, want, want_skip = planar_case(seed)
+    P.assert_planar_answer(want, info, what=seed)
+    P.assert_planar_answer(want_skip, info, skip_face0=True, what=seed)
+    for flags, ref in ((0, want), (SKIP0 | NOPTS, want_skip)):
+        rc, got, _ = twin_rings(twin, m, flags)
+        assert rc == 0
+        D.assert_same_rings(got, ref, (seed, flags))
+        P.assert_planar_answer(got, info, skip_face0=bool(flags & SKIP0), what=(seed, flags))
+
+
+def test_planar_seeds_have_holes_trees_long_rings_wide_junctions_and_wide_areas():
+    """what the seeds of the GPU test must contain, on the definition alone, so that test cannot run empty"""
+    holes = trees = longest = degree = bits = 0
+    for seed in PLANAR_GPU_SEEDS:
+        m, info, want, _ = planar_case(seed)
+        a2, face = D.area2_of(want["rings"]), want["rings"]["face"].tolist()
+        holes += sum(1 for f, a in zip(face, a2) if f != 0 and a < 0)
+        trees += sum(1 for a in a2 if a == 0)
+        longest = max(longest, int(np.diff(want["ring_first"].astype(np.int64)).max()))
+        ends = np.concatenate([m[0][m[1][:-1].astype(np.int64)], m[0][m[1][1:].astype(np.int64) - 1]])  # the chains' end points
+        degree = max(degree, int(np.unique(ends, axis=0, return_counts=True)[1].max()))
+        if info["full_range"]:
+            bits = max(bits, max(abs(a) for a in a2).bit_length())
+            assert m[0].max() > (1 << 46) - (1 << 40) and m[0].min() < -(1 << 46) + (1 << 40), seed
+    assert holes >= 1 and trees >= 1 and longest > 256 and degree == 8 and bits > 64, (holes, trees, longest, degree, bits)
+    assert sum(1 for s in PLANAR_GPU_SEEDS if planar_case(s)[1]["frame"]) in range(2, 7)
+    assert sum(1 for s in PLANAR_GPU_SEEDS if planar_case(s)[1]["full_range"]) in range(2, 7)
+
+
+def test_fan_is_one_ring_in_the_written_order(twin):
+    """599 directions of length 2^47 on one point, neighbours one unit apart: the walk written out in fan_walk"""
+    n = 300
+    m, want = generated_case("fan-%d" % n)
+    assert want["counts"] == dict(n_rings=1, n_halves=2 * (2 * n - 1), n_points=2 * (2 * n - 1), n_mixed=0, n_skipped=0)
+    assert want["ring_half"].tolist() == fan_walk(n) and D.area2_of(want["rings"]) == [0]
+    for flags in (0, NOPTS):
+        rc, got, _ = twin_rings(twin, m, flags)
+        assert rc == 0
+        D.assert_same_rings(got, D.rings_ref(*m, points=not flags) if flags else want, flags)
+
+
+def test_sliver_fan_orders_cross_products_of_one_unit(twin):
+    """300 directions whose cross products are j - j' between two products of 2^94"""
+    m, want = generated_case("sliver-fan-300")
+    inc = [(int(a[0]) - int(b[0]), int(a[1]) - int(b[1])) for a, b in ((m[0][2 * c + 1 - c % 2], m[0][2 * c + c % 2]) for c in range(300))]
+    assert all(0 < abs(p[0] * q[1] - p[1] * q[0]) < 300 for p, q in zip(inc, inc[1:])) and min(min(p) for p in inc) > 1 << 46
+    assert float(inc[0][0]) * float(inc[1][1]) == float(inc[0][1]) * float(inc[1][0])  # (what a comparator in double would see)
+    assert want["counts"]["n_rings"] == 1 and want["counts"]["n_halves"] == 600 and D.area2_of(want["rings"]) == [0]
+    rc, got, _ = twin_rings(twin, m)
+    assert rc == 0
+    D.assert_same_rings(got, want)
+
+
+def test_tie_fan_is_ordered_by_h(twin):
+    """200 chains along one direction from each of two hubs, 300 spokes round them: h alone orders the ties; the first
+    hub's ring mixes faces, the second's does not"""
+    m, want = generated_case("tie-fan-200")
+    assert want["counts"] == dict(n_rings=2, n_halves=2000, n_points=2000, n_mixed=1, n_skipped=0)
+    assert sorted(want["rings"]["flags"].tolist()) == [0, 1] and want["rings"]["face"][want["rings"]["flags"] == 0].tolist() == [5]
+    for flags in (0, SKIP0, NOPTS):
+        rc, got, _ = twin_rings(twin, m, flags)
+        assert rc == 0
+        D.assert_same_rings(got, D.rings_ref(*m, skip_face0=bool(flags & SKIP0), points=not flags & NOPTS) if flags else want, flags)
+
+
+@pytest.mark.parametrize("n", [64, 65, 32768, 32769])
+def test_path_is_one_ring_within_the_round_budget(twin, n):
+    """one ring of exactly 2 n half-chains.  The budget is the smallest `rounds` with 2^(rounds - 1) >= 2 n; a ring of
+    2^k half-chains needs all k + 1 of them, the last one being the round in which no minimum changes"""
+    m, want = generated_case("path-%d" % n)
+    assert want["counts"] == dict(n_rings=1, n_halves=2 * n, n_points=2 * n, n_mixed=0, n_skipped=0)
+    rc, got, rounds = twin_rings(twin, m)
+    assert rc == 0  # (5 = RJ_E_INTERNAL: the budget ran out)
+    D.assert_same_rings(got, want, n)
+    budget = (2 * n - 1).bit_length() + 1
+    assert rounds[0] <= budget and rounds[1] <= budget
+    if 2 * n & (2 * n - 1) == 0:
+        assert rounds[0] == budget == {128: 8, 65536: 17}[2 * n]
+
+
+def check_shoelace(got):
+    row = got["ring_row"].astype(np.int64)
+    assert [P.shoelace(got["ring_xy"][row[k]:row[k + 1]]) for k in range(len(got["rings"]))] == D.area2_of(got["rings"])
+
+
+def test_long_chains(twin):
+    """chains of 100 003 and 50 000 points, 74 and 79 zero-length edges at a chain's end: every array against the
+    definition, and the shoelace sum of every ring's points is its area2"""
+    m, want = generated_case("long-chains")
+    lengths = np.diff(m[1].astype(np.int64)).tolist()
+    assert lengths == [100_003, 50_000, 100_083] and (m[0][100_003:100_003 + 75] == m[0][100_003]).all() and (m[0][-81:] == m[0][-1]).all()
+    assert [(f, le) for f, le, *_ in D.ring_list(*m)[0]] == [(0, 1), (1, 0), (1, 4), (2, 5)]
+    a2 = D.area2_of(want["rings"])
+    assert a2[0] == -a2[1] and a2[2] == -a2[3] and a2[1] > 3 * a2[3] > 0 and want["counts"]["n_points"] == 2 * (100_002 + 49_999 + 100_082)
+    assert P.shoelace(np.array([[0, 0], [-(1 << 46), 5], [(1 << 46) - 1, -(1 << 46)]])) == (1 << 92) - 5 * ((1 << 46) - 1)
+    check_shoelace(want)
+    rc, got, _ = twin_rings(twin, m)
+    assert rc == 0
+    D.assert_same_rings(got, want)
+
+
+def check_face_order(got, skip_face0):
+    """the rings ascend by ((uint32) face, leader): negative faces behind every non-negative one"""
+    face, leader = got["rings"]["face"].astype(np.int64), got["rings"]["leader"].astype(np.int64)
+    key = [((f & 0xFFFFFFFF) << 32) | le for f, le in zip(face.tolist(), leader.tolist())]
+    assert key == sorted(key) and len(set(key)) == len(key)
+    neg = np.flatnonzero(face < 0)
+    assert len(neg) and (face[neg[0]:] < 0).all() and (face[:neg[0]] >= 0).all()
+    assert bool((face == 0).any()) != skip_face0
+
+
+def test_faces_outside_31_bits_sort_as_unsigned(twin):
+    m, want = generated_case("odd-faces")
+    assert set(P.ODD_FACES) <= set(m[2].tolist()) | set(m[3].tolist())
+    assert want["rings"]["face"].tolist() == sorted(want["rings"]["face"].tolist(), key=lambda f: f & 0xFFFFFFFF)
+    assert want["rings"]["face"][-1] == -1 and (want["rings"]["face"] == -(1 << 31)).any() and want["counts"]["n_rings"] == 28
+    for flags in (0, SKIP0):
+        ref = D.rings_ref(*m, skip_face0=True) if flags else want
+        check_face_order(ref, bool(flags))
+        rc, got, _ = twin_rings(twin, m, flags)
+        assert rc == 0
+        D.assert_same_rings(got, ref, flags)
+
+
+FIELD = 530_000
+
+
+def check_triangle_field(got, n):
+    """the closed forms of P.triangle_field(n): every half-chain is a ring of its own of three points and area2 +-36;
+    the rings of face f are the half-chains of column f - 1, contiguous and in leader order"""
+    assert got["counts"] == dict(n_rings=2 * n, n_halves=2 * n, n_points=6 * n, n_mixed=0, n_skipped=0)
+    h = np.arange(2 * n, dtype=np.int64)
+    order = np.lexsort((h, (h >> 1) % 1000))
+    assert np.array_equal(got["rings"]["leader"], order) and np.array_equal(got["ring_half"], order)
+    assert np.array_equal(got["rings"]["face"], (order >> 1) % 1000 + 1) and not got["rings"]["flags"].any()
+    assert np.array_equal(got["ring_first"], np.arange(2 * n + 1)) and np.array_equal(got["ring_row"], 3 * np.arange(2 * n + 1))
+    ccw = ((order >> 1) % 3 == 2) == (order & 1).astype(bool)  # (a chain digitised clockwise and walked backwards is counter-clockwise)
+    assert np.array_equal(got["rings"]["area2_lo"].view(np.int64), np.where(ccw, 36, -36))
+    assert np.array_equal(got["rings"]["area2_hi"], np.where(ccw, 0, -1))
+
+
+def test_triangle_field_on_the_twin_has_the_closed_forms(twin):
+    """1 060 000 half-chains, more than the 1 048 576 threads of the device's largest grid"""
+    rc, got, _ = twin_rings(twin, P.triangle_field(FIELD))
+    assert rc == 0 and 2 * FIELD > 4096 * 256
+    check_triangle_field(got, FIELD)
+    # and on a field small enough for the definition
+    m = P.triangle_field(2500)
+    want = D.rings_ref(*m)
+    check_triangle_field(want, 2500)
+    rc, got, _ = twin_rings(twin, m)
+    assert rc == 0
+    D.assert_same_rings(got, want)
