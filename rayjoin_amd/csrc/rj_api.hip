@@ -17,6 +17,7 @@
 #include "rj_kernels.h"
 #include "rj_overlay_dev.h"
 #include "rj_overlay_ops.h"
+#include "rj_pipeline.h"
 #include "rj_rings.h"
 
 using namespace rj;
@@ -258,7 +259,7 @@ struct rj_handle_s {
   uint64_t ord_cap = 0;
   MortonKey *ord_kin = nullptr, *ord_kout = nullptr;
   uint32_t *ord_vin = nullptr, *ord_vout = nullptr;
-  void* ord_temp = nullptr;
+  char* ord_temp = nullptr;
   size_t ord_temp_bytes = 0;
   int leaf_order = 1;        // "leaf_order" (default 1, or RJ_LEAF_ORDER): what the NEXT rj_build_lbvh makes a leaf of
   int debug_run_cap = 0;     // experiments: edges per polyline run (0: by the mean chain length)
@@ -1111,12 +1112,7 @@ static int ensure_sort_scratch(rj_handle h, uint64_t n) {
   }
   size_t need = 0;
   RJ_HIP(h, sort_morton_pairs(h->stream, nullptr, need, h->ord_kin, h->ord_kout, h->ord_vin, h->ord_vout, n));
-  if (need > h->ord_temp_bytes) {
-    (void) hipFree(h->ord_temp);
-    h->ord_temp = nullptr; h->ord_temp_bytes = 0;
-    RJ_HIP(h, hipMalloc(&h->ord_temp, need));
-    h->ord_temp_bytes = need;
-  }
+  RJ_HIP(h, grow_block(&h->ord_temp, &h->ord_temp_bytes, need));
   return RJ_OK;
 }
 
@@ -1130,16 +1126,10 @@ static int build_strips(rj_handle h, BvhState& b, bool with_sky) {
   //  and serves the map alone -- RJ_E_NOMEM only under "pip_columns" 1)
   const bool forced = h->pip_columns == 1;
   auto scratch = [&](size_t bytes) -> int {
-    if (bytes <= h->strip_scratch_bytes) return RJ_OK;
-    (void) hipFree(h->strip_scratch);
-    h->strip_scratch = nullptr; h->strip_scratch_bytes = 0;
-    const hipError_t e = hipMalloc((void**) &h->strip_scratch, bytes);
-    if (e != hipSuccess) {
-      (void) hipGetLastError();
-      return forced ? fail(h, RJ_E_NOMEM, "rj_build_lbvh: %zu bytes of scratch for the column index: %s", bytes, hipGetErrorString(e)) : -1;
-    }
-    h->strip_scratch_bytes = bytes;
-    return RJ_OK;
+    const hipError_t e = grow_block(&h->strip_scratch, &h->strip_scratch_bytes, bytes);
+    if (e == hipSuccess) return RJ_OK;
+    (void) hipGetLastError();
+    return forced ? fail(h, RJ_E_NOMEM, "rj_build_lbvh: %zu bytes of scratch for the column index: %s", bytes, hipGetErrorString(e)) : -1;
   };
   // the strip width: widest power of two below 2.3 x the mean x-extent of a segment (rj_device.h, DeviceStrips)
   size_t scan_bytes = 0;
@@ -2532,28 +2522,31 @@ int rj_overlay_edge_xsects(rj_handle h, int im, const uint32_t* pairs_dev, uint6
   if (n >= (1ull << 32)) return fail(h, RJ_E_INVALID, "rj_overlay_edge_xsects: too many intersections");
   if (int r = set_device(h)) return r;
   // carve all temporaries out of one grow-only arena
-  auto up = [](size_t v) { return (v + 255) & ~(size_t) 255; };
   size_t sort_bytes = 0;
   RJ_HIP(h, sort_pairs_u64_u32(h->stream, nullptr, sort_bytes, (const uint64_t*) nullptr, (uint64_t*) nullptr,
                               (const uint32_t*) nullptr, (uint32_t*) nullptr, n));
-  const size_t need = up(48 * n) + 2 * up(8 * n) + 4 * up(4 * n) + up(16 * n) + up(sort_bytes);
-  if (need > h->arena_bytes) {
-    (void) hipFree(h->arena);
-    h->arena = nullptr; h->arena_bytes = 0;
-    RJ_HIP(h, hipMalloc((void**) &h->arena, need));
-    h->arena_bytes = need;
-  }
-  char* p = h->arena;
-  auto take = [&](size_t bytes) { char* r = p; p += up(bytes); return r; };
-  XsectRec* tmp = (XsectRec*) take(48 * n);
-  uint64_t* kin = (uint64_t*) take(8 * n);
-  uint64_t* kout = (uint64_t*) take(8 * n);
-  uint32_t* vin = (uint32_t*) take(4 * n);
-  uint32_t* vout = (uint32_t*) take(4 * n);
-  uint32_t* closest = (uint32_t*) take(4 * n);
-  int32_t* face = (int32_t*) take(4 * n);
-  int64_t* mid = (int64_t*) take(16 * n);
-  void* temp = take(sort_bytes);
+  XsectRec* tmp;
+  uint64_t *kin, *kout;
+  uint32_t *vin, *vout, *closest;
+  int32_t* face;
+  int64_t* mid;
+  void* temp;
+  Carve A;
+  auto carve = [&]() {
+    A.used = 0;
+    tmp = A.take<XsectRec>(n);
+    kin = A.take<uint64_t>(n); kout = A.take<uint64_t>(n);
+    vin = A.take<uint32_t>(n); vout = A.take<uint32_t>(n);
+    closest = A.take<uint32_t>(n);
+    face = A.take<int32_t>(n);
+    mid = A.take<int64_t>(2 * n);
+    temp = A.take<char>(sort_bytes);
+    (void) A.take<char>(0);  // (the arena's size: whole 256-byte units)
+  };
+  carve();
+  RJ_HIP(h, grow_block(&h->arena, &h->arena_bytes, A.used));
+  A.base = h->arena;
+  carve();
   size_t temp_bytes = sort_bytes;
   int rc = RJ_OK;
   hipError_t e = hipSuccess;
@@ -2583,6 +2576,27 @@ int rj_overlay_edge_xsects(rj_handle h, int im, const uint32_t* pairs_dev, uint6
   return RJ_OK;
 }
 
+// what the overlay's entry points check of the loaded maps, the records and the vertex faces -- with each call's own
+// checks of its outputs (null_output) and of its 32-bit indices (too_many: what there is too much of) in their places --,
+// then the device, the streams joined and the two maps' arrays
+static int overlay_begin(rj_handle h, const char* name, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
+                         const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, bool null_output, const char* too_many,
+                         OverlayFacesMap m[2]) {
+  if (!h->map[0].present || !h->map[1].present) return fail(h, RJ_E_INVALID, "%s: both maps must be uploaded", name);
+  if (n && (!xsects0_dev || !xsects1_dev)) return fail(h, RJ_E_INVALID, "%s: null records", name);
+  if ((h->map[0].np && !vertex_face0_dev) || (h->map[1].np && !vertex_face1_dev))
+    return fail(h, RJ_E_INVALID, "%s: null vertex faces", name);
+  if (null_output) return fail(h, RJ_E_INVALID, "%s: null output", name);
+  if (too_many) return fail(h, RJ_E_INVALID, "%s: too many %s", name, too_many);
+  if (int r = set_device(h)) return r;
+  RJ_HIP(h, join_aux(h));
+  for (int im = 0; im < 2; im++) {
+    const MapState& s = h->map[im];
+    m[im] = OverlayFacesMap{s.pts, s.edge_chain, s.edge_begin, s.left, s.right, s.ne, s.nc};
+  }
+  return RJ_OK;
+}
+
 // rj_overlay_faces (op == null: the intersection's own kernels) and rj_overlay_faces_op
 static int overlay_faces_call(rj_handle h, const char* name, const rj_xsect* xsects0_dev, const rj_xsect* xsects1_dev, uint64_t n,
                               const int32_t* vertex_face0_dev, const int32_t* vertex_face1_dev, uint64_t capacity,
@@ -2590,19 +2604,10 @@ static int overlay_faces_call(rj_handle h, const char* name, const rj_xsect* xse
   RJ_CHECK_H(h);
   if (!n_faces) return fail(h, RJ_E_INVALID, "%s: n_faces is null", name);
   *n_faces = 0;
-  if (!h->map[0].present || !h->map[1].present) return fail(h, RJ_E_INVALID, "%s: both maps must be uploaded", name);
-  if (n && (!xsects0_dev || !xsects1_dev)) return fail(h, RJ_E_INVALID, "%s: null records", name);
-  if ((h->map[0].np && !vertex_face0_dev) || (h->map[1].np && !vertex_face1_dev))
-    return fail(h, RJ_E_INVALID, "%s: null vertex faces", name);
-  if (capacity && !out_dev) return fail(h, RJ_E_INVALID, "%s: null output", name);
-  if (n >= (1ull << 32)) return fail(h, RJ_E_INVALID, "%s: too many intersections", name);
-  if (int r = set_device(h)) return r;
-  RJ_HIP(h, join_aux(h));
   OverlayFacesMap m[2];
-  for (int im = 0; im < 2; im++) {
-    const MapState& s = h->map[im];
-    m[im] = OverlayFacesMap{s.pts, s.edge_chain, s.edge_begin, s.left, s.right, s.ne, s.nc};
-  }
+  if (int r = overlay_begin(h, name, xsects0_dev, xsects1_dev, n, vertex_face0_dev, vertex_face1_dev, capacity && !out_dev,
+                            n >= (1ull << 32) ? "intersections" : nullptr, m))
+    return r;
   const rj_xsect* const xs[2] = {xsects0_dev, xsects1_dev};
   const int32_t* const vf[2] = {vertex_face0_dev, vertex_face1_dev};
   uint64_t rows = 0;
@@ -2623,22 +2628,14 @@ static int overlay_map_call(rj_handle h, const char* name, const rj_xsect* xsect
   if (!counts) return fail(h, RJ_E_INVALID, "%s: counts is null", name);
   counts->n_chains = counts->n_points = counts->n_faces = 0;
   if (flags & ~(uint32_t) (RJ_OVM_DROP_DEGENERATE | RJ_OVM_MERGE_PIECES)) return fail(h, RJ_E_INVALID, "%s: unknown flags 0x%x", name, flags);
-  if (!h->map[0].present || !h->map[1].present) return fail(h, RJ_E_INVALID, "%s: both maps must be uploaded", name);
-  if (n && (!xsects0_dev || !xsects1_dev)) return fail(h, RJ_E_INVALID, "%s: null records", name);
-  if ((h->map[0].np && !vertex_face0_dev) || (h->map[1].np && !vertex_face1_dev))
-    return fail(h, RJ_E_INVALID, "%s: null vertex faces", name);
-  if ((point_capacity && !xy_dev) || (chain_capacity && (!row_index_dev || !left_dev || !right_dev)) || (face_capacity && !face_pairs_dev))
-    return fail(h, RJ_E_INVALID, "%s: null output", name);
+  const bool null_output =
+      (point_capacity && !xy_dev) || (chain_capacity && (!row_index_dev || !left_dev || !right_dev)) || (face_capacity && !face_pairs_dev);
   // (row_index is 32-bit: every point the maps could emit must have a slot below 2^32)
-  if (n >= (1ull << 32) || h->map[0].np + h->map[1].np + 4 * n >= (1ull << 32))
-    return fail(h, RJ_E_INVALID, "%s: too many points for a 32-bit row_index", name);
-  if (int r = set_device(h)) return r;
-  RJ_HIP(h, join_aux(h));
+  const bool too_many = n >= (1ull << 32) || h->map[0].np + h->map[1].np + 4 * n >= (1ull << 32);
   OverlayFacesMap m[2];
-  for (int im = 0; im < 2; im++) {
-    const MapState& s = h->map[im];
-    m[im] = OverlayFacesMap{s.pts, s.edge_chain, s.edge_begin, s.left, s.right, s.ne, s.nc};
-  }
+  if (int r = overlay_begin(h, name, xsects0_dev, xsects1_dev, n, vertex_face0_dev, vertex_face1_dev, null_output,
+                            too_many ? "points for a 32-bit row_index" : nullptr, m))
+    return r;
   const uint64_t np[2] = {h->map[0].np, h->map[1].np};
   const rj_xsect* const xs[2] = {xsects0_dev, xsects1_dev};
   const int32_t* const vf[2] = {vertex_face0_dev, vertex_face1_dev};

@@ -10,6 +10,7 @@
 // (cell, eid) 64-bit keys + one radix sort instead of the reference's count / scan / atomic fill,
 // whose order inside a cell is whatever the atomics produced.
 #include "rj_kernels.h"
+#include "rj_pipeline.h"
 
 #include <cstring>
 #include <rocprim/device/device_scan.hpp>
@@ -184,26 +185,20 @@ __global__ __launch_bounds__(256) void k_pip_grid(GridPipArgs A) {
   }
 }
 
-static inline int grid_blocks(uint64_t items, int per_block, int max_blocks) {
-  uint64_t b = (items + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  return (int) (b > (uint64_t) max_blocks ? max_blocks : b);
-}
-
 }  // namespace
 
 hipError_t launch_grid_count(hipStream_t st, const Seg* seg, uint64_t ne, int g, double scale, uint32_t* counts,
                              unsigned long long* total) {
-  if (ne) hipLaunchKernelGGL(k_grid_count, dim3(grid_blocks(ne, 256, 8192)), dim3(256), 0, st, seg, ne, g, scale, counts, total);
+  if (ne) hipLaunchKernelGGL(k_grid_count, dim3(blocks_for(ne, 8192)), dim3(256), 0, st, seg, ne, g, scale, counts, total);
   return hipGetLastError();
 }
 hipError_t launch_grid_emit(hipStream_t st, const Seg* seg, uint64_t ne, int g, double scale, uint64_t* keys,
                             unsigned long long* cursor) {
-  if (ne) hipLaunchKernelGGL(k_grid_emit, dim3(grid_blocks(ne, 256, 8192)), dim3(256), 0, st, seg, ne, g, scale, keys, cursor);
+  if (ne) hipLaunchKernelGGL(k_grid_emit, dim3(blocks_for(ne, 8192)), dim3(256), 0, st, seg, ne, g, scale, keys, cursor);
   return hipGetLastError();
 }
 hipError_t launch_grid_unpack(hipStream_t st, const uint64_t* keys, uint64_t n, uint32_t* eids) {
-  if (n) hipLaunchKernelGGL(k_grid_unpack, dim3(grid_blocks(n, 256, 8192)), dim3(256), 0, st, keys, n, eids);
+  if (n) hipLaunchKernelGGL(k_grid_unpack, dim3(blocks_for(n, 8192)), dim3(256), 0, st, keys, n, eids);
   return hipGetLastError();
 }
 __global__ void k_grid_noop() {}
@@ -216,11 +211,11 @@ hipError_t scan_cell_counts(hipStream_t st, void* temp, size_t& temp_bytes, cons
 }
 hipError_t launch_lsi_grid(hipStream_t st, const GridLsiArgs& a) {
   const uint64_t ncells = (uint64_t) a.g * a.g;
-  hipLaunchKernelGGL(k_lsi_grid, dim3(grid_blocks(ncells, 256, 16384)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_lsi_grid, dim3(blocks_for(ncells, 16384)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 hipError_t launch_pip_grid(hipStream_t st, const GridPipArgs& a) {
-  if (a.n) hipLaunchKernelGGL(k_pip_grid, dim3(grid_blocks(a.n, 256, 16384)), dim3(256), 0, st, a);
+  if (a.n) hipLaunchKernelGGL(k_pip_grid, dim3(blocks_for(a.n, 16384)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -22,6 +22,7 @@
 #include "rj_overlay.h"
 #include "rj_overlay_dev.h"
 #include "rj_overlay_ops.h"
+#include "rj_pipeline.h"
 
 namespace rj {
 
@@ -194,6 +195,19 @@ __global__ __launch_bounds__(kThreads) void k_ovf_emit(const uint64_t* __restric
   }
 }
 
+// one pass over map im: the intersection's kernel, or the operation's when there is one
+template <bool kWrite>
+void launch_contrib(hipStream_t st, const OverlayOp* op, int im, const OverlayFacesMap& m, const rj_xsect* xs, uint64_t n,
+                    const int32_t* vertex_face, uint64_t* keys, Area2* vals, uint32_t* wave_count, const uint64_t* wave_base, uint64_t cap) {
+  const dim3 grid(blocks_for(64 * ((m.ne + 63) / 64), 8192));  // a lane per edge, whole waves
+  if (op)
+    hipLaunchKernelGGL(k_ovf_contrib_op<kWrite>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin, (const int32_t*) m.left,
+                       (const int32_t*) m.right, m.ne, (const Rec48*) xs, n, vertex_face, keys, vals, wave_count, wave_base, cap, op->how, op->by);
+  else
+    hipLaunchKernelGGL(k_ovf_contrib<kWrite>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin, (const int32_t*) m.left,
+                       (const int32_t*) m.right, m.ne, (const Rec48*) xs, n, vertex_face, keys, vals, wave_count, wave_base, cap);
+}
+
 __global__ void k_ovf_noop() {}
 
 }  // namespace
@@ -208,20 +222,22 @@ hipError_t overlay_faces_device(hipStream_t st, const OverlayFacesMap maps[2], c
                                 char** scratch, size_t* scratch_bytes, const OverlayOp* op) {
   uint64_t total = 0;
   for (int im = 0; im < 2; im++) total += max_contributions(maps[im].ne, maps[im].nc, n);
-  size_t sort_bytes = 0, rbk_bytes = 0;
-  hipError_t e = rocprim::radix_sort_pairs(nullptr, sort_bytes, (const uint64_t*) nullptr, (uint64_t*) nullptr, (const Area2*) nullptr,
-                                           (Area2*) nullptr, (size_t) total, 0, 64, st);
-  if (e != hipSuccess) return e;
-  e = rocprim::reduce_by_key(nullptr, rbk_bytes, (const uint64_t*) nullptr, (const Area2*) nullptr, (size_t) total, (uint64_t*) nullptr,
-                             (Area2*) nullptr, (uint64_t*) nullptr, Area2Sum(), rocprim::equal_to<uint64_t>(), st);
-  if (e != hipSuccess) return e;
   const uint64_t max_waves = (maps[0].ne > maps[1].ne ? maps[0].ne : maps[1].ne) / 64 + 1;
-  size_t scan_bytes = 0;
-  e = rocprim::exclusive_scan(nullptr, scan_bytes, (const uint32_t*) nullptr, (uint64_t*) nullptr, (uint64_t) 0, (size_t) max_waves,
-                              rocprim::plus<uint64_t>(), st);
-  if (e != hipSuccess) return e;
-  size_t temp_bytes = sort_bytes > rbk_bytes ? sort_bytes : rbk_bytes;
-  if (scan_bytes > temp_bytes) temp_bytes = scan_bytes;
+  TempSize temp_size;
+  temp_size([&](size_t& b) {
+    return rocprim::radix_sort_pairs(nullptr, b, (const uint64_t*) nullptr, (uint64_t*) nullptr, (const Area2*) nullptr, (Area2*) nullptr,
+                                     (size_t) total, 0, 64, st);
+  });
+  temp_size([&](size_t& b) {
+    return rocprim::reduce_by_key(nullptr, b, (const uint64_t*) nullptr, (const Area2*) nullptr, (size_t) total, (uint64_t*) nullptr,
+                                  (Area2*) nullptr, (uint64_t*) nullptr, Area2Sum(), rocprim::equal_to<uint64_t>(), st);
+  });
+  temp_size([&](size_t& b) {
+    return rocprim::exclusive_scan(nullptr, b, (const uint32_t*) nullptr, (uint64_t*) nullptr, (uint64_t) 0, (size_t) max_waves,
+                                   rocprim::plus<uint64_t>(), st);
+  });
+  if (temp_size.error != hipSuccess) return temp_size.error;
+  const size_t temp_bytes = temp_size.bytes;
   uint64_t *kin, *kout, *nu, *rows;
   Area2 *vin, *vout;
   uint32_t* wcount;
@@ -241,13 +257,8 @@ hipError_t overlay_faces_device(hipStream_t st, const OverlayFacesMap maps[2], c
     temp = A.take<char>(temp_bytes);
   };
   carve();
-  const size_t need = A.used;
-  if (*scratch_bytes < need) {
-    (void) hipFree(*scratch);
-    *scratch = nullptr; *scratch_bytes = 0;
-    if ((e = hipMalloc((void**) scratch, need)) != hipSuccess) return e;
-    *scratch_bytes = need;
-  }
+  hipError_t e = grow_block(scratch, scratch_bytes, A.used);
+  if (e != hipSuccess) return e;
   A.base = *scratch;
   carve();
   // (the unique keys and their sums reuse the sort's input arrays: reduce_by_key reads kout / vout)
@@ -260,27 +271,12 @@ hipError_t overlay_faces_device(hipStream_t st, const OverlayFacesMap maps[2], c
     const uint64_t part = max_contributions(m.ne, m.nc, n);
     if (m.ne) {
       const uint64_t waves = (m.ne + 63) / 64;
-      const dim3 grid(grid_for(64 * waves, 8192));
-      if (op)
-        hipLaunchKernelGGL(k_ovf_contrib_op<false>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin,
-                           (const int32_t*) m.left, (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im], kin + at,
-                           vin + at, wcount, (const uint64_t*) nullptr, part, op->how, op->by);
-      else
-        hipLaunchKernelGGL(k_ovf_contrib<false>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin, (const int32_t*) m.left,
-                           (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im], kin + at, vin + at, wcount,
-                           (const uint64_t*) nullptr, part);
+      launch_contrib<false>(st, op, im, m, xsects[im], n, vertex_face[im], kin + at, vin + at, wcount, nullptr, part);
       if ((e = hipGetLastError()) != hipSuccess) return e;
       size_t sb = temp_bytes;
       if ((e = rocprim::exclusive_scan(temp, sb, wcount, wbase, (uint64_t) 0, (size_t) waves, rocprim::plus<uint64_t>(), st)) != hipSuccess)
         return e;
-      if (op)
-        hipLaunchKernelGGL(k_ovf_contrib_op<true>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin,
-                           (const int32_t*) m.left, (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im], kin + at,
-                           vin + at, wcount, (const uint64_t*) wbase, part, op->how, op->by);
-      else
-        hipLaunchKernelGGL(k_ovf_contrib<true>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin, (const int32_t*) m.left,
-                           (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im], kin + at, vin + at, wcount,
-                           (const uint64_t*) wbase, part);
+      launch_contrib<true>(st, op, im, m, xsects[im], n, vertex_face[im], kin + at, vin + at, wcount, wbase, part);
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     at += part;
@@ -291,7 +287,7 @@ hipError_t overlay_faces_device(hipStream_t st, const OverlayFacesMap maps[2], c
   if ((e = rocprim::reduce_by_key(temp, tb, kout, vout, (size_t) total, ukeys, usums, nu, Area2Sum(), rocprim::equal_to<uint64_t>(),
                                   st)) != hipSuccess)
     return e;
-  hipLaunchKernelGGL(k_ovf_emit, dim3(grid_for(capacity < total ? capacity : total, 4096)), dim3(kThreads), 0, st, ukeys, usums, nu,
+  hipLaunchKernelGGL(k_ovf_emit, dim3(blocks_for(capacity < total ? capacity : total, 4096)), dim3(kThreads), 0, st, ukeys, usums, nu,
                      capacity, out, rows);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   // the one read-back: the row count

@@ -1,6 +1,5 @@
 // rj_overlay_dev.h -- what the overlay's device passes share (rj_overlay.hip: the face table, rj_overlay_map.hip: the
-// output map): the wave-wide record search, the launch width and the scratch carving; and what rj_api.hip calls in
-// rj_overlay_map.hip.  HIP only.
+// output map): the wave-wide record search; and what rj_api.hip calls in rj_overlay_map.hip.  HIP only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,8 +10,6 @@
 
 namespace rj {
 namespace overlay {
-
-constexpr int kThreads = 256;
 
 // first record whose eid[im] >= eid, found by the whole wave: 64 probes per step (a dependent load per 64x narrowing,
 // where one lane's binary search makes one per halving -- those serial loads were most of this pass).  Wave-uniform.
@@ -29,23 +26,6 @@ __device__ __forceinline__ uint64_t wave_first_record(const Rec48* __restrict__ 
   const bool below = b + lane < e && (uint64_t) xs[b + lane].eid[im] < eid;
   return b + (uint64_t) __popcll(__ballot(below));
 }
-
-inline int grid_for(uint64_t threads, int cap_blocks) {
-  uint64_t b = (threads + kThreads - 1) / kThreads;
-  return (int) (b < 1 ? 1 : (b > (uint64_t) cap_blocks ? (uint64_t) cap_blocks : b));
-}
-
-struct Carve {
-  char* base = nullptr;
-  size_t used = 0;
-  template <typename T>
-  T* take(uint64_t count) {
-    used = (used + 255) & ~(size_t) 255;
-    T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
-    used += count * sizeof(T);
-    return p;
-  }
-};
 
 }  // namespace overlay
 

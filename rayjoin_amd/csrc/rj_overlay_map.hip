@@ -30,6 +30,7 @@
 #include "rj_overlay_map.h"
 #include "rj_overlay_dev.h"
 #include "rj_overlay_ops.h"
+#include "rj_pipeline.h"
 
 namespace rj {
 
@@ -183,7 +184,7 @@ __device__ __forceinline__ int32_t face_id(const uint64_t* ukeys, uint64_t nf, u
 __global__ __launch_bounds__(kThreads) void k_ovm_keep(const uint32_t* __restrict__ row, const Slots* __restrict__ totals, uint64_t bound,
                                                        Slots* __restrict__ kept) {
   const uint64_t nch = totals->chains;
-  for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < bound; i += (uint64_t) gridDim.x * blockDim.x) {
+  RJ_GRID_STRIDE(i, bound) {
     const uint64_t len = i < nch ? (uint64_t) (row[i + 1] - row[i]) : 0;
     kept[i] = len >= 2 ? Slots{len, 1} : Slots{0, 0};
   }
@@ -235,7 +236,7 @@ __global__ __launch_bounds__(kThreads) void k_ovm_compact_points(const int64_t* 
                                                                  const Slots* __restrict__ kept, const Slots* __restrict__ kept_base,
                                                                  int64_t* __restrict__ xy, uint64_t point_cap) {
   const uint64_t np = totals->points;
-  for (uint64_t j = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; j < np; j += (uint64_t) gridDim.x * blockDim.x) {
+  RJ_GRID_STRIDE(j, np) {
     const uint32_t i = point_piece[j];
     if (!kept[i].chains) continue;
     const uint64_t to = kept_base[i].points + (j - staged_row[i]);
@@ -268,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void k_ovm_join(const uint64_t* __restric
                                                        const uint32_t* __restrict__ prev_kept, const Slots* __restrict__ totals,
                                                        uint64_t bound, Slots* __restrict__ adds) {
   const uint64_t nch = totals->chains;
-  for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < bound; i += (uint64_t) gridDim.x * blockDim.x) {
+  RJ_GRID_STRIDE(i, bound) {
     Slots s{0, 0};
     if (i < nch) {
       const uint32_t first = row[i];
@@ -329,13 +330,33 @@ __global__ __launch_bounds__(kThreads) void k_ovm_merge_points(const int64_t* __
                                                                const Slots* __restrict__ adds, const Slots* __restrict__ adds_base,
                                                                int64_t* __restrict__ xy, uint64_t point_cap) {
   const uint64_t np = totals->points;
-  for (uint64_t j = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; j < np; j += (uint64_t) gridDim.x * blockDim.x) {
+  RJ_GRID_STRIDE(j, np) {
     const uint32_t i = point_piece[j];
     const uint64_t at = j - staged_row[i], skip = adds[i].chains ? 0 : 1;
     if (at < skip) continue;
     const uint64_t to = adds_base[i].points + at - skip;
     if (to < point_cap) *reinterpret_cast<Point16*>(xy + 2 * to) = *reinterpret_cast<const Point16*>(staged_xy + 2 * j);
   }
+}
+
+// one pass over map im: the intersection's kernel, or the operation's when there is one
+template <bool kWrite>
+void launch_emit(hipStream_t st, const OverlayOp* op, int im, const OverlayFacesMap& m, const rj_xsect* xs, uint64_t n, const int32_t* vertex_face,
+                 Slots* wave_count, const Slots* wave_base, const Stage& stage) {
+  const dim3 grid(blocks_for(64 * ((m.ne + 63) / 64), 8192));  // a lane per edge, whole waves
+  if (op)
+    hipLaunchKernelGGL(k_ovm_emit_op<kWrite>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin, (const int32_t*) m.left,
+                       (const int32_t*) m.right, m.ne, (const Rec48*) xs, n, vertex_face, wave_count, wave_base, stage, op->how, op->by);
+  else
+    hipLaunchKernelGGL(k_ovm_emit<kWrite>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin, (const int32_t*) m.left,
+                       (const int32_t*) m.right, m.ne, (const Rec48*) xs, n, vertex_face, wave_count, wave_base, stage);
+}
+// (prev_kept: null unless drop)
+void launch_join(hipStream_t st, bool drop, const uint64_t* keys, const uint32_t* row, const uint32_t* origin, const int64_t* xy,
+                 const uint32_t* prev_kept, const Slots* totals, uint64_t bound, Slots* adds) {
+  const dim3 grid(blocks_for(bound, 4096));
+  if (drop) hipLaunchKernelGGL(k_ovm_join<true>, grid, dim3(kThreads), 0, st, keys, row, origin, xy, prev_kept, totals, bound, adds);
+  else hipLaunchKernelGGL(k_ovm_join<false>, grid, dim3(kThreads), 0, st, keys, row, origin, xy, prev_kept, totals, bound, adds);
 }
 
 // rj_upload_map_dev: what rj_upload_map checks in host loops, and edge_begin[c] = row_index[c] - c.  *status = the
@@ -363,7 +384,7 @@ hipError_t map_check_device(hipStream_t st, const int64_t* xy, uint64_t np, cons
   hipError_t e = hipMemsetAsync(status_dev, 0, 4, st);
   if (e != hipSuccess) return e;
   const uint64_t work = 2 * np > nc + 1 ? 2 * np : nc + 1;
-  hipLaunchKernelGGL(k_map_check, dim3(grid_for(work, 2048)), dim3(kThreads), 0, st, xy, np, row_index, nc, edge_begin, status_dev);
+  hipLaunchKernelGGL(k_map_check, dim3(blocks_for(work, 2048)), dim3(kThreads), 0, st, xy, np, row_index, nc, edge_begin, status_dev);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = hipMemcpyAsync(status, status_dev, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
   return hipStreamSynchronize(st);
@@ -376,27 +397,25 @@ hipError_t overlay_map_device(hipStream_t st, const OverlayFacesMap maps[2], con
   const uint64_t piece_bound = max_pieces(maps[0].nc, n) + max_pieces(maps[1].nc, n);
   const uint64_t point_bound = max_points(np[0], n) + max_points(np[1], n);
   const uint64_t nkeys = 2 * piece_bound;
-  size_t sort_bytes = 0, uniq_bytes = 0, scan_bytes = 0, scan2_bytes = 0;
-  hipError_t e = rocprim::radix_sort_keys(nullptr, sort_bytes, (const uint64_t*) nullptr, (uint64_t*) nullptr, (size_t) nkeys, 0, 64, st);
-  if (e != hipSuccess) return e;
-  e = rocprim::unique(nullptr, uniq_bytes, (const uint64_t*) nullptr, (uint64_t*) nullptr, (uint64_t*) nullptr, (size_t) nkeys,
-                      rocprim::equal_to<uint64_t>(), st);
-  if (e != hipSuccess) return e;
-  e = rocprim::exclusive_scan(nullptr, scan_bytes, (const Slots*) nullptr, (Slots*) nullptr, Slots{0, 0}, (size_t) (nwaves + 1), SlotsSum(), st);
-  if (e != hipSuccess) return e;
-  e = rocprim::exclusive_scan(nullptr, scan2_bytes, (const Slots*) nullptr, (Slots*) nullptr, Slots{0, 0}, (size_t) (piece_bound + 1), SlotsSum(),
-                              st);
-  if (e != hipSuccess) return e;
-  size_t temp_bytes = sort_bytes > uniq_bytes ? sort_bytes : uniq_bytes;
-  if (scan_bytes > temp_bytes) temp_bytes = scan_bytes;
-  if (scan2_bytes > temp_bytes) temp_bytes = scan2_bytes;
-  if (merge && drop) {
-    size_t scan3_bytes = 0;
-    e = rocprim::exclusive_scan(nullptr, scan3_bytes, KeptIndexIt(rocprim::counting_iterator<uint32_t>(0), KeptIndex{nullptr, nullptr}),
-                                (uint32_t*) nullptr, 0u, (size_t) (piece_bound + 1), rocprim::maximum<uint32_t>(), st);
-    if (e != hipSuccess) return e;
-    if (scan3_bytes > temp_bytes) temp_bytes = scan3_bytes;
-  }
+  TempSize temp_size;
+  temp_size([&](size_t& b) { return rocprim::radix_sort_keys(nullptr, b, (const uint64_t*) nullptr, (uint64_t*) nullptr, (size_t) nkeys, 0, 64, st); });
+  temp_size([&](size_t& b) {
+    return rocprim::unique(nullptr, b, (const uint64_t*) nullptr, (uint64_t*) nullptr, (uint64_t*) nullptr, (size_t) nkeys,
+                           rocprim::equal_to<uint64_t>(), st);
+  });
+  temp_size([&](size_t& b) {
+    return rocprim::exclusive_scan(nullptr, b, (const Slots*) nullptr, (Slots*) nullptr, Slots{0, 0}, (size_t) (nwaves + 1), SlotsSum(), st);
+  });
+  temp_size([&](size_t& b) {
+    return rocprim::exclusive_scan(nullptr, b, (const Slots*) nullptr, (Slots*) nullptr, Slots{0, 0}, (size_t) (piece_bound + 1), SlotsSum(), st);
+  });
+  if (merge && drop)
+    temp_size([&](size_t& b) {
+      return rocprim::exclusive_scan(nullptr, b, KeptIndexIt(rocprim::counting_iterator<uint32_t>(0), KeptIndex{nullptr, nullptr}),
+                                     (uint32_t*) nullptr, 0u, (size_t) (piece_bound + 1), rocprim::maximum<uint32_t>(), st);
+    });
+  if (temp_size.error != hipSuccess) return temp_size.error;
+  const size_t temp_bytes = temp_size.bytes;
   const bool staged = drop || merge;
   Slots *wcount, *wbase, *totals, *kept = nullptr, *kept_base = nullptr;
   uint64_t *keys, *sorted, *ukeys, *nu, *counts_dev;
@@ -426,13 +445,8 @@ hipError_t overlay_map_device(hipStream_t st, const OverlayFacesMap maps[2], con
     if (merge && drop) prev_kept = A.take<uint32_t>(piece_bound + 1);
   };
   carve();
-  const size_t need = A.used;
-  if (*scratch_bytes < need) {
-    (void) hipFree(*scratch);
-    *scratch = nullptr; *scratch_bytes = 0;
-    if ((e = hipMalloc((void**) scratch, need)) != hipSuccess) return e;
-    *scratch_bytes = need;
-  }
+  hipError_t e = grow_block(scratch, scratch_bytes, A.used);
+  if (e != hipSuccess) return e;
   A.base = *scratch;
   carve();
   Stage stage;
@@ -444,23 +458,8 @@ hipError_t overlay_map_device(hipStream_t st, const OverlayFacesMap maps[2], con
     for (int im = 0; im < 2; im++) {
       const OverlayFacesMap& m = maps[im];
       if (m.ne) {
-        const dim3 grid(grid_for(64 * waves[im], 8192));
-        if (op && pass == 0)
-          hipLaunchKernelGGL(k_ovm_emit_op<false>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin,
-                             (const int32_t*) m.left, (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im],
-                             wcount + at, (const Slots*) nullptr, stage, op->how, op->by);
-        else if (op)
-          hipLaunchKernelGGL(k_ovm_emit_op<true>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin,
-                             (const int32_t*) m.left, (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im],
-                             (Slots*) nullptr, (const Slots*) (wbase + at), stage, op->how, op->by);
-        else if (pass == 0)
-          hipLaunchKernelGGL(k_ovm_emit<false>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin, (const int32_t*) m.left,
-                             (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im], wcount + at,
-                             (const Slots*) nullptr, stage);
-        else
-          hipLaunchKernelGGL(k_ovm_emit<true>, grid, dim3(kThreads), 0, st, im, m.pts, m.edge_chain, m.edge_begin, (const int32_t*) m.left,
-                             (const int32_t*) m.right, m.ne, (const Rec48*) xsects[im], n, vertex_face[im], (Slots*) nullptr,
-                             (const Slots*) (wbase + at), stage);
+        if (pass == 0) launch_emit<false>(st, op, im, m, xsects[im], n, vertex_face[im], wcount + at, nullptr, stage);
+        else launch_emit<true>(st, op, im, m, xsects[im], n, vertex_face[im], nullptr, wbase + at, stage);
         if ((e = hipGetLastError()) != hipSuccess) return e;
       }
       at += waves[im];
@@ -487,43 +486,35 @@ hipError_t overlay_map_device(hipStream_t st, const OverlayFacesMap maps[2], con
                                   (size_t) piece_bound, rocprim::maximum<uint32_t>(), st);
       if (e != hipSuccess) return e;
     }
-    const dim3 grid(grid_for(piece_bound, 4096));
-    if (drop)
-      hipLaunchKernelGGL(k_ovm_join<true>, grid, dim3(kThreads), 0, st, (const uint64_t*) keys, (const uint32_t*) staged_row,
-                         (const uint32_t*) staged_origin, (const int64_t*) staged_xy, (const uint32_t*) prev_kept, (const Slots*) totals,
-                         piece_bound, kept);
-    else
-      hipLaunchKernelGGL(k_ovm_join<false>, grid, dim3(kThreads), 0, st, (const uint64_t*) keys, (const uint32_t*) staged_row,
-                         (const uint32_t*) staged_origin, (const int64_t*) staged_xy, (const uint32_t*) nullptr, (const Slots*) totals,
-                         piece_bound, kept);
+    launch_join(st, drop, keys, staged_row, staged_origin, staged_xy, prev_kept, totals, piece_bound, kept);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (piece_bound) {
       tb = temp_bytes;
       if ((e = rocprim::exclusive_scan(temp, tb, kept, kept_base, Slots{0, 0}, (size_t) piece_bound, SlotsSum(), st)) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_ovm_merge_points, dim3(grid_for(point_bound, 8192)), dim3(kThreads), 0, st, (const int64_t*) staged_xy,
+    hipLaunchKernelGGL(k_ovm_merge_points, dim3(blocks_for(point_bound, 8192)), dim3(kThreads), 0, st, (const int64_t*) staged_xy,
                        (const uint32_t*) staged_row, (const uint32_t*) point_piece, (const Slots*) totals, (const Slots*) kept,
                        (const Slots*) kept_base, o.xy, o.point_cap);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ovm_merge_label, dim3(grid_for(piece_bound > nkeys ? piece_bound : nkeys, 4096)), dim3(kThreads), 0, st,
+    hipLaunchKernelGGL(k_ovm_merge_label, dim3(blocks_for(piece_bound > nkeys ? piece_bound : nkeys, 4096)), dim3(kThreads), 0, st,
                        (const uint64_t*) keys, (const uint64_t*) ukeys, (const uint64_t*) nu, (const Slots*) totals,
                        (const uint32_t*) staged_origin, (const Slots*) kept, (const Slots*) kept_base, o, counts_dev);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   } else if (drop) {
-    hipLaunchKernelGGL(k_ovm_keep, dim3(grid_for(piece_bound, 4096)), dim3(kThreads), 0, st, (const uint32_t*) staged_row,
+    hipLaunchKernelGGL(k_ovm_keep, dim3(blocks_for(piece_bound, 4096)), dim3(kThreads), 0, st, (const uint32_t*) staged_row,
                        (const Slots*) totals, piece_bound, kept);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (piece_bound) {
       tb = temp_bytes;
       if ((e = rocprim::exclusive_scan(temp, tb, kept, kept_base, Slots{0, 0}, (size_t) piece_bound, SlotsSum(), st)) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_ovm_compact_points, dim3(grid_for(point_bound, 8192)), dim3(kThreads), 0, st, (const int64_t*) staged_xy,
+    hipLaunchKernelGGL(k_ovm_compact_points, dim3(blocks_for(point_bound, 8192)), dim3(kThreads), 0, st, (const int64_t*) staged_xy,
                        (const uint32_t*) staged_row, (const uint32_t*) point_piece, (const Slots*) totals, (const Slots*) kept,
                        (const Slots*) kept_base, o.xy, o.point_cap);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (!merge) {
-    hipLaunchKernelGGL(k_ovm_label, dim3(grid_for(piece_bound > nkeys ? piece_bound : nkeys, 4096)), dim3(kThreads), 0, st,
+    hipLaunchKernelGGL(k_ovm_label, dim3(blocks_for(piece_bound > nkeys ? piece_bound : nkeys, 4096)), dim3(kThreads), 0, st,
                        (const uint64_t*) keys, (const uint64_t*) ukeys, (const uint64_t*) nu, (const Slots*) totals,
                        (const uint32_t*) staged_row, (const uint32_t*) staged_origin, (const Slots*) kept, (const Slots*) kept_base, o,
                        counts_dev);

@@ -11,6 +11,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/functional.hpp>
 
+#include "rj_pipeline.h"
 #include "rj_rings.h"
 
 namespace rj {
@@ -19,14 +20,7 @@ using namespace rings;
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kGroup = 8;  // lanes per half-chain in the placement kernel (the chains of an overlay's output map are short)
-inline int blocks_for(uint64_t n, int cap_blocks = 4096) {
-  uint64_t b = (n + kThreads - 1) / kThreads;
-  return (int) (b < 1 ? 1 : (b > (uint64_t) cap_blocks ? (uint64_t) cap_blocks : b));
-}
-#define RJ_GRID_STRIDE(i, n) \
-  for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < (n); i += (uint64_t) gridDim.x * blockDim.x)
 
 struct IncBefore {
   const Inc* inc;
@@ -38,30 +32,6 @@ struct SlotsSum {
 struct U128Sum {
   __host__ __device__ U128 operator()(const U128& a, const U128& b) const { return add(a, b); }
 };
-
-struct Carve {  // one allocation, carved: sizes first (base null), then the pointers
-  char* base = nullptr;
-  size_t used = 0;
-  template <typename T>
-  T* take(uint64_t count) {
-    used = (used + 255) & ~(size_t) 255;
-    T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
-    used += count * sizeof(T);
-    return p;
-  }
-};
-
-// the sum of `mine` over the block, in thread 0 (one atomic per block behind it)
-__device__ __forceinline__ uint32_t block_sum(uint32_t mine) {
-  __shared__ uint32_t part[kThreads / 64];
-  for (int d = 32; d >= 1; d >>= 1) mine += __shfl_down(mine, d, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  uint32_t sum = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kThreads / 64; w++) sum += part[w];
-  return sum;
-}
 
 __global__ __launch_bounds__(kThreads) void k_rg_check(const int64_t* __restrict__ xy, uint64_t np, const uint32_t* __restrict__ row, uint64_t nc,
                                                        Meta* meta) {
@@ -202,20 +172,22 @@ hipError_t map_rings_device(hipStream_t st, const int64_t* xy, uint64_t np, cons
   const uint64_t n1 = (uint64_t) ni + 1;
   int rounds = 1;  // rings of up to 2^(rounds - 1) half-chains
   while ((1ull << (rounds - 1)) < ni && rounds < kMaxRounds) rounds++;
-  size_t msort_bytes = 0, rsort_bytes = 0, scan32_bytes = 0, scan_slots_bytes = 0, scan128_bytes = 0;
-  hipError_t e = rocprim::merge_sort(nullptr, msort_bytes, (const uint32_t*) nullptr, (uint32_t*) nullptr, (size_t) ni, IncBefore{nullptr}, st);
-  if (e != hipSuccess) return e;
-  e = rocprim::radix_sort_keys(nullptr, rsort_bytes, (const uint64_t*) nullptr, (uint64_t*) nullptr, (size_t) ni, 0, 64, st);
-  if (e != hipSuccess) return e;
-  e = rocprim::inclusive_scan(nullptr, scan32_bytes, (const uint32_t*) nullptr, (uint32_t*) nullptr, (size_t) ni, rocprim::maximum<uint32_t>(), st);
-  if (e != hipSuccess) return e;
-  e = rocprim::exclusive_scan(nullptr, scan_slots_bytes, (const Slots*) nullptr, (Slots*) nullptr, Slots{0, 0}, (size_t) n1, SlotsSum(), st);
-  if (e != hipSuccess) return e;
-  e = rocprim::exclusive_scan(nullptr, scan128_bytes, (const U128*) nullptr, (U128*) nullptr, U128{0, 0}, (size_t) n1, U128Sum(), st);
-  if (e != hipSuccess) return e;
-  size_t temp_bytes = msort_bytes;
-  for (size_t b : {rsort_bytes, scan32_bytes, scan_slots_bytes, scan128_bytes})
-    if (b > temp_bytes) temp_bytes = b;
+  TempSize temp_size;
+  temp_size([&](size_t& b) {
+    return rocprim::merge_sort(nullptr, b, (const uint32_t*) nullptr, (uint32_t*) nullptr, (size_t) ni, IncBefore{nullptr}, st);
+  });
+  temp_size([&](size_t& b) { return rocprim::radix_sort_keys(nullptr, b, (const uint64_t*) nullptr, (uint64_t*) nullptr, (size_t) ni, 0, 64, st); });
+  temp_size([&](size_t& b) {
+    return rocprim::inclusive_scan(nullptr, b, (const uint32_t*) nullptr, (uint32_t*) nullptr, (size_t) ni, rocprim::maximum<uint32_t>(), st);
+  });
+  temp_size([&](size_t& b) {
+    return rocprim::exclusive_scan(nullptr, b, (const Slots*) nullptr, (Slots*) nullptr, Slots{0, 0}, (size_t) n1, SlotsSum(), st);
+  });
+  temp_size([&](size_t& b) {
+    return rocprim::exclusive_scan(nullptr, b, (const U128*) nullptr, (U128*) nullptr, U128{0, 0}, (size_t) n1, U128Sum(), st);
+  });
+  if (temp_size.error != hipSuccess) return temp_size.error;
+  const size_t temp_bytes = temp_size.bytes;
   // ---- scratch: one allocation, carved (sizes first, then the pointers), freed at the end ----------------------
   Meta* meta;
   Inc* inc;
@@ -242,14 +214,15 @@ hipError_t map_rings_device(hipStream_t st, const int64_t* xy, uint64_t np, cons
   };
   carve();
   char* scratch = nullptr;
-  if ((e = hipMalloc((void**) &scratch, A.used)) != hipSuccess) return e;
+  hipError_t e = hipMalloc((void**) &scratch, A.used);
+  if (e != hipSuccess) return e;
   A.base = scratch;
   carve();
   // the five junction arrays are dead once next[] is known: the ring keys and their sorted form live there later
   uint32_t *iota = junction, *sv = junction + ni, *pos = junction + 2 * (uint64_t) ni, *head = junction + 3 * (uint64_t) ni,
            *begin = junction + 4 * (uint64_t) ni, *last_of = head;  // (head[] is dead behind its scan)
   uint64_t *keys = reinterpret_cast<uint64_t*>(junction), *skeys = keys + ni;
-  const int B = blocks_for(ni), Br = blocks_for(ni, 2048);
+  const int B = blocks_for(ni, 4096), Br = blocks_for(ni, 2048);
   do {
     if ((e = hipMemsetAsync(meta, 0, sizeof(Meta), st)) != hipSuccess) break;
     hipLaunchKernelGGL(k_rg_check, dim3(blocks_for(2 * np > nc64 + 1 ? 2 * np : nc64 + 1, 2048)), dim3(kThreads), 0, st, xy, np, row, nc64, meta);

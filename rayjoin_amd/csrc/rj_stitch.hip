@@ -8,6 +8,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "rj_kernels.h"
+#include "rj_pipeline.h"
 #include "rj_stitch.h"
 
 namespace rj {
@@ -15,14 +16,6 @@ namespace rj {
 using namespace stitch;
 
 namespace {
-
-constexpr int kThreads = 256;
-inline int blocks_for(uint64_t n) {
-  uint64_t b = (n + kThreads - 1) / kThreads;
-  return (int) (b < 1 ? 1 : (b > 16384 ? 16384 : b));
-}
-#define RJ_GRID_STRIDE(i, n) \
-  for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < (n); i += (uint64_t) gridDim.x * blockDim.x)
 
 __global__ __launch_bounds__(kThreads) void k_st_end_keys(uint32_t ni, const int64_t* __restrict__ pts, const uint32_t* __restrict__ eb,
                                                           uint64_t* __restrict__ kx, uint64_t* __restrict__ ky, Dir* __restrict__ dir,
@@ -32,15 +25,8 @@ __global__ __launch_bounds__(kThreads) void k_st_end_keys(uint32_t ni, const int
     rings += end_keys((uint32_t) i, pts, eb, kx, ky, dir) ? 1u : 0u;
     iota[i] = (uint32_t) i;
   }
-  __shared__ uint32_t part[kThreads / 64];
-  for (int d = 32; d >= 1; d >>= 1) rings += __shfl_down(rings, d, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = rings;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t sum = 0;
-    for (int w = 0; w < kThreads / 64; w++) sum += part[w];
-    if (sum) atomicAdd(&meta->closed_chains, sum);
-  }
+  const uint32_t sum = block_sum(rings);
+  if (threadIdx.x == 0 && sum) atomicAdd(&meta->closed_chains, sum);
 }
 __global__ __launch_bounds__(kThreads) void k_st_gather_keys(uint32_t ni, const uint64_t* __restrict__ kx, const uint32_t* __restrict__ sv,
                                                              uint64_t* __restrict__ out) {
@@ -65,16 +51,8 @@ __global__ __launch_bounds__(kThreads) void k_st_rank_round(uint32_t ni, const N
   }
   uint32_t mine = 0;
   RJ_GRID_STRIDE(i, ni) mine += rank_round((uint32_t) i, in, out) ? 1u : 0u;
-  // one atomic per block (27 k same-address atomics, one per wave of a 1.7 M-incidence map, were 90 % of this kernel)
-  __shared__ uint32_t part[kThreads / 64];
-  for (int d = 32; d >= 1; d >>= 1) mine += __shfl_down(mine, d, 64);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t sum = 0;
-    for (int w = 0; w < kThreads / 64; w++) sum += part[w];
-    if (sum) atomicAdd(&act[r], sum);
-  }
+  const uint32_t sum = block_sum(mine);
+  if (threadIdx.x == 0 && sum) atomicAdd(&act[r], sum);
 }
 __global__ void k_st_rank_done(Meta* meta, int rounds, int second) {
   uint32_t* done = second ? &meta->done_round2 : &meta->done_round;
@@ -119,18 +97,6 @@ __global__ __launch_bounds__(kThreads) void k_st_emit(uint32_t nc, const uint32_
     chain_emit((uint32_t) s, nc, eb, cap, ch_key, ch_off, ch_total, base, slot_chain, slot_pieces, pbase, piece_begin, piece_len, run_first, meta);
 }
 
-struct Arena {
-  char* base = nullptr;
-  size_t used = 0, size = 0;
-  template <typename T>
-  T* take(uint64_t count) {
-    used = (used + 255) & ~(size_t) 255;
-    T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
-    used += count * sizeof(T);
-    return p;
-  }
-};
-
 }  // namespace
 
 // first launch of a kernel of this file = loading its code object (milliseconds): rj_create pays that, not a build
@@ -157,18 +123,21 @@ hipError_t stitch_runs_device(hipStream_t st, const int64_t* pts, const uint32_t
   int rounds = 2;
   while ((1ull << (rounds - 2)) <= nc && rounds < kMaxRounds) rounds++;
   // ---- scratch: one allocation, carved (sizes first, then the pointers) --------------------------
-  size_t sort_bytes = 0, scan64_bytes = 0, scan32_bytes = 0;
-  hipError_t e = rocprim::radix_sort_pairs(nullptr, sort_bytes, (const uint64_t*) nullptr, (uint64_t*) nullptr, (const uint32_t*) nullptr,
-                                           (uint32_t*) nullptr, (size_t) ni, 0, kKeyBits, st);
-  if (e != hipSuccess) return e;
-  e = rocprim::exclusive_scan(nullptr, scan64_bytes, (const uint64_t*) nullptr, (uint64_t*) nullptr, (uint64_t) 0, (size_t) 2 * ni,
-                              rocprim::plus<uint64_t>(), st);
-  if (e != hipSuccess) return e;
-  e = rocprim::exclusive_scan(nullptr, scan32_bytes, (const uint32_t*) nullptr, (uint32_t*) nullptr, 0u, (size_t) nc, rocprim::plus<uint32_t>(), st);
-  if (e != hipSuccess) return e;
-  size_t temp_bytes = sort_bytes > scan64_bytes ? sort_bytes : scan64_bytes;
-  if (scan32_bytes > temp_bytes) temp_bytes = scan32_bytes;
-  Arena A;
+  TempSize temp_size;
+  temp_size([&](size_t& b) {
+    return rocprim::radix_sort_pairs(nullptr, b, (const uint64_t*) nullptr, (uint64_t*) nullptr, (const uint32_t*) nullptr, (uint32_t*) nullptr,
+                                     (size_t) ni, 0, kKeyBits, st);
+  });
+  temp_size([&](size_t& b) {
+    return rocprim::exclusive_scan(nullptr, b, (const uint64_t*) nullptr, (uint64_t*) nullptr, (uint64_t) 0, (size_t) 2 * ni,
+                                   rocprim::plus<uint64_t>(), st);
+  });
+  temp_size([&](size_t& b) {
+    return rocprim::exclusive_scan(nullptr, b, (const uint32_t*) nullptr, (uint32_t*) nullptr, 0u, (size_t) nc, rocprim::plus<uint32_t>(), st);
+  });
+  if (temp_size.error != hipSuccess) return temp_size.error;
+  const size_t temp_bytes = temp_size.bytes;
+  Carve A;
   uint64_t *kx, *ky, *ska, *skb, *head, *base;
   uint32_t *va, *vb, *partner, *ch_key, *ch_off, *ch_total, *ch_rank, *slot_chain, *slot_pieces, *pbase;
   uint8_t *ch_back, *in_loop;
@@ -193,27 +162,22 @@ hipError_t stitch_runs_device(hipStream_t st, const int64_t* pts, const uint32_t
     temp = A.take<char>(temp_bytes);
   };
   carve();
-  A.size = A.used;
   // (the caller's grow-only block: freeing a block of its own cost every first build of a map 0.25 ms -- hipFree waits
   //  for the device and unmaps -- a sixth of the headline map's)
-  if (*scratch_bytes < A.size) {
-    (void) hipFree(*scratch);
-    *scratch = nullptr; *scratch_bytes = 0;
-    if ((e = hipMalloc((void**) scratch, A.size)) != hipSuccess) return e;
-    *scratch_bytes = A.size;
-  }
+  hipError_t e = grow_block(scratch, scratch_bytes, A.used);
+  if (e != hipSuccess) return e;
   A.base = *scratch;
   carve();
   Link* links = nullptr;
   Meta hm;
-  const int B = blocks_for(ni), Bc = blocks_for(nc);
-  const int Br = B > 2048 ? 2048 : B;  // the ranking rounds: one counter update per block
+  const int B = blocks_for(ni, 16384), Bc = blocks_for(nc, 16384);
+  const int Br = blocks_for(ni, 2048);  // the ranking rounds and the end keys: one counter update per block
   do {
     if ((e = hipMemsetAsync(meta, 0, sizeof(Meta), st)) != hipSuccess) break;
     if ((e = hipMemsetAsync(partner, 0xFF, 4 * (size_t) ni, st)) != hipSuccess) break;
     if ((e = hipMemsetAsync(in_loop, 0, nc, st)) != hipSuccess) break;
     // 1. end points -> keys; 2. sort by y, then stably by x; pair every junction
-    hipLaunchKernelGGL(k_st_end_keys, dim3(B > 2048 ? 2048 : B), dim3(kThreads), 0, st, ni, pts, eb, kx, ky, dir, va, meta);
+    hipLaunchKernelGGL(k_st_end_keys, dim3(Br), dim3(kThreads), 0, st, ni, pts, eb, kx, ky, dir, va, meta);
     // (a map of closed rings has nothing to pair -- a ring's ends never take part -- and the two sorts of its 2 nc chain
     //  ends were half of this stage on the lake-shaped maps: one more look at the count decides)
     if ((e = hipMemcpyAsync(&hm, meta, sizeof(Meta), hipMemcpyDeviceToHost, st)) != hipSuccess) break;

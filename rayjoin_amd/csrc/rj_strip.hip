@@ -17,18 +17,11 @@
 #include <rocprim/iterator/reverse_iterator.hpp>
 
 #include "rj_kernels.h"
+#include "rj_pipeline.h"
 
 namespace rj {
 
 namespace {
-
-#define RJ_GRID_STRIDE(i, n) \
-  for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < (n); i += (uint64_t) gridDim.x * blockDim.x)
-
-inline int blocks_for(uint64_t n, int per_block = 256, int cap = 16384) {
-  uint64_t b = (n + per_block - 1) / per_block;
-  return (int) (b < 1 ? 1 : (b > (uint64_t) cap ? cap : b));
-}
 
 // how many strips the box of sorted slot i touches (0: a padding slot); flag[0] = 1 when one is too wide to register
 __global__ __launch_bounds__(256) void k_strip_count(const QBox* __restrict__ box0, const uint32_t* __restrict__ seid, uint64_t n0p,
@@ -439,7 +432,7 @@ hipError_t warm_strip_kernels(hipStream_t st) {
 hipError_t launch_strip_width(hipStream_t st, const QBox* box0, const uint32_t* seid, uint64_t n0p, unsigned long long* out2) {
   hipError_t e = hipMemsetAsync(out2, 0, 16, st);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_strip_width, dim3(blocks_for(n0p / 64 + 1, 256, 512)), dim3(256), 0, st, box0, seid, n0p, out2);
+  hipLaunchKernelGGL(k_strip_width, dim3(blocks_for(n0p / 64 + 1, 512)), dim3(256), 0, st, box0, seid, n0p, out2);
   return hipGetLastError();
 }
 hipError_t launch_strip_count(hipStream_t st, const QBox* box0, const uint32_t* seid, uint64_t n0p, int shift, uint32_t* cnt, uint32_t* offs,
@@ -448,7 +441,7 @@ hipError_t launch_strip_count(hipStream_t st, const QBox* box0, const uint32_t* 
                                             rocprim::plus<uint32_t>(), st);
   hipError_t e = hipMemsetAsync(cnt + n0p, 0, 4, st);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_strip_count, dim3(blocks_for(n0p)), dim3(256), 0, st, box0, seid, n0p, shift, cnt, flag);
+  hipLaunchKernelGGL(k_strip_count, dim3(blocks_for(n0p, 16384)), dim3(256), 0, st, box0, seid, n0p, shift, cnt, flag);
   return rocprim::exclusive_scan(temp, temp_bytes, cnt, offs, 0u, (size_t) n0p + 1, rocprim::plus<uint32_t>(), st);  // offs[n0p] = the total
 }
 // pass 2: the entries, sorted by (strip, y0), with their boxes, their {slot, edge id, face id} and the height-bucket
@@ -472,18 +465,18 @@ hipError_t launch_strip_fill(hipStream_t st, const QBox* box0, const uint32_t* s
   }
   hipError_t e = hipMemsetAsync(tall, 0, (size_t) strips * 4, st);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_strip_emit, dim3(blocks_for(n0p)), dim3(256), 0, st, box0, cnt, offs, n0p, shift, key_tmp, slot_tmp);
+  hipLaunchKernelGGL(k_strip_emit, dim3(blocks_for(n0p, 16384)), dim3(256), 0, st, box0, cnt, offs, n0p, shift, key_tmp, slot_tmp);
   if ((e = rocprim::radix_sort_pairs(temp, temp_bytes, key_tmp, key, slot_tmp, eslot, (size_t) entries, 0, bits, st)) != hipSuccess) return e;
   const size_t nt = ((size_t) strips << kStripYBits) + 1;
   if ((e = hipMemsetAsync(ytab, 0xFF, nt * 4, st)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_strip_finish, dim3(blocks_for(entries)), dim3(256), 0, st, key, eslot, entries, box0, seid, sface, ebox, einfo, ytab, strips, tall, sky, shift);
+  hipLaunchKernelGGL(k_strip_finish, dim3(blocks_for(entries, 16384)), dim3(256), 0, st, key, eslot, entries, box0, seid, sface, ebox, einfo, ytab, strips, tall, sky, shift);
   // suffix minimum, in place (the sort's temporary storage is free again and larger than a scan's)
   size_t need = 0;
   auto rb = rocprim::make_reverse_iterator(ytab + nt);
   if ((e = rocprim::inclusive_scan(nullptr, need, rb, rb, nt, rocprim::minimum<uint32_t>(), st)) != hipSuccess) return e;
   if (need > temp_bytes) return hipErrorInvalidValue;
   if ((e = rocprim::inclusive_scan(temp, need, rb, rb, nt, rocprim::minimum<uint32_t>(), st)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_strip_ends, dim3(blocks_for(strips)), dim3(256), 0, st, tall, ytab, strips, tall_end);
+  hipLaunchKernelGGL(k_strip_ends, dim3(blocks_for(strips, 16384)), dim3(256), 0, st, tall, ytab, strips, tall_end);
   return hipGetLastError();
 }
 
@@ -496,7 +489,7 @@ hipError_t launch_pip_strip(hipStream_t st, const PipArgs& a, int max_blocks, in
   const uint64_t resident_waves = (uint64_t) cus * 32;
   const int pts = a.stats || a.n >= resident_waves * 2 * 128 ? 2 : 1;  // (the instrumented build is the two-point one)
   const uint64_t ngroups = (a.n + (uint64_t) pts * 64 - 1) / ((uint64_t) pts * 64);
-  int grid = blocks_for(ngroups, 4, cus * 8);
+  int grid = blocks_for(64 * ngroups, cus * 8);  // (a wave per group)
   if (grid > max_blocks) grid = max_blocks;
   strip_note_grid = grid; strip_note_pts = pts;
   if (a.stats) { hipLaunchKernelGGL((k_pip_strip<2, true>), dim3(grid), dim3(256), 0, st, a); return hipGetLastError(); }  // (the instrumented build: "stats" 1 + "pip_walk" 2)
