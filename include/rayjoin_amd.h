@@ -425,6 +425,51 @@ int rj_map_rings(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t
                  rj_ring* rings_dev, uint32_t* ring_first_dev, uint32_t* ring_half_dev, uint32_t* ring_row_dev,
                  int64_t* ring_xy_dev, rj_rings_counts* counts);
 
+/* ---- polygons ---------------------------------------------------------------------------- */
+#define RJ_POLY_NONE 0xFFFFFFFFu /* parent_dev: a ring of face 0, or a hole without a shell round it (an orphan) */
+
+typedef struct {
+  int32_t face;
+  uint32_t shell;   /* the ring index of its outer ring */
+  uint32_t n_holes;
+  uint32_t _pad;
+  uint64_t area2_lo; /* twice the area: the shell's area2 plus its holes', a two's-complement int128 like rj_ring's */
+  int64_t area2_hi;
+} rj_polygon; /* 32 bytes */
+
+typedef struct {
+  uint64_t n_polygons, n_members, n_holes, n_orphans, n_face0;
+} rj_polygons_counts;
+
+/* extends: the polygons of the rings that rj_map_rings gave (with points; rings_dev, ring_row_dev, ring_xy_dev as it
+ * wrote them, n_rings <= 2^32 - 2): every hole ring assigned to the outer ring it lies in, on the device.  The
+ * definition, in full in rayjoin_amd/csrc/rj_polygons.h:
+ *   a ring of face 0 belongs to no polygon (n_face0); a ring of another face is a shell when area2 > 0, else a hole (a
+ *   ring of area 0 is a dangling tree inside its face).  The top of a ring is its largest (y, x).  A ceiling edge is a
+ *   ring edge u -> v with v.x < u.x (the ring's face lies below it).  above(H), for a hole H of face f with top p: among
+ *   the ceiling edges of the rings of face f with v.x <= p.x < u.x whose height at p.x is strictly above p.y, the ring of
+ *   the edge with the smallest height at p.x, then the smallest slope, then the smallest point slot of u (all exact,
+ *   int128).  parent(H): follow above until a shell; a walk that ends at a hole with nothing above it makes H an orphan
+ *   (n_orphans; none on a consistently labelled planar map).  One polygon per shell, ascending by shell index (the
+ *   polygons of a face are contiguous); its members: the shell, then its holes by ascending ring index; area2 = the sum
+ *   of its members' area2.
+ * Output, all caller-owned device memory: parent_dev[n_rings] (may be NULL): the shell's ring index for a hole, its own
+ * index for a shell, RJ_POLY_NONE for a ring of face 0 and for an orphan -- always written in full;
+ * polygons_dev[polygon_capacity]; poly_first_dev[polygon_capacity + 1], the CSR of the polygons into
+ * poly_ring_dev[member_capacity] (ring indices).  n_members = n_polygons + n_holes; n_holes counts the holes that have
+ * a parent.  RJ_E_OVERFLOW when a count exceeds its capacity: *counts holds the true counts and nothing beyond any
+ * capacity is written; all capacities 0 (arrays may be NULL) is the sizing call.  n_rings == 0 is valid.  flags must be
+ * 0.  RJ_E_INVALID for a ring_row that does not start at 0, decreases or does not end at n_points, a coordinate outside
+ * [-2^46, 2^46), rings that do not ascend by ((uint32) face << 32) | leader, a non-zero flags; RJ_E_INTERNAL when the
+ * round budget runs out (33 jumping steps: cannot happen).  Runs on the handle's stream with one host sync, at the
+ * end, to read the counts; scratch (72 bytes per point and 96 per ring plus the sorts' temporary storage) is
+ * allocated per call and freed; no state of the handle changes. */
+int rj_rings_polygons(rj_handle h, const rj_ring* rings_dev, uint64_t n_rings, const uint32_t* ring_row_dev,
+                      const int64_t* ring_xy_dev, uint64_t n_points, uint32_t flags,
+                      uint64_t polygon_capacity, uint64_t member_capacity,
+                      uint32_t* parent_dev, rj_polygon* polygons_dev, uint32_t* poly_first_dev,
+                      uint32_t* poly_ring_dev, rj_polygons_counts* counts);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

@@ -36,6 +36,10 @@ FACE_DTYPE = np.dtype([("face", "<i4", (2,)), ("area2_lo", "<u8"), ("area2_hi", 
 # rj_ring: a closed boundary of a chain map -- its face, RJ_RING_MIXED, its smallest half-chain, twice its signed area
 RING_DTYPE = np.dtype([("face", "<i4"), ("flags", "<u4"), ("leader", "<u4"), ("_pad", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
 RINGS_COUNTS = ("n_rings", "n_halves", "n_points", "n_mixed", "n_skipped")
+RJ_POLY_NONE = 0xFFFFFFFF  # rj_rings_polygons' parent of a ring of face 0 and of an orphan
+# rj_polygon: one outer ring with its holes -- its face, the shell's ring index, its holes, twice its area
+POLYGON_DTYPE = np.dtype([("face", "<i4"), ("shell", "<u4"), ("n_holes", "<u4"), ("_pad", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
+POLYGONS_COUNTS = ("n_polygons", "n_members", "n_holes", "n_orphans", "n_face0")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
 _vp, _u64, _i64, _int = C.c_void_p, C.c_uint64, C.c_int64, C.c_int
@@ -84,6 +88,7 @@ SYMBOLS = {
     "rj_overlay_map_op": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32,
                                  C.c_uint32]),
     "rj_map_rings": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rj_rings_polygons": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -160,6 +165,14 @@ class MapOverflow(RayJoinError):
 
 class RingsOverflow(RayJoinError):
     """RJ_E_OVERFLOW of rj_map_rings: counts = dict(n_rings, n_halves, n_points, n_mixed, n_skipped), the true counts"""
+
+    def __init__(self, msg, counts):
+        super().__init__(RJ_E_OVERFLOW, msg)
+        self.counts = counts
+
+
+class PolygonsOverflow(RayJoinError):
+    """RJ_E_OVERFLOW of rj_rings_polygons: counts = dict(n_polygons, n_members, n_holes, n_orphans, n_face0), the true counts"""
 
     def __init__(self, msg, counts):
         super().__init__(RJ_E_OVERFLOW, msg)
@@ -496,6 +509,21 @@ class Handle:
         named = dict(zip(RINGS_COUNTS, (int(v) for v in counts)))
         if rc == RJ_E_OVERFLOW:
             raise RingsOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        self._check(rc)
+        return named
+
+    def rings_polygons(self, rings_dev, n_rings, ring_row_dev, ring_xy_dev, n_points, flags, capacities, parent_dev, polygons_dev,
+                       poly_first_dev, poly_ring_dev):
+        """rj_rings_polygons of rj_map_rings' arrays in device memory into the caller's device arrays; capacities =
+        (polygons, members); parent_dev may be None.  Returns the counts as a dict (POLYGONS_COUNTS); PolygonsOverflow
+        (with the true counts) past a capacity."""
+        counts = (_u64 * 5)()
+        pc, mc = (int(v) for v in capacities)
+        rc = self.L.rj_rings_polygons(self.h, _ptr(rings_dev), int(n_rings), _ptr(ring_row_dev), _ptr(ring_xy_dev), int(n_points), int(flags),
+                                      pc, mc, _ptr(parent_dev), _ptr(polygons_dev), _ptr(poly_first_dev), _ptr(poly_ring_dev), counts)
+        named = dict(zip(POLYGONS_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise PolygonsOverflow(self.L.rj_last_error_string(self.h).decode(), named)
         self._check(rc)
         return named
 

@@ -18,6 +18,7 @@
 #include "rj_overlay_dev.h"
 #include "rj_overlay_ops.h"
 #include "rj_pipeline.h"
+#include "rj_polygons.h"
 #include "rj_rings.h"
 
 using namespace rj;
@@ -2733,6 +2734,38 @@ int rj_map_rings(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t
     return fail(h, RJ_E_OVERFLOW, "rj_map_rings: %llu rings, %llu half-chains, %llu points; capacities %llu, %llu, %llu",
                 (unsigned long long) counts->n_rings, (unsigned long long) counts->n_halves, (unsigned long long) counts->n_points,
                 (unsigned long long) ring_capacity, (unsigned long long) half_capacity, (unsigned long long) point_capacity);
+  return RJ_OK;
+}
+
+int rj_rings_polygons(rj_handle h, const rj_ring* rings_dev, uint64_t n_rings, const uint32_t* ring_row_dev, const int64_t* ring_xy_dev,
+                      uint64_t n_points, uint32_t flags, uint64_t polygon_capacity, uint64_t member_capacity, uint32_t* parent_dev,
+                      rj_polygon* polygons_dev, uint32_t* poly_first_dev, uint32_t* poly_ring_dev, rj_polygons_counts* counts) {
+  static_assert(sizeof(rj_polygon) == 32 && sizeof(polygons::Polygon) == 32 && sizeof(rj_polygons_counts) == sizeof(polygons::Counts), "layouts");
+  static_assert(RJ_POLY_NONE == polygons::kNone, "RJ_POLY_NONE");
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_rings_polygons: counts is null");
+  memset(counts, 0, sizeof(*counts));
+  if (flags) return fail(h, RJ_E_INVALID, "rj_rings_polygons: unknown flags 0x%x", flags);
+  if (n_rings > 0xFFFFFFFEull || n_points >= (1ull << 32)) return fail(h, RJ_E_INVALID, "rj_rings_polygons: n_rings <= 2^32 - 2 and n_points < 2^32");
+  if (n_rings == 0 && n_points != 0) return fail(h, RJ_E_INVALID, "rj_rings_polygons: points without rings");
+  if ((n_rings && (!rings_dev || !ring_row_dev)) || (n_points && !ring_xy_dev)) return fail(h, RJ_E_INVALID, "rj_rings_polygons: null input array");
+  if ((polygon_capacity && (!polygons_dev || !poly_first_dev)) || (member_capacity && !poly_ring_dev))
+    return fail(h, RJ_E_INVALID, "rj_rings_polygons: null output");
+  if (int r = set_device(h)) return r;
+  const polygons::Out out{parent_dev, reinterpret_cast<polygons::Polygon*>(polygons_dev), poly_first_dev, poly_ring_dev, polygon_capacity,
+                          member_capacity};
+  polygons::Meta m;
+  RJ_HIP(h, rings_polygons_device(h->stream, reinterpret_cast<const rings::Ring*>(rings_dev), n_rings, ring_row_dev, ring_xy_dev, n_points, out, &m));
+  if (m.bad == polygons::kBadStart) return fail(h, RJ_E_INVALID, "rj_rings_polygons: ring_row must start at 0");
+  if (m.bad == polygons::kBadEnd) return fail(h, RJ_E_INVALID, "rj_rings_polygons: ring_row must end at n_points");
+  if (m.bad == polygons::kBadRow) return fail(h, RJ_E_INVALID, "rj_rings_polygons: ring_row must not decrease");
+  if (m.bad == polygons::kBadOrder) return fail(h, RJ_E_INVALID, "rj_rings_polygons: the rings must ascend by (face, leader)");
+  if (m.bad) return fail(h, RJ_E_INVALID, "rj_rings_polygons: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  if (m.unfinished) return fail(h, RJ_E_INTERNAL, "rj_rings_polygons: a hole did not reach its shell within %d jumping steps", polygons::kMaxRounds);
+  memcpy(counts, &m.counts, sizeof(*counts));
+  if (counts->n_polygons > polygon_capacity || counts->n_members > member_capacity)
+    return fail(h, RJ_E_OVERFLOW, "rj_rings_polygons: %llu polygons, %llu members; capacities %llu, %llu", (unsigned long long) counts->n_polygons,
+                (unsigned long long) counts->n_members, (unsigned long long) polygon_capacity, (unsigned long long) member_capacity);
   return RJ_OK;
 }
 

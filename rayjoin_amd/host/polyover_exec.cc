@@ -15,6 +15,10 @@
 //   either flag the two files are the intersection's (the calls without _op), byte for byte what they were.
 //   -merge (ours): -output_map with RJ_OVM_MERGE_PIECES: adjacent pieces of one source chain that have the same two
 //   faces and touch are written as one chain (what a dissolve leaves of a chain the other map cut).
+//   -polygons <path> (ours): the polygons of the result, on the device: the output map (under -how, -by, -merge), its
+//   rings without those of face 0 (rj_map_rings, RJ_RINGS_SKIP_FACE0), every hole assigned to its outer ring
+//   (rj_rings_polygons).  One line per polygon: "f0 f1 area2 POLYGON ((shell), (hole), ...)" -- (f0, f1) the polygon's row
+//   of face_pairs, area2 twice its area in scaled units^2 (exact), the points unscaled ("%.6f"), every ring closed.
 #include <iostream>
 #include <unordered_map>
 
@@ -137,39 +141,144 @@ class MapOverlayLBVH {
     }
     fclose(fp);
   }
-  // the output map on the device (rj_overlay_map): a sizing call, then the arrays; to the host for the file
-  void ComputeOutputMap() {
-    rj_handle h = ctx_.handle();
-    rj_overlay_map_counts c;
-    auto overlay_map = [&](uint64_t cc, uint64_t pc, uint64_t fc, int64_t* xy, uint32_t* row, int32_t* left, int32_t* right,
-                           int32_t* pairs) {
-      return use_op_ ? rj_overlay_map_op(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], map_flags_, cc, pc, fc, xy, row,
-                                         left, right, pairs, nullptr, &c, how_, by_)
-                     : rj_overlay_map(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], map_flags_, cc, pc, fc, xy, row, left,
-                                      right, pairs, nullptr, &c);
-    };
-    int rc = overlay_map(0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
-    if (rc != RJ_E_OVERFLOW) rj_check(h, rc, "rj_overlay_map");
+  // the output map on the device (rj_overlay_map): a sizing call, then the arrays, which stay with the caller
+  struct DeviceMap {
+    rj_overlay_map_counts c{};
     int64_t* xy = nullptr;
     uint32_t* row = nullptr;
     int32_t *left = nullptr, *right = nullptr, *pairs = nullptr;
-    rj_check(h, rj_dev_alloc(h, 16 * (c.n_points ? c.n_points : 1), (void**) &xy), "rj_dev_alloc");
-    rj_check(h, rj_dev_alloc(h, 4 * (c.n_chains + 1), (void**) &row), "rj_dev_alloc");
-    rj_check(h, rj_dev_alloc(h, 4 * (c.n_chains ? c.n_chains : 1), (void**) &left), "rj_dev_alloc");
-    rj_check(h, rj_dev_alloc(h, 4 * (c.n_chains ? c.n_chains : 1), (void**) &right), "rj_dev_alloc");
-    rj_check(h, rj_dev_alloc(h, 8 * (c.n_faces ? c.n_faces : 1), (void**) &pairs), "rj_dev_alloc");
-    rc = overlay_map(c.n_chains, c.n_points, c.n_faces, xy, row, left, right, pairs);
+  };
+  DeviceMap RunOutputMap() {
+    rj_handle h = ctx_.handle();
+    DeviceMap m;
+    auto overlay_map = [&](uint64_t cc, uint64_t pc, uint64_t fc) {
+      return use_op_ ? rj_overlay_map_op(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], map_flags_, cc, pc, fc, m.xy, m.row,
+                                         m.left, m.right, m.pairs, nullptr, &m.c, how_, by_)
+                     : rj_overlay_map(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], map_flags_, cc, pc, fc, m.xy, m.row,
+                                      m.left, m.right, m.pairs, nullptr, &m.c);
+    };
+    int rc = overlay_map(0, 0, 0);
+    if (rc != RJ_E_OVERFLOW) rj_check(h, rc, "rj_overlay_map");
+    const rj_overlay_map_counts c = m.c;
+    rj_check(h, rj_dev_alloc(h, 16 * (c.n_points ? c.n_points : 1), (void**) &m.xy), "rj_dev_alloc");
+    rj_check(h, rj_dev_alloc(h, 4 * (c.n_chains + 1), (void**) &m.row), "rj_dev_alloc");
+    rj_check(h, rj_dev_alloc(h, 4 * (c.n_chains ? c.n_chains : 1), (void**) &m.left), "rj_dev_alloc");
+    rj_check(h, rj_dev_alloc(h, 4 * (c.n_chains ? c.n_chains : 1), (void**) &m.right), "rj_dev_alloc");
+    rj_check(h, rj_dev_alloc(h, 8 * (c.n_faces ? c.n_faces : 1), (void**) &m.pairs), "rj_dev_alloc");
+    rc = overlay_map(c.n_chains, c.n_points, c.n_faces);
+    if (rc != RJ_OK) FreeMap(m);
+    rj_check(h, rc, "rj_overlay_map");
+    return m;
+  }
+  void FreeMap(DeviceMap& m) {
+    rj_handle h = ctx_.handle();
+    rj_dev_free(h, m.xy); rj_dev_free(h, m.row); rj_dev_free(h, m.left); rj_dev_free(h, m.right); rj_dev_free(h, m.pairs);
+  }
+  // ... to the host for the file
+  void ComputeOutputMap() {
+    rj_handle h = ctx_.handle();
+    DeviceMap m = RunOutputMap();
+    const rj_overlay_map_counts c = m.c;
     om_xy_.resize(2 * c.n_points);
     om_row_.resize(c.n_chains + 1);
     om_left_.resize(c.n_chains);
     om_right_.resize(c.n_chains);
-    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_xy_.data(), xy, 16 * c.n_points);
-    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_row_.data(), row, 4 * (c.n_chains + 1));
-    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_left_.data(), left, 4 * c.n_chains);
-    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_right_.data(), right, 4 * c.n_chains);
-    rj_dev_free(h, xy); rj_dev_free(h, row); rj_dev_free(h, left); rj_dev_free(h, right); rj_dev_free(h, pairs);
+    int rc = rj_memcpy_d2h(h, om_xy_.data(), m.xy, 16 * c.n_points);
+    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_row_.data(), m.row, 4 * (c.n_chains + 1));
+    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_left_.data(), m.left, 4 * c.n_chains);
+    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_right_.data(), m.right, 4 * c.n_chains);
+    FreeMap(m);
     rj_check(h, rc, "rj_overlay_map");
     std::cerr << "Output map: " << c.n_chains << " chains, " << c.n_points << " points, " << c.n_faces << " faces" << std::endl;
+  }
+  // the polygons of the output map on the device: the map, its rings without those of face 0, the holes to their outer
+  // rings (a sizing call before each); what the file needs goes to the host
+  void ComputePolygons() {
+    rj_handle h = ctx_.handle();
+    DeviceMap m = RunOutputMap();
+    rj_rings_counts rc_{};
+    rj_ring* rings = nullptr;
+    uint32_t *ring_first = nullptr, *ring_half = nullptr, *ring_row = nullptr, *poly_first = nullptr, *poly_ring = nullptr;
+    int64_t* ring_xy = nullptr;
+    rj_polygon* polygons = nullptr;
+    auto free_all = [&]() {
+      FreeMap(m);
+      rj_dev_free(h, rings); rj_dev_free(h, ring_first); rj_dev_free(h, ring_half); rj_dev_free(h, ring_row); rj_dev_free(h, ring_xy);
+      rj_dev_free(h, polygons); rj_dev_free(h, poly_first); rj_dev_free(h, poly_ring);
+    };
+    auto must = [&](int rc, const char* what) {
+      if (rc != RJ_OK) free_all();
+      rj_check(h, rc, what);
+    };
+    int rc = rj_map_rings(h, m.xy, m.c.n_points, m.row, m.left, m.right, m.c.n_chains, RJ_RINGS_SKIP_FACE0, 0, 0, 0, nullptr, nullptr, nullptr,
+                          nullptr, nullptr, &rc_);
+    if (rc != RJ_E_OVERFLOW) must(rc, "rj_map_rings");
+    must(rj_dev_alloc(h, sizeof(rj_ring) * (rc_.n_rings ? rc_.n_rings : 1), (void**) &rings), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (rc_.n_rings + 1), (void**) &ring_first), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (rc_.n_halves ? rc_.n_halves : 1), (void**) &ring_half), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (rc_.n_rings + 1), (void**) &ring_row), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 16 * (rc_.n_points ? rc_.n_points : 1), (void**) &ring_xy), "rj_dev_alloc");
+    must(rj_map_rings(h, m.xy, m.c.n_points, m.row, m.left, m.right, m.c.n_chains, RJ_RINGS_SKIP_FACE0, rc_.n_rings, rc_.n_halves, rc_.n_points,
+                      rings, ring_first, ring_half, ring_row, ring_xy, &rc_),
+         "rj_map_rings");
+    rj_polygons_counts pc{};
+    rc = rj_rings_polygons(h, rings, rc_.n_rings, ring_row, ring_xy, rc_.n_points, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, &pc);
+    if (rc != RJ_E_OVERFLOW) must(rc, "rj_rings_polygons");
+    must(rj_dev_alloc(h, sizeof(rj_polygon) * (pc.n_polygons ? pc.n_polygons : 1), (void**) &polygons), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (pc.n_polygons + 1), (void**) &poly_first), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (pc.n_members ? pc.n_members : 1), (void**) &poly_ring), "rj_dev_alloc");
+    must(rj_rings_polygons(h, rings, rc_.n_rings, ring_row, ring_xy, rc_.n_points, 0, pc.n_polygons, pc.n_members, nullptr, polygons, poly_first,
+                           poly_ring, &pc),
+         "rj_rings_polygons");
+    pg_polygons_.resize(pc.n_polygons);
+    pg_first_.resize(pc.n_polygons + 1);
+    pg_ring_.resize(pc.n_members);
+    pg_row_.resize(rc_.n_rings + 1);
+    pg_xy_.resize(2 * rc_.n_points);
+    pg_pairs_.resize(2 * m.c.n_faces);
+    must(rj_memcpy_d2h(h, pg_polygons_.data(), polygons, sizeof(rj_polygon) * pc.n_polygons), "rj_memcpy_d2h");
+    must(rj_memcpy_d2h(h, pg_first_.data(), poly_first, 4 * (pc.n_polygons + 1)), "rj_memcpy_d2h");
+    must(rj_memcpy_d2h(h, pg_ring_.data(), poly_ring, 4 * pc.n_members), "rj_memcpy_d2h");
+    must(rj_memcpy_d2h(h, pg_row_.data(), ring_row, 4 * (rc_.n_rings + 1)), "rj_memcpy_d2h");
+    must(rj_memcpy_d2h(h, pg_xy_.data(), ring_xy, 16 * rc_.n_points), "rj_memcpy_d2h");
+    must(rj_memcpy_d2h(h, pg_pairs_.data(), m.pairs, 8 * m.c.n_faces), "rj_memcpy_d2h");
+    free_all();
+    std::cerr << "Polygons: " << pc.n_polygons << " polygons, " << pc.n_holes << " holes, " << pc.n_orphans << " orphans of " << rc_.n_rings
+              << " rings" << std::endl;
+  }
+  // one line per polygon: "f0 f1 area2 POLYGON ((shell), (hole), ...)"
+  void WritePolygons(const char* path) const {
+    FILE* fp = fopen(path, "w");
+    if (!fp) throw std::runtime_error(std::string("Cannot open ") + path);
+    const Scaling& sc = ctx_.get_scaling();
+    for (size_t k = 0; k < pg_polygons_.size(); k++) {
+      const rj_polygon& g = pg_polygons_[k];
+      const bool known = g.face >= 1 && 2 * (size_t) g.face <= pg_pairs_.size();
+      unsigned __int128 a2 = ((unsigned __int128) (uint64_t) g.area2_hi << 64) | g.area2_lo;
+      const bool negative = g.area2_hi < 0;
+      if (negative) a2 = (unsigned __int128) 0 - a2;
+      char digits[48];
+      int nd = 0;
+      do {
+        digits[nd++] = (char) ('0' + (int) (a2 % 10));
+        a2 /= 10;
+      } while (a2);
+      std::string area(negative ? "-" : "");
+      while (nd) area.push_back(digits[--nd]);
+      fprintf(fp, "%d %d %s POLYGON (", known ? pg_pairs_[2 * (size_t) (g.face - 1)] : g.face, known ? pg_pairs_[2 * (size_t) (g.face - 1) + 1] : 0,
+              area.c_str());
+      for (uint32_t j = pg_first_[k]; j < pg_first_[k + 1]; j++) {
+        const uint32_t r = pg_ring_[j], b = pg_row_[r], e = pg_row_[r + 1];
+        fputs(j == pg_first_[k] ? "(" : ", (", fp);
+        for (uint32_t p = b; p <= e; p++) {  // (closed: the first point again at the end)
+          const size_t q = p == e ? b : p;
+          fprintf(fp, "%s%.6f %.6f", p == b ? "" : ", ", sc.UnscaleX(pg_xy_[2 * q]), sc.UnscaleY(pg_xy_[2 * q + 1]));
+        }
+        fputs(")", fp);
+      }
+      fputs(")\n", fp);
+    }
+    fclose(fp);
   }
   // the device map as a CDB file: "id points first last left right", then the points
   void WriteOutputMapFile(const char* path) const {
@@ -251,6 +360,10 @@ class MapOverlayLBVH {
   std::vector<int64_t> om_xy_;  // the device output map on the host (-output_map)
   std::vector<uint32_t> om_row_;
   std::vector<int32_t> om_left_, om_right_;
+  std::vector<rj_polygon> pg_polygons_;  // the polygons on the host (-polygons), with the rings' points and the map's face pairs
+  std::vector<uint32_t> pg_first_, pg_ring_, pg_row_;
+  std::vector<int64_t> pg_xy_;
+  std::vector<int32_t> pg_pairs_;
   uint32_t* pairs_ = nullptr;
   uint32_t* closest_[2] = {nullptr, nullptr};
   int32_t* faces_[2] = {nullptr, nullptr};
@@ -266,7 +379,7 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
   auto g2 = load_from(f.poly2, f.serialize, f.v);
   tm.next("Create App");
   Context ctx({g1, g2}, f.device, f.scale_fma);
-  MapOverlayLBVH overlay(ctx, f.xsect_factor, f.mode == "grid", f.grid_size, !f.face_table.empty() || !f.output_map.empty());
+  MapOverlayLBVH overlay(ctx, f.xsect_factor, f.mode == "grid", f.grid_size, !f.face_table.empty() || !f.output_map.empty() || !f.polygons.empty());
   overlay.SetOperation(f.how, f.by);
   overlay.SetMerge(f.merge);
   tm.next("Load Data");
@@ -291,6 +404,10 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
     tm.next("Compute output map");
     overlay.ComputeOutputMap();
   }
+  if (!f.polygons.empty()) {
+    tm.next("Compute polygons");
+    overlay.ComputePolygons();
+  }
   if (f.check && f.mode != "grid") {  // run_overlay.cu:199-204: compare with -mode=grid
     tm.next("Check result");
     if (!overlay.CheckAgainstGrid(f.grid_size)) throw std::runtime_error("result differs from -mode=grid");
@@ -307,6 +424,10 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
     tm.next("Write output map");
     overlay.WriteOutputMapFile(f.output_map.c_str());
   }
+  if (!f.polygons.empty()) {
+    tm.next("Write polygons");
+    overlay.WritePolygons(f.polygons.c_str());
+  }
   tm.end();
 }
 
@@ -317,7 +438,7 @@ int main(int argc, char* argv[]) {
     std::cerr << "Usage: " << argv[0] << " -poly1 <map0.cdb> -poly2 <map1.cdb> -mode lbvh|grid [-grid_size 2048] [-output <result.cdb>]\n"
               << "  [-serialize <dir>] [-xsect_factor 0.2] [-check] [-device 0] [-v 1]\n"
               << "  [-face_table <rows.txt>] [-output_map <map.cdb>] [-how intersection|union|difference|symmetric_difference|identity]\n"
-              << "  [-by pair|map0|map1] [-merge]\n";
+              << "  [-by pair|map0|map1] [-merge] [-polygons <polygons.txt>]\n";
     return 1;
   }
   Flags f;

@@ -427,10 +427,76 @@ class DeviceRings:
             out.setdefault(int(g["face"]), []).append(((int(g["area2_hi"]) << 64) | int(g["area2_lo"]), pts))
         return out
 
+    def Polygons(self, handle, capacities=None):
+        """The polygons of these rings as a DevicePolygons (rj_rings_polygons): every hole assigned to the outer ring it
+        lies in, on the device.  Needs the points.  capacities = (polygons, members): PolygonsOverflow with the true
+        counts when one is too small; left open, a sizing call finds them."""
+        if self.ring_xy is None:
+            raise RuntimeError("DeviceRings.Polygons needs the points (points=True)")
+        args = (self.rings, self.n_rings, self.ring_row, self.ring_xy, self.n_points, 0)
+        if capacities is None:
+            try:
+                c = handle.rings_polygons(*args, (0, 0), None, None, None, None)
+            except _capi.PolygonsOverflow as e:
+                c = e.counts
+            capacities = (c["n_polygons"], c["n_members"])
+        pc, mc = (int(v) for v in capacities)
+        bufs = [handle.alloc(4 * max(1, self.n_rings)), handle.alloc(_capi.POLYGON_DTYPE.itemsize * max(1, pc)), handle.alloc(4 * (pc + 1)),
+                handle.alloc(4 * max(1, mc))]
+        try:
+            counts = handle.rings_polygons(*args, (pc, mc), *bufs)
+        except _capi.RayJoinError:
+            for b in bufs:
+                b.free()
+            raise
+        return DevicePolygons(*bufs, self.n_rings, counts)
+
     def free(self):
         for b in (self.rings, self.ring_first, self.ring_half, self.ring_row, self.ring_xy):
             if b is not None:
                 b.free()
+
+
+class DevicePolygons:
+    """The polygons of a DeviceRings in device memory (rj_rings_polygons): parent (uint32 per ring: the shell's ring index
+    for a hole, its own for a shell, RJ_POLY_NONE for a ring of face 0 and for an orphan), polygons (POLYGON_DTYPE rows,
+    ascending by shell), poly_first (uint32 CSR of the polygons into poly_ring) and poly_ring (uint32 ring indices: the
+    shell, then its holes) as DeviceBuffers, and the counts n_polygons, n_members, n_holes, n_orphans, n_face0."""
+
+    def __init__(self, parent, polygons, poly_first, poly_ring, n_rings, counts):
+        self.parent, self.polygons_, self.poly_first, self.poly_ring = parent, polygons, poly_first, poly_ring
+        self.n_rings = int(n_rings)
+        self.counts = dict(counts)
+        for name in _capi.POLYGONS_COUNTS:
+            setattr(self, name, int(counts[name]))
+
+    def to_host(self):
+        """-> dict(parent, polygons, poly_first, poly_ring, counts)"""
+        n = self.n_polygons
+        return dict(parent=self.parent.to_host(np.uint32, self.n_rings), polygons=self.polygons_.to_host(_capi.POLYGON_DTYPE, n),
+                    poly_first=self.poly_first.to_host(np.uint32, n + 1), poly_ring=self.poly_ring.to_host(np.uint32, self.n_members),
+                    counts=dict(self.counts))
+
+    def polygons(self, rings, scaling=None):
+        """[(face, area2, shell_points[n, 2], [hole_points, ...])] on the host, in polygon order, of the DeviceRings these
+        polygons were computed from: area2 exact (a Python int, scaled units^2), the points scaled integers, or input
+        coordinates when the map's maps.Scaling is given"""
+        host, rh = self.to_host(), rings.to_host()
+        row = rh["ring_row"].astype(np.int64)
+
+        def points(r):
+            pts = rh["ring_xy"][row[r]:row[r + 1]]
+            return scaling.unscale(pts) if scaling is not None else pts
+
+        first, out = host["poly_first"].astype(np.int64), []
+        for k, g in enumerate(host["polygons"]):
+            members = host["poly_ring"][first[k]:first[k + 1]].tolist()
+            out.append((int(g["face"]), (int(g["area2_hi"]) << 64) | int(g["area2_lo"]), points(members[0]), [points(r) for r in members[1:]]))
+        return out
+
+    def free(self):
+        for b in (self.parent, self.polygons_, self.poly_first, self.poly_ring):
+            b.free()
 
 
 def overlay_op(how, by):
