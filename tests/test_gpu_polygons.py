@@ -3,8 +3,10 @@ plain-Python definition (tests/polygons_ref.py), array for array: the cases of t
 columns, ray degeneracies, the domain-wide edge, laminar families with construction-known parents), the rings of the
 device's OWN output maps of the overlay tests' pairs (five calls, drop and merge on and off) with the exact area invariant
 against the device's own face table, the rings of fuzzed overlays; against the host twin where the input is too large for
-the Python loop (the lattice pair's clip, more rings than one grid covers, more than 2^16 holes in one face); overflow with
-canaries, the sizing call, no rings, malformed input; the command line.  The CPU side is tests/test_polygons.py."""
+the Python loop (the lattice pair's clip, more rings than one grid covers, more than 2^16 holes in one face); the raw ring
+sets of tests/polygons_soups.py against the answers tests/test_polygons.py holds the definition, the twin and the
+constructions equal on; overflow with canaries, the sizing call, no rings, malformed input; the command line.  The CPU
+side is tests/test_polygons.py."""
 import os
 import subprocess
 import sys
@@ -19,6 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import overlay_hard_pairs as H  # noqa: E402
 import polygons_cases as PC  # noqa: E402
 import polygons_ref as PR  # noqa: E402
+import polygons_soups as PS  # noqa: E402
 import rings_planar as P  # noqa: E402
 import rings_ref as D  # noqa: E402
 import test_gpu_overlay_fuzz as FZ  # noqa: E402
@@ -27,7 +30,8 @@ from test_gpu_overlay_merge import CALLS, DROP, MERGE, overlay_of, raw_map  # no
 from test_gpu_rings import FUZZ_EDGE_CAP, DeviceMap  # noqa: E402
 from test_overlay_map import pair  # noqa: E402
 from test_overlay_ops import OPS  # noqa: E402
-from test_polygons import LAMINAR_GPU_SEEDS, args_of, bad_inputs, hand_case, laminar_case, span_case, twin_lib, twin_polygons  # noqa: E402
+from test_polygons import BIG_FIELD_SIDE, CARRY_SQUARES, FAN_SEEDS, LAMINAR_GPU_SEEDS, SLIVER_SEEDS, big_field_case, check_hole_field, soup_case  # noqa: E402
+from test_polygons import args_of, bad_inputs, hand_case, laminar_case, span_case, twin_lib, twin_polygons  # noqa: E402
 from test_rings import FIELD  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -265,6 +269,69 @@ def test_one_face_with_more_than_65536_holes_equals_the_host_twin(handle):
     PR.assert_same_polygons(got, want)
     assert got["counts"] == dict(n_polygons=n + 1, n_members=2 * n + 1, n_holes=n, n_orphans=0, n_face0=1)
     assert int(got["polygons"]["n_holes"][0]) == n and (got["parent"][1:n + 2] == 1).all() and stats["shift"] == 16
+
+
+def test_hole_field_of_270400_holes_makes_a_second_trip_of_the_lane_groups(handle):
+    """PC.hole_field(520): 540 802 rings, 270 400 of them holes with a ring above, more than the 262 144 rings that one grid
+    of k_pg_above (8192 blocks of 256 threads, 8 lanes to a ring) covers.  The device's rings are the rings twin's, so the
+    polygons twin's answer of tests/test_polygons.py serves; and the construction: every hole's parent is ring 1."""
+    m, rg_twin, want, stats = big_field_case()
+    rg, got = device_rings_and_polygons(handle, m)
+    D.assert_same_rings(rg, rg_twin)
+    n = BIG_FIELD_SIDE * BIG_FIELD_SIDE
+    assert rg["counts"]["n_rings"] == 2 * n + 2 > 2 * (8192 * 256 // 8)
+    PR.assert_same_polygons(got, want)
+    check_hole_field(rg["rings"], got, stats, n)
+
+
+# ---- raw ring sets: the answers of tests/test_polygons.py ------------------------------------------------------------------
+def check_soup(h, kind, *args):
+    rings, want = soup_case(kind, *args)[::2]
+    got = device_polygons(h, *rings)
+    PR.assert_same_polygons(got, want, (kind,) + args)
+    return got
+
+
+@pytest.mark.parametrize("seed", SLIVER_SEEDS)
+def test_sliver_soups_equal_the_definition(handle, seed):
+    """products near 2^90 that differ by at most 5, heights that differ by 2^-45, falling edges: candidate(), floor_div()
+    and lower() on the device, the winners of 8 lanes reduced over buckets of about 490 near-ties"""
+    check_soup(handle, "sliver", seed)
+
+
+@pytest.mark.parametrize("seed", FAN_SEEDS)
+def test_slope_fans_equal_the_definition(handle, seed):
+    """equal heights: the slope step and the slot step of lower(), within a lane and across lanes"""
+    got = check_soup(handle, "fan", seed)
+    for g in soup_case("fan", seed)[1]["groups"]:
+        assert int(got["parent"][g["hole"]]) == g["above"], seed
+
+
+def test_top_sweep_equals_the_definition(handle):
+    """k_pg_tops: rings shorter than, as long as and longer than the lane group, the top at every lane position"""
+    got = check_soup(handle, "tops")
+    assert np.array_equal(got["parent"], soup_case("tops")[1]["parent"])
+
+
+def test_long_rings_equal_the_definition(handle):
+    got = check_soup(handle, "long")
+    assert got["parent"].tolist() == [1, 1, 2, 3, 4]
+
+
+@pytest.mark.parametrize("faces", PS.DEGENERATE_FACES)
+def test_degenerate_records_equal_the_definition(handle, faces):
+    """walks that end at an orphan after up to 39 steps (a state that has ended, copied by jump_round), rings without
+    points as the first and the last record, faces outside [0, 2^31) in the entry keys and the ring order"""
+    got = check_soup(handle, "degenerate", faces)
+    assert got["counts"] == PS.DEGENERATE_COUNTS
+
+
+@pytest.mark.parametrize("salt", [0, 1])
+def test_carry_field_equals_the_construction(handle, salt):
+    """40 000 members: 39 blocks of rocPRIM's scan of the int128 areas (1024 items to a block for a 16-byte type); with
+    salt 1 the low words of the prefix carry into the high ones at about half of the shells"""
+    got = check_soup(handle, "carry", CARRY_SQUARES, salt)
+    assert got["counts"]["n_polygons"] == CARRY_SQUARES and got["counts"]["n_orphans"] == 0
 
 
 # ---- the rings of fuzzed overlays ---------------------------------------------------------------------------------------------

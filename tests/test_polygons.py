@@ -2,12 +2,17 @@
 tests/polygons_cases.py with the answers written out; on laminar families of nested rectangles whose parents are known from
 the construction; the host twin of the device's per-element functions (tests/hosttwin/polygons_twin.cc compiling
 rayjoin_amd/csrc/rj_polygons.h) against that definition, every array and every count, on all cases and on the helper
-output maps of the overlay tests' pairs for every operation.  The GPU side is tests/test_gpu_polygons.py."""
+output maps of the overlay tests' pairs for every operation; on the raw ring sets of tests/polygons_soups.py -- ray orders
+that only exact arithmetic at 2^46 decides, tops at every lane position, rings of 100 003 points, records without points,
+faces outside 31 bits, areas whose prefix needs all 128 bits -- twin = definition = the construction's answer, with the
+conditions that keep each of them from running empty.  The GPU side is tests/test_gpu_polygons.py."""
 import ctypes as C
 import functools
+import itertools
 import os
 import subprocess
 import sys
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -18,10 +23,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import polygons_cases as PC  # noqa: E402
 import polygons_ref as PR  # noqa: E402
+import polygons_soups as PS  # noqa: E402
 import rings_cases as K  # noqa: E402
 import rings_ref as D  # noqa: E402
 from test_overlay_ops import OPS  # noqa: E402
 from test_rings import as_map, helper_maps  # noqa: E402
+from test_rings import twin_lib as rings_twin_lib  # noqa: E402
+from test_rings import twin_rings  # noqa: E402
 
 SRC = os.path.join(ROOT, "tests", "hosttwin", "polygons_twin.cc")
 HDRS = [os.path.join(ROOT, "rayjoin_amd", "csrc", name) for name in ("rj_polygons.h", "rj_rings.h")]
@@ -248,6 +256,208 @@ def test_twin_equals_the_definition_on_the_helper_output_maps(oracle, twin, name
         seen += 1
         holes += want["counts"]["n_holes"]
     assert seen == 4 * len(OPS) and (holes > 0 or name != "rings")  # (the rings pair: 47 holes under (union, pair))
+
+
+# ---- raw ring sets: tests/polygons_soups.py ------------------------------------------------------------------------------
+SLIVER_SEEDS = tuple(range(8))
+FAN_SEEDS = tuple(range(6))
+CARRY_SQUARES = 20_000
+BIG_FIELD_SIDE = 520
+SOUPS = {"sliver": PS.sliver_ceilings, "fan": PS.slope_fan, "tops": PS.top_sweep, "long": PS.long_rings, "degenerate": PS.degenerate_records,
+         "carry": PS.carry_field}
+
+
+@functools.lru_cache(maxsize=None)
+def soup_case(kind, *args):
+    """-> ((rings, ring_row, ring_xy), info, the expected polygons): the definition's, and for the carry field (where the
+    definition is quadratic) the construction's; computed once, shared with the GPU tests, left unchanged"""
+    rings, row, xy, info = SOUPS[kind](*args)
+    want = PS.answer_from_parents(rings, info["parent"]) if kind == "carry" else PR.polygons_ref(rings, row, xy)
+    return (rings, row, xy), info, want
+
+
+def is_candidate(u, v, p, num=int):
+    """the test of candidate() in Python integers, or in floats"""
+    return v[0] <= p[0] < u[0] and num(u[1] - v[1]) * num(p[0] - v[0]) > num(p[1] - v[1]) * num(u[0] - v[0])
+
+
+def height_at(u, v, px, num=Fraction):
+    return num(v[1]) + num(u[1] - v[1]) * num(px - v[0]) / num(u[0] - v[0])
+
+
+def check_twin(twin, args, want, what):
+    rc, got, stats = twin_polygons(twin, *args)
+    assert rc == 0, what
+    PR.assert_same_polygons(got, want, what)
+    return stats
+
+
+@pytest.mark.parametrize("seed", SLIVER_SEEDS)
+def test_sliver_soup_is_decided_by_exact_products_and_remainders(twin, seed):
+    """heights p.y + t / d with d near 2^45 and t in [-2, 5]: candidate() compares two products near 2^90 that differ by t,
+    two candidates differ by about 2^-45 (the step rem_a d_b against rem_b d_a of lower()), half of the edges fall (a
+    negative n in floor_div).  The seed conditions: per hole a quarter of its edges are candidates and a quarter are not;
+    the candidate test in floats decides at least one edge differently; the float heights order at least one pair of
+    candidates differently; a falling edge is a candidate; the bucket of a hole holds all its edges."""
+    args, info, want = soup_case("sliver", seed)
+    stats = check_twin(twin, args, want, seed)
+    flips = orders = falling = 0
+    for _, p, edges in info["holes"]:
+        cands = [e for e in edges if e[2] > 0]
+        assert 4 * len(cands) >= len(edges) and 4 * (len(edges) - len(cands)) >= len(edges), seed
+        for u, v, t, d in edges:
+            assert is_candidate(u, v, p) == (t > 0) and height_at(u, v, p[0]) == p[1] + Fraction(t, d) and u[0] - v[0] == d
+            flips += is_candidate(u, v, p, float) != (t > 0)
+        falling += sum(1 for u, v, _, _ in cands if u[1] < v[1])
+        hs = [(Fraction(t, d), height_at(u, v, p[0], float)) for u, v, t, d in cands]
+        orders += sum(1 for a, b in itertools.combinations(hs, 2) if (a[0] < b[0]) != (a[1] < b[1]))
+    assert flips >= 1 and orders >= 1 and falling >= 1, (seed, flips, orders, falling)
+    assert stats["longest_bucket"] >= len(info["holes"][0][2]) and stats["shift"] >= 40
+    assert want["counts"]["n_holes"] >= len(info["holes"]) and want["counts"]["n_polygons"] > 100
+
+
+@pytest.mark.parametrize("seed", FAN_SEEDS)
+def test_slope_fan_is_decided_by_exact_slopes_then_slots(twin, seed):
+    """per hole a fan of candidates of exactly equal height (an integer with n = 0, a half, an integer with n = dy dx)
+    whose neighbouring slopes differ by 1 / (dx_a dx_b), the cross products of lower() by 1, 2 or 4; the lowest slope comes
+    more than once, and in the first fan once more with twice the length: the ring of the smallest slot is the ring above.
+    The seed conditions:
+    every fan edge is a candidate of the fan's height, the copies and the collinear edge among them; the cross products
+    of lower() in floats order at least one neighbouring pair differently; the winners fall and rise."""
+    args, info, want = soup_case("fan", seed)
+    check_twin(twin, args, want, seed)
+    _, above = PR.above_of(*args)
+    flips, signs = 0, set()
+    for g, n_ties, det in zip(info["groups"], (4, 2, 2), (1, 2, 4)):
+        p = g["p"]
+        for _, u, v in g["edges"]:
+            assert is_candidate(u, v, p) and height_at(u, v, p[0]) == g["height"], seed
+        assert len(g["ties"]) == n_ties and g["above"] == min(g["ties"]) and above[g["hole"]] == g["above"], seed
+        assert int(want["parent"][g["hole"]]) == g["above"], seed
+        by_ring = {r: (u, v) for r, u, v in g["edges"]}
+        lengths = {by_ring[r][0][0] - by_ring[r][1][0] for r in g["ties"]}
+        assert len(lengths) == (2 if n_ties == 4 else 1)  # (the collinear edge of double length)
+        for a, b in g["pairs"]:
+            (ua, va), (ub, vb) = g["edges"][a][1:], g["edges"][b][1:]
+            dya, dxa, dyb, dxb = ua[1] - va[1], ua[0] - va[0], ub[1] - vb[1], ub[0] - vb[0]
+            assert abs(dya * dxb - dyb * dxa) == det
+            flips += (dya * dxb < dyb * dxa) != (float(dya) * float(dxb) < float(dyb) * float(dxa))
+        u, v = by_ring[g["above"]]
+        signs.add(u[1] > v[1])
+    assert flips >= 1 and signs == {False, True}, (seed, flips, signs)
+    assert info["groups"][1]["height"].denominator == 2 and info["groups"][2]["p"][0] > info["groups"][2]["edges"][0][2][0]
+
+
+def test_top_sweep_has_the_top_at_every_lane_position(twin):
+    """rings of 1 to 1000 points, the top at every index: a ring whose top comes out as any other of its points -- the point
+    of equal y and smaller x among them -- has the decoy above it.  Every lane position of a group of 8 holds a top, and
+    a point of equal y sits in another one."""
+    args, info, want = soup_case("tops")
+    PR.assert_same_polygons(PS.answer_from_parents(args[0], info["parent"]), want)
+    check_twin(twin, args, want, "tops")
+    assert {t % 8 for _, _, t, _ in info["holes"]} == set(range(8)) and {n for _, n, _, _ in info["holes"]} == set(PS.TOP_SIZES)
+    assert all((twin_at is None) == (n == 1) and (n == 1 or twin_at % 8 != t % 8) for _, n, t, twin_at in info["holes"])
+    assert want["counts"] == dict(n_polygons=len(info["holes"]) + 1, n_members=2 * len(info["holes"]) + 1, n_holes=len(info["holes"]), n_orphans=0,
+                                  n_face0=0)
+    assert int(np.abs(args[2]).max()) == PS.LIM
+    # the decoy does its work: with the equal-y point as the top the ring above is the decoy
+    rings, row, xy = args
+    ring, n, t, twin_at = next(h for h in info["holes"] if h[1] == 17)
+    moved = xy.copy()
+    moved[int(row[ring]) + t, 0] -= 20
+    assert int(PR.polygons_ref(rings, row, moved)["parent"][ring]) != int(want["parent"][ring])
+
+
+def test_long_rings_have_the_top_late_and_the_winning_edge_deep(twin):
+    args, info, want = soup_case("long")
+    PR.assert_same_polygons(PS.answer_from_parents(args[0], info["parent"]), want)
+    check_twin(twin, args, want, "long")
+    row = args[1].tolist()
+    assert sorted(b - a for a, b in zip(row, row[1:])) == [2, 2, 4, PS.LONG, PS.LONG] and want["parent"].tolist() == [1, 1, 2, 3, 4]
+
+
+@pytest.mark.parametrize("faces", PS.DEGENERATE_FACES)
+def test_degenerate_records(twin, faces):
+    """a column of 40 holes without a shell (orphans by walks of up to 39 steps and the end), the same column with one,
+    rings without points of every kind as the first, a middle and the last ring of their face, a one-point ring; faces
+    outside [0, 2^31) order as unsigned"""
+    args, info, want = soup_case("degenerate", faces)
+    PR.assert_same_polygons(PS.answer_from_parents(args[0], info["parent"]), want, faces)
+    stats = check_twin(twin, args, want, faces)
+    assert want["counts"] == PS.DEGENERATE_COUNTS, faces
+    kinds, above = PR.above_of(*args)
+    steps, at = 0, info["column"][0]
+    while above[at] is not None:
+        at, steps = above[at], steps + 1
+    assert steps >= 32 and kinds[at] == "hole" and stats["rounds"] >= 6, (faces, steps)
+    rings, row, _ = args
+    empty = np.flatnonzero(np.diff(row.astype(np.int64)) == 0).tolist()
+    assert len(empty) == 9 and empty[0] == 0 and empty[-1] == len(rings) - 1 and int(row[-2]) == int(row[-1])
+    key = (rings["face"].astype(np.int64) & 0xFFFFFFFF) << 32 | rings["leader"]
+    assert (np.diff(key) > 0).all() and set(rings["face"].tolist()) == {0, *faces}
+
+
+@pytest.mark.parametrize("salt", [0, 1])
+def test_carry_field_sums_int128_areas_over_many_members(twin, salt):
+    """20 000 polygons of a shell of 2^65 and a hole of -2 (2^32 - 2)(2^32 - 3) in three faces: 40 000 members, 39
+    blocks of the device's int128 scan (rocPRIM's default configuration for a 16-byte type that is no built-in integer:
+    256 threads of 16 / (16 / 4) = 4 items, 1024 to a block; 3584 with the tuning for gfx942, 1280 with the one for an
+    unknown target).  The prefix crosses a multiple of 2^64 at every member.  With salt 0 the low words never carry (2^65
+    has none, the holes' add up to 20 000 (10 x 2^32 - 12)); salt 1 adds a pseudo-random low word to every recorded shell
+    area, and the low words of the prefix carry into the high ones at about half of the shells."""
+    args, info, want = soup_case("carry", CARRY_SQUARES, salt)
+    check_twin(twin, args, want, salt)
+    n = CARRY_SQUARES
+    crossings = carries = prefix = 0
+    for a in info["areas"]:
+        crossings += (prefix + a) >> 64 != prefix >> 64
+        carries += (prefix & PS.M64) + (a & PS.M64) > PS.M64 and a > 0
+        prefix += a
+    assert 2 * crossings >= n and len(info["areas"]) == 2 * n and (salt == 0 or 4 * carries >= n), (crossings, carries)
+    assert want["counts"] == dict(n_polygons=n, n_members=2 * n, n_holes=n, n_orphans=0, n_face0=0)
+    if salt == 0:
+        assert set(PR.area2_of(want["polygons"])) == {10 * (1 << 32) - 12}
+    # the definition itself on a field that is small enough for it
+    small, small_info, _ = soup_case("carry", 300, salt)
+    PR.assert_same_polygons(PS.answer_from_parents(small[0], small_info["parent"]), PR.polygons_ref(*small), salt)
+
+
+def test_an_edge_that_ends_on_a_strip_boundary_has_no_entry_beyond_it(twin):
+    """the ceiling edge (65536, 9) -> (65526, 9) lies in strips strip(v.x) .. strip(u.x - 1): one entry under shift 16, although
+    u.x starts the next strip (an entry there would change no answer -- p.x < u.x fails for every ray of that strip --
+    only the count of entries that the shift is chosen by)"""
+    rings, row, xy, index = PS.pack([(1, 0, -7, PS._triangle(65530, 5)[0]), (1, 1, 1, [(65536, 9), (65526, 9)])])
+    want = PR.polygons_ref(rings, row, xy)
+    stats = check_twin(twin, (rings, row, xy), want, "boundary")
+    assert want["parent"].tolist() == [1, 1] and (65536 + PS.LIM) % (1 << 16) == 0
+    assert stats["shift"] == 16 and stats["n_edges"] == 2 and stats["n_entries"] == 2, stats
+
+
+@functools.lru_cache(maxsize=None)
+def big_field_case():
+    """PC.hole_field(520) -> (the map, its rings by the rings twin, their polygons and stats by the polygons twin): once for
+    the CPU and the GPU test (the twin takes seconds: each of 270 400 holes against the 521 ceiling edges of its bucket)"""
+    m = PC.hole_field(BIG_FIELD_SIDE)
+    rc, rg, _ = twin_rings(rings_twin_lib(), m)
+    assert rc == 0
+    rc, got, stats = twin_polygons(twin_lib(), *args_of(rg))
+    assert rc == 0
+    return m, rg, got, stats
+
+
+def check_hole_field(rings, got, stats, n):
+    """the construction's answer of PC.hole_field with n holes, and the counts written out"""
+    PR.assert_same_polygons(got, PS.hole_field_answer(rings, n))
+    assert got["counts"] == dict(n_polygons=n + 1, n_members=2 * n + 1, n_holes=n, n_orphans=0, n_face0=1)
+    assert int(got["polygons"]["n_holes"][0]) == n and (got["parent"][1:n + 2] == 1).all() and stats["shift"] == 16
+
+
+def test_hole_field_of_270400_holes_on_the_twin_has_the_parents_of_the_construction():
+    """540 802 rings: more than the 262 144 that one grid of the device's lane groups of 8 covers"""
+    _, rg, got, stats = big_field_case()
+    n = BIG_FIELD_SIDE * BIG_FIELD_SIDE
+    assert len(rg["rings"]) == 2 * n + 2 > 2 * 262144 and stats["longest_bucket"] == BIG_FIELD_SIDE + 1
+    check_hole_field(rg["rings"], got, stats, n)
 
 
 # ---- the contract of the call ----------------------------------------------------------------------------------------------
