@@ -470,6 +470,49 @@ int rj_rings_polygons(rj_handle h, const rj_ring* rings_dev, uint64_t n_rings, c
                       uint32_t* parent_dev, rj_polygon* polygons_dev, uint32_t* poly_first_dev,
                       uint32_t* poly_ring_dev, rj_polygons_counts* counts);
 
+/* ---- rings to map ------------------------------------------------------------------------ */
+/* rj_rings_map flags */
+#define RJ_RMAP_DISSOLVE 1u /* leave out every unique edge with the same face on both sides (n_dissolved) */
+
+typedef struct {
+  uint64_t n_chains, n_points, n_edges, n_closed, n_zero_edges, n_conflicts, n_dissolved;
+} rj_rings_map_counts;
+
+/* extends: the chain map that a set of labelled rings bounds, on the device -- the inverse of rj_map_rings, and the way
+ * in for polygon data: one closed ring per boundary (every shared boundary stored twice) becomes chains with a left and
+ * a right face, shared boundaries stored once, cut at junctions, and maximal.  ring_row_dev[n_rings + 1] is the CSR into
+ * ring_xy_dev[2 n_points] (the layout rj_map_rings writes; a ring is a closed walk, its last point is followed by its
+ * first; 0, 1 or 2 points are allowed); ring r has the 32-bit label *(int32_t*) ((char*) ring_face_dev + r face_stride)
+ * on the LEFT of its walk, y up (shells counter-clockwise, holes clockwise; 0 is "no face"): face_stride 4 reads a plain
+ * int32 array, sizeof(rj_ring) the face field of rj_map_rings' records in place.  n_points < 2^31.  The definition, in
+ * full in rayjoin_amd/csrc/rj_ringmap.h:
+ *   point slot i gives the directed edge u -> v to its successor; u == v is dropped (n_zero_edges); lo < hi its points by
+ *   (x, y); forward (u == lo) it has the ring's face on the left of lo -> hi, backward on the right.  One unique edge per
+ *   distinct (lo, hi), ascending by (lo.x, lo.y, hi.x, hi.y): left = the face of its forward directed edge with the
+ *   smallest slot (0: none), right the same over the backward ones; more than one of a kind is counted in n_conflicts
+ *   (overlapping input; the result is still determined).  Under RJ_RMAP_DISSOLVE an edge with left == right is left out
+ *   (n_dissolved).  Kept edge e has the half-edges 2 e (lo -> hi, faces (left, right)) and 2 e + 1 (hi -> lo, faces
+ *   swapped).  h passes the vertex it arrives at when exactly two kept half-edges start there, h ^ 1 and one other, g,
+ *   with faces(g) == faces(h): next(h) = g; otherwise it ends there.  The maximal sequences under next are the walks; the
+ *   leader of an open walk is its first half-edge, of a closed walk (a cycle) its smallest, which it is read from; of a
+ *   walk and its twin walk the chain is the one with the smaller leader.  A chain's points: the start points of its
+ *   half-edges, then the end point of the last (a closed chain repeats its first point); left / right: its leader's
+ *   faces; chains ascend by leader.  n_points = n_edges + n_chains; n_closed counts the closed chains.
+ * Output, all caller-owned device memory, with the contract of rj_upload_map_dev (every chain has at least 2 points):
+ * xy_dev[2 point_capacity], row_index_dev[chain_capacity + 1], left_dev / right_dev[chain_capacity].  RJ_E_OVERFLOW when a
+ * count exceeds its capacity: *counts holds the true counts and nothing beyond any capacity is written; all capacities
+ * 0 (arrays may be NULL) is the sizing call.  n_rings == 0 is valid.  RJ_E_INVALID for a ring_row that does not start
+ * at 0, decreases or does not end at n_points, a coordinate outside [-2^46, 2^46), n_points >= 2^31, a face_stride below
+ * 4 or no multiple of 4, an unknown flag bit; RJ_E_INTERNAL when a round budget runs out (33 doubling steps: cannot
+ * happen below 2^32 half-edges).  Runs on the handle's stream with one host sync, at the end, to read the counts;
+ * scratch (288 bytes per point slot plus the sorts' temporary storage) is allocated per call and freed; no state of the
+ * handle changes. */
+int rj_rings_map(rj_handle h, const uint32_t* ring_row_dev, const int64_t* ring_xy_dev, uint64_t n_points,
+                 const void* ring_face_dev, uint64_t face_stride, uint64_t n_rings, uint32_t flags,
+                 uint64_t chain_capacity, uint64_t point_capacity,
+                 int64_t* xy_dev, uint32_t* row_index_dev, int32_t* left_dev, int32_t* right_dev,
+                 rj_rings_map_counts* counts);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

@@ -24,6 +24,7 @@ OVERLAY_BY = {"pair": RJ_OV_BY_PAIR, "map0": RJ_OV_BY_MAP0, "map1": RJ_OV_BY_MAP
 RJ_RINGS_SKIP_FACE0 = 1  # rj_map_rings flags
 RJ_RINGS_NO_POINTS = 2
 RJ_RING_MIXED = 1  # rj_ring flags
+RJ_RMAP_DISSOLVE = 1  # rj_rings_map flags
 RJ_T_BUILD, RJ_T_LSI_KERNEL, RJ_T_PIP_KERNEL, RJ_T_LSI_POINTS, RJ_T_SORT, RJ_T_ORDER = 0, 1, 2, 3, 4, 5
 RJ_T_BUILD_KEYS, RJ_T_BUILD_SORT, RJ_T_BUILD_LEAVES, RJ_T_BUILD_LEVELS, RJ_T_PIP_WALK, RJ_T_BUILD_RUNS = 6, 7, 8, 9, 10, 11
 MISS_EID = 0xFFFFFFFF
@@ -40,6 +41,7 @@ RJ_POLY_NONE = 0xFFFFFFFF  # rj_rings_polygons' parent of a ring of face 0 and o
 # rj_polygon: one outer ring with its holes -- its face, the shell's ring index, its holes, twice its area
 POLYGON_DTYPE = np.dtype([("face", "<i4"), ("shell", "<u4"), ("n_holes", "<u4"), ("_pad", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
 POLYGONS_COUNTS = ("n_polygons", "n_members", "n_holes", "n_orphans", "n_face0")
+RINGS_MAP_COUNTS = ("n_chains", "n_points", "n_edges", "n_closed", "n_zero_edges", "n_conflicts", "n_dissolved")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
 _vp, _u64, _i64, _int = C.c_void_p, C.c_uint64, C.c_int64, C.c_int
@@ -89,6 +91,7 @@ SYMBOLS = {
                                  C.c_uint32]),
     "rj_map_rings": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rj_rings_polygons": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "rj_rings_map": (_int, [_vp, _vp, _vp, _u64, _vp, _u64, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -173,6 +176,15 @@ class RingsOverflow(RayJoinError):
 
 class PolygonsOverflow(RayJoinError):
     """RJ_E_OVERFLOW of rj_rings_polygons: counts = dict(n_polygons, n_members, n_holes, n_orphans, n_face0), the true counts"""
+
+    def __init__(self, msg, counts):
+        super().__init__(RJ_E_OVERFLOW, msg)
+        self.counts = counts
+
+
+class RingsMapOverflow(RayJoinError):
+    """RJ_E_OVERFLOW of rj_rings_map: counts = dict(n_chains, n_points, n_edges, n_closed, n_zero_edges, n_conflicts, n_dissolved),
+    the true counts"""
 
     def __init__(self, msg, counts):
         super().__init__(RJ_E_OVERFLOW, msg)
@@ -524,6 +536,21 @@ class Handle:
         named = dict(zip(POLYGONS_COUNTS, (int(v) for v in counts)))
         if rc == RJ_E_OVERFLOW:
             raise PolygonsOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        self._check(rc)
+        return named
+
+    def rings_map(self, ring_row_dev, ring_xy_dev, n_points, ring_face_dev, face_stride, n_rings, flags, capacities, xy_dev, row_index_dev,
+                  left_dev, right_dev):
+        """rj_rings_map of labelled rings in device memory (ring_face_dev read through face_stride bytes) into the caller's
+        device arrays; capacities = (chains, points).  Returns the counts as a dict (RINGS_MAP_COUNTS); RingsMapOverflow
+        (with the true counts) past a capacity."""
+        counts = (_u64 * 7)()
+        cc, pc = (int(v) for v in capacities)
+        rc = self.L.rj_rings_map(self.h, _ptr(ring_row_dev), _ptr(ring_xy_dev), int(n_points), _ptr(ring_face_dev), int(face_stride),
+                                 int(n_rings), int(flags), cc, pc, _ptr(xy_dev), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev), counts)
+        named = dict(zip(RINGS_MAP_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise RingsMapOverflow(self.L.rj_last_error_string(self.h).decode(), named)
         self._check(rc)
         return named
 

@@ -19,6 +19,7 @@
 #include "rj_overlay_ops.h"
 #include "rj_pipeline.h"
 #include "rj_polygons.h"
+#include "rj_ringmap.h"
 #include "rj_rings.h"
 
 using namespace rj;
@@ -2766,6 +2767,43 @@ int rj_rings_polygons(rj_handle h, const rj_ring* rings_dev, uint64_t n_rings, c
   if (counts->n_polygons > polygon_capacity || counts->n_members > member_capacity)
     return fail(h, RJ_E_OVERFLOW, "rj_rings_polygons: %llu polygons, %llu members; capacities %llu, %llu", (unsigned long long) counts->n_polygons,
                 (unsigned long long) counts->n_members, (unsigned long long) polygon_capacity, (unsigned long long) member_capacity);
+  return RJ_OK;
+}
+
+int rj_rings_map(rj_handle h, const uint32_t* ring_row_dev, const int64_t* ring_xy_dev, uint64_t n_points, const void* ring_face_dev,
+                 uint64_t face_stride, uint64_t n_rings, uint32_t flags, uint64_t chain_capacity, uint64_t point_capacity, int64_t* xy_dev,
+                 uint32_t* row_index_dev, int32_t* left_dev, int32_t* right_dev, rj_rings_map_counts* counts) {
+  static_assert(sizeof(rj_rings_map_counts) == sizeof(ringmap::Counts) && RJ_RMAP_DISSOLVE == ringmap::kDissolve, "layouts");
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_rings_map: counts is null");
+  memset(counts, 0, sizeof(*counts));
+  if (flags & ~(uint32_t) RJ_RMAP_DISSOLVE) return fail(h, RJ_E_INVALID, "rj_rings_map: unknown flags 0x%x", flags);
+  if (face_stride < 4 || face_stride % 4) return fail(h, RJ_E_INVALID, "rj_rings_map: face_stride must be a multiple of 4, at least 4");
+  if (n_rings > 0xFFFFFFFEull || n_points >= (1ull << 31)) return fail(h, RJ_E_INVALID, "rj_rings_map: n_rings <= 2^32 - 2 and n_points < 2^31");
+  if (n_rings == 0 && n_points != 0) return fail(h, RJ_E_INVALID, "rj_rings_map: points without rings");
+  if ((n_rings && (!ring_row_dev || !ring_face_dev)) || (n_points && !ring_xy_dev)) return fail(h, RJ_E_INVALID, "rj_rings_map: null input array");
+  if ((chain_capacity && (!row_index_dev || !left_dev || !right_dev)) || (point_capacity && !xy_dev))
+    return fail(h, RJ_E_INVALID, "rj_rings_map: null output");
+  if (int r = set_device(h)) return r;
+  if (n_rings == 0) {  // no rings: the row's one entry, where the caller has an array
+    if (row_index_dev) {
+      RJ_HIP(h, hipMemsetAsync(row_index_dev, 0, 4, h->stream));
+      RJ_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return RJ_OK;
+  }
+  const ringmap::Out out{xy_dev, row_index_dev, left_dev, right_dev, chain_capacity, point_capacity};
+  ringmap::Meta m;
+  RJ_HIP(h, rings_map_device(h->stream, ring_row_dev, ring_xy_dev, n_points, ring_face_dev, face_stride, n_rings, flags, out, &m));
+  if (m.bad == ringmap::kBadStart) return fail(h, RJ_E_INVALID, "rj_rings_map: ring_row must start at 0");
+  if (m.bad == ringmap::kBadEnd) return fail(h, RJ_E_INVALID, "rj_rings_map: ring_row must end at n_points");
+  if (m.bad == ringmap::kBadRow) return fail(h, RJ_E_INVALID, "rj_rings_map: ring_row must not decrease");
+  if (m.bad) return fail(h, RJ_E_INVALID, "rj_rings_map: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  if (m.unfinished) return fail(h, RJ_E_INTERNAL, "rj_rings_map: a walk was not ranked within %d doubling steps", ringmap::kMaxRounds);
+  memcpy(counts, &m.counts, sizeof(*counts));
+  if (counts->n_chains > chain_capacity || counts->n_points > point_capacity)
+    return fail(h, RJ_E_OVERFLOW, "rj_rings_map: %llu chains, %llu points; capacities %llu, %llu", (unsigned long long) counts->n_chains,
+                (unsigned long long) counts->n_points, (unsigned long long) chain_capacity, (unsigned long long) point_capacity);
   return RJ_OK;
 }
 

@@ -32,6 +32,7 @@ struct Flags {
   std::string how, by;       // ours (polyover_exec): the overlay operation of -face_table / -output_map (rj_overlay_*_op); empty: the intersection
   bool merge = false;        // ours (polyover_exec): -output_map with RJ_OVM_MERGE_PIECES: adjacent pieces of one chain with equal faces as one chain
   std::string polygons;      // ours (polyover_exec): the polygons of the result (output map, rj_map_rings, rj_rings_polygons) as "f0 f1 area2 POLYGON (...)" lines
+  std::string coarse_map;    // ours (polyover_exec): the output map without degenerate pieces, through rj_map_rings and rj_rings_map: maximal chains, as CDB
   bool scale_fma = false;    // ours: scale with one fma per coordinate (nvcc's contraction of map.h:171-180) instead of scaling.h's multiply + add
 
   static bool parse_bool(const std::string& s) {
@@ -49,7 +50,7 @@ struct Flags {
     RJ_S(poly1) RJ_S(poly2) RJ_S(output) RJ_S(mode) RJ_S(serialize) RJ_S(sample) RJ_S(query)
     RJ_I(grid_size) RJ_D(xsect_factor) RJ_B(box) RJ_B(check) RJ_B(fau) RJ_I(warmup) RJ_I(repeat)
     RJ_I(ag) RJ_I(ag_iter) RJ_I(win) RJ_D(enlarge) RJ_I(sample_map_id) RJ_D(sample_rate)
-    RJ_I(seed) RJ_D(gen_t) RJ_I(gen_n) RJ_B(histo) RJ_B(profile) RJ_B(scale_fma) RJ_B(merge) RJ_I(v) RJ_I(device) RJ_I(nranks) RJ_I(rank) RJ_S(comm_file) RJ_S(sample_output) RJ_S(face_table) RJ_S(output_map) RJ_S(how) RJ_S(by) RJ_S(polygons)
+    RJ_I(seed) RJ_D(gen_t) RJ_I(gen_n) RJ_B(histo) RJ_B(profile) RJ_B(scale_fma) RJ_B(merge) RJ_I(v) RJ_I(device) RJ_I(nranks) RJ_I(rank) RJ_S(comm_file) RJ_S(sample_output) RJ_S(face_table) RJ_S(output_map) RJ_S(how) RJ_S(by) RJ_S(polygons) RJ_S(coarse_map)
 #undef RJ_S
 #undef RJ_I
 #undef RJ_D

@@ -19,6 +19,9 @@
 //   rings without those of face 0 (rj_map_rings, RJ_RINGS_SKIP_FACE0), every hole assigned to its outer ring
 //   (rj_rings_polygons).  One line per polygon: "f0 f1 area2 POLYGON ((shell), (hole), ...)" -- (f0, f1) the polygon's row
 //   of face_pairs, area2 twice its area in scaled units^2 (exact), the points unscaled ("%.6f"), every ring closed.
+//   -coarse_map <path> (ours): the map of -output_map (under -how, -by, -merge) without its degenerate pieces, taken through
+//   its rings (rj_map_rings) and back (rj_rings_map): the same faces and boundaries with maximal chains -- a chain ends
+//   only where three or more boundaries meet or the faces change -- written as -output_map writes.
 #include <iostream>
 #include <unordered_map>
 
@@ -141,6 +144,24 @@ class MapOverlayLBVH {
     }
     fclose(fp);
   }
+  // a chain map read back for its file
+  struct HostMap {
+    std::vector<int64_t> xy;
+    std::vector<uint32_t> row;
+    std::vector<int32_t> left, right;
+    int Fetch(rj_handle h, const int64_t* xy_dev, const uint32_t* row_dev, const int32_t* left_dev, const int32_t* right_dev, uint64_t n_chains,
+              uint64_t n_points) {
+      xy.resize(2 * n_points);
+      row.resize(n_chains + 1);
+      left.resize(n_chains);
+      right.resize(n_chains);
+      int rc = rj_memcpy_d2h(h, xy.data(), xy_dev, 16 * n_points);
+      if (rc == RJ_OK) rc = rj_memcpy_d2h(h, row.data(), row_dev, 4 * (n_chains + 1));
+      if (rc == RJ_OK) rc = rj_memcpy_d2h(h, left.data(), left_dev, 4 * n_chains);
+      if (rc == RJ_OK) rc = rj_memcpy_d2h(h, right.data(), right_dev, 4 * n_chains);
+      return rc;
+    }
+  };
   // the output map on the device (rj_overlay_map): a sizing call, then the arrays, which stay with the caller
   struct DeviceMap {
     rj_overlay_map_counts c{};
@@ -148,13 +169,14 @@ class MapOverlayLBVH {
     uint32_t* row = nullptr;
     int32_t *left = nullptr, *right = nullptr, *pairs = nullptr;
   };
-  DeviceMap RunOutputMap() {
+  DeviceMap RunOutputMap(uint32_t more_flags = 0) {
     rj_handle h = ctx_.handle();
     DeviceMap m;
+    const uint32_t flags = map_flags_ | more_flags;
     auto overlay_map = [&](uint64_t cc, uint64_t pc, uint64_t fc) {
-      return use_op_ ? rj_overlay_map_op(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], map_flags_, cc, pc, fc, m.xy, m.row,
+      return use_op_ ? rj_overlay_map_op(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], flags, cc, pc, fc, m.xy, m.row,
                                          m.left, m.right, m.pairs, nullptr, &m.c, how_, by_)
-                     : rj_overlay_map(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], map_flags_, cc, pc, fc, m.xy, m.row,
+                     : rj_overlay_map(h, xsects_dev_[0], xsects_dev_[1], n_xsects_, faces_[0], faces_[1], flags, cc, pc, fc, m.xy, m.row,
                                       m.left, m.right, m.pairs, nullptr, &m.c);
     };
     int rc = overlay_map(0, 0, 0);
@@ -179,24 +201,63 @@ class MapOverlayLBVH {
     rj_handle h = ctx_.handle();
     DeviceMap m = RunOutputMap();
     const rj_overlay_map_counts c = m.c;
-    om_xy_.resize(2 * c.n_points);
-    om_row_.resize(c.n_chains + 1);
-    om_left_.resize(c.n_chains);
-    om_right_.resize(c.n_chains);
-    int rc = rj_memcpy_d2h(h, om_xy_.data(), m.xy, 16 * c.n_points);
-    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_row_.data(), m.row, 4 * (c.n_chains + 1));
-    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_left_.data(), m.left, 4 * c.n_chains);
-    if (rc == RJ_OK) rc = rj_memcpy_d2h(h, om_right_.data(), m.right, 4 * c.n_chains);
+    const int rc = om_.Fetch(h, m.xy, m.row, m.left, m.right, c.n_chains, c.n_points);
     FreeMap(m);
     rj_check(h, rc, "rj_overlay_map");
     std::cerr << "Output map: " << c.n_chains << " chains, " << c.n_points << " points, " << c.n_faces << " faces" << std::endl;
+  }
+  // the output map without its degenerate pieces -> its rings, those of face 0 included (rj_map_rings) -> the map the rings
+  // bound (rj_rings_map, the faces read from the ring records in place); a sizing call before each.  The output map is
+  // computed again here even when -output_map has just computed it: that one may hold degenerate pieces and is already
+  // freed; one more rj_overlay_map call is cheap next to reading the two input files.
+  void ComputeCoarseMap() {
+    rj_handle h = ctx_.handle();
+    DeviceMap m = RunOutputMap(RJ_OVM_DROP_DEGENERATE);
+    rj_rings_counts ring_counts{};
+    rj_rings_map_counts mc{};
+    rj_ring* rings = nullptr;
+    uint32_t *ring_first = nullptr, *ring_half = nullptr, *ring_row = nullptr, *row = nullptr;
+    int64_t *ring_xy = nullptr, *xy = nullptr;
+    int32_t *left = nullptr, *right = nullptr;
+    auto free_all = [&]() {
+      FreeMap(m);
+      rj_dev_free(h, rings); rj_dev_free(h, ring_first); rj_dev_free(h, ring_half); rj_dev_free(h, ring_row); rj_dev_free(h, ring_xy);
+      rj_dev_free(h, xy); rj_dev_free(h, row); rj_dev_free(h, left); rj_dev_free(h, right);
+    };
+    auto must = [&](int rc, const char* what) {
+      if (rc != RJ_OK) free_all();
+      rj_check(h, rc, what);
+    };
+    int rc = rj_map_rings(h, m.xy, m.c.n_points, m.row, m.left, m.right, m.c.n_chains, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &ring_counts);
+    if (rc != RJ_E_OVERFLOW) must(rc, "rj_map_rings");
+    must(rj_dev_alloc(h, sizeof(rj_ring) * (ring_counts.n_rings ? ring_counts.n_rings : 1), (void**) &rings), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (ring_counts.n_rings + 1), (void**) &ring_first), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (ring_counts.n_halves ? ring_counts.n_halves : 1), (void**) &ring_half), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (ring_counts.n_rings + 1), (void**) &ring_row), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 16 * (ring_counts.n_points ? ring_counts.n_points : 1), (void**) &ring_xy), "rj_dev_alloc");
+    must(rj_map_rings(h, m.xy, m.c.n_points, m.row, m.left, m.right, m.c.n_chains, 0, ring_counts.n_rings, ring_counts.n_halves, ring_counts.n_points, rings, ring_first,
+                      ring_half, ring_row, ring_xy, &ring_counts),
+         "rj_map_rings");
+    rc = rj_rings_map(h, ring_row, ring_xy, ring_counts.n_points, rings, sizeof(rj_ring), ring_counts.n_rings, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, &mc);
+    if (rc != RJ_E_OVERFLOW) must(rc, "rj_rings_map");
+    must(rj_dev_alloc(h, 16 * (mc.n_points ? mc.n_points : 1), (void**) &xy), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (mc.n_chains + 1), (void**) &row), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (mc.n_chains ? mc.n_chains : 1), (void**) &left), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (mc.n_chains ? mc.n_chains : 1), (void**) &right), "rj_dev_alloc");
+    must(rj_rings_map(h, ring_row, ring_xy, ring_counts.n_points, rings, sizeof(rj_ring), ring_counts.n_rings, 0, mc.n_chains, mc.n_points, xy, row, left, right, &mc),
+         "rj_rings_map");
+    must(cm_.Fetch(h, xy, row, left, right, mc.n_chains, mc.n_points), "rj_memcpy_d2h");
+    const uint64_t source_chains = m.c.n_chains;
+    free_all();
+    std::cerr << "Coarse map: " << mc.n_chains << " chains (" << mc.n_closed << " closed), " << mc.n_points << " points of " << source_chains
+              << " chains; " << mc.n_conflicts << " conflicts" << std::endl;
   }
   // the polygons of the output map on the device: the map, its rings without those of face 0, the holes to their outer
   // rings (a sizing call before each); what the file needs goes to the host
   void ComputePolygons() {
     rj_handle h = ctx_.handle();
     DeviceMap m = RunOutputMap();
-    rj_rings_counts rc_{};
+    rj_rings_counts ring_counts{};
     rj_ring* rings = nullptr;
     uint32_t *ring_first = nullptr, *ring_half = nullptr, *ring_row = nullptr, *poly_first = nullptr, *poly_ring = nullptr;
     int64_t* ring_xy = nullptr;
@@ -211,39 +272,39 @@ class MapOverlayLBVH {
       rj_check(h, rc, what);
     };
     int rc = rj_map_rings(h, m.xy, m.c.n_points, m.row, m.left, m.right, m.c.n_chains, RJ_RINGS_SKIP_FACE0, 0, 0, 0, nullptr, nullptr, nullptr,
-                          nullptr, nullptr, &rc_);
+                          nullptr, nullptr, &ring_counts);
     if (rc != RJ_E_OVERFLOW) must(rc, "rj_map_rings");
-    must(rj_dev_alloc(h, sizeof(rj_ring) * (rc_.n_rings ? rc_.n_rings : 1), (void**) &rings), "rj_dev_alloc");
-    must(rj_dev_alloc(h, 4 * (rc_.n_rings + 1), (void**) &ring_first), "rj_dev_alloc");
-    must(rj_dev_alloc(h, 4 * (rc_.n_halves ? rc_.n_halves : 1), (void**) &ring_half), "rj_dev_alloc");
-    must(rj_dev_alloc(h, 4 * (rc_.n_rings + 1), (void**) &ring_row), "rj_dev_alloc");
-    must(rj_dev_alloc(h, 16 * (rc_.n_points ? rc_.n_points : 1), (void**) &ring_xy), "rj_dev_alloc");
-    must(rj_map_rings(h, m.xy, m.c.n_points, m.row, m.left, m.right, m.c.n_chains, RJ_RINGS_SKIP_FACE0, rc_.n_rings, rc_.n_halves, rc_.n_points,
-                      rings, ring_first, ring_half, ring_row, ring_xy, &rc_),
+    must(rj_dev_alloc(h, sizeof(rj_ring) * (ring_counts.n_rings ? ring_counts.n_rings : 1), (void**) &rings), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (ring_counts.n_rings + 1), (void**) &ring_first), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (ring_counts.n_halves ? ring_counts.n_halves : 1), (void**) &ring_half), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 4 * (ring_counts.n_rings + 1), (void**) &ring_row), "rj_dev_alloc");
+    must(rj_dev_alloc(h, 16 * (ring_counts.n_points ? ring_counts.n_points : 1), (void**) &ring_xy), "rj_dev_alloc");
+    must(rj_map_rings(h, m.xy, m.c.n_points, m.row, m.left, m.right, m.c.n_chains, RJ_RINGS_SKIP_FACE0, ring_counts.n_rings, ring_counts.n_halves, ring_counts.n_points,
+                      rings, ring_first, ring_half, ring_row, ring_xy, &ring_counts),
          "rj_map_rings");
     rj_polygons_counts pc{};
-    rc = rj_rings_polygons(h, rings, rc_.n_rings, ring_row, ring_xy, rc_.n_points, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, &pc);
+    rc = rj_rings_polygons(h, rings, ring_counts.n_rings, ring_row, ring_xy, ring_counts.n_points, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, &pc);
     if (rc != RJ_E_OVERFLOW) must(rc, "rj_rings_polygons");
     must(rj_dev_alloc(h, sizeof(rj_polygon) * (pc.n_polygons ? pc.n_polygons : 1), (void**) &polygons), "rj_dev_alloc");
     must(rj_dev_alloc(h, 4 * (pc.n_polygons + 1), (void**) &poly_first), "rj_dev_alloc");
     must(rj_dev_alloc(h, 4 * (pc.n_members ? pc.n_members : 1), (void**) &poly_ring), "rj_dev_alloc");
-    must(rj_rings_polygons(h, rings, rc_.n_rings, ring_row, ring_xy, rc_.n_points, 0, pc.n_polygons, pc.n_members, nullptr, polygons, poly_first,
+    must(rj_rings_polygons(h, rings, ring_counts.n_rings, ring_row, ring_xy, ring_counts.n_points, 0, pc.n_polygons, pc.n_members, nullptr, polygons, poly_first,
                            poly_ring, &pc),
          "rj_rings_polygons");
     pg_polygons_.resize(pc.n_polygons);
     pg_first_.resize(pc.n_polygons + 1);
     pg_ring_.resize(pc.n_members);
-    pg_row_.resize(rc_.n_rings + 1);
-    pg_xy_.resize(2 * rc_.n_points);
+    pg_row_.resize(ring_counts.n_rings + 1);
+    pg_xy_.resize(2 * ring_counts.n_points);
     pg_pairs_.resize(2 * m.c.n_faces);
     must(rj_memcpy_d2h(h, pg_polygons_.data(), polygons, sizeof(rj_polygon) * pc.n_polygons), "rj_memcpy_d2h");
     must(rj_memcpy_d2h(h, pg_first_.data(), poly_first, 4 * (pc.n_polygons + 1)), "rj_memcpy_d2h");
     must(rj_memcpy_d2h(h, pg_ring_.data(), poly_ring, 4 * pc.n_members), "rj_memcpy_d2h");
-    must(rj_memcpy_d2h(h, pg_row_.data(), ring_row, 4 * (rc_.n_rings + 1)), "rj_memcpy_d2h");
-    must(rj_memcpy_d2h(h, pg_xy_.data(), ring_xy, 16 * rc_.n_points), "rj_memcpy_d2h");
+    must(rj_memcpy_d2h(h, pg_row_.data(), ring_row, 4 * (ring_counts.n_rings + 1)), "rj_memcpy_d2h");
+    must(rj_memcpy_d2h(h, pg_xy_.data(), ring_xy, 16 * ring_counts.n_points), "rj_memcpy_d2h");
     must(rj_memcpy_d2h(h, pg_pairs_.data(), m.pairs, 8 * m.c.n_faces), "rj_memcpy_d2h");
     free_all();
-    std::cerr << "Polygons: " << pc.n_polygons << " polygons, " << pc.n_holes << " holes, " << pc.n_orphans << " orphans of " << rc_.n_rings
+    std::cerr << "Polygons: " << pc.n_polygons << " polygons, " << pc.n_holes << " holes, " << pc.n_orphans << " orphans of " << ring_counts.n_rings
               << " rings" << std::endl;
   }
   // one line per polygon: "f0 f1 area2 POLYGON ((shell), (hole), ...)"
@@ -280,8 +341,10 @@ class MapOverlayLBVH {
     }
     fclose(fp);
   }
-  // the device map as a CDB file: "id points first last left right", then the points
-  void WriteOutputMapFile(const char* path) const {
+  void WriteOutputMapFile(const char* path) const { WriteMapFile(path, om_); }
+  void WriteCoarseMapFile(const char* path) const { WriteMapFile(path, cm_); }
+  // a device map as a CDB file: "id points first last left right", then the points
+  void WriteMapFile(const char* path, const HostMap& hm) const {
     FILE* fp = fopen(path, "w");
     if (!fp) throw std::runtime_error(std::string("Cannot open ") + path);
     const Scaling& sc = ctx_.get_scaling();
@@ -292,13 +355,13 @@ class MapOverlayLBVH {
     };
     std::unordered_map<std::pair<int64_t, int64_t>, uint32_t, Hash> ids;
     auto id_of = [&](uint32_t p) {
-      return ids.emplace(std::make_pair(om_xy_[2 * (size_t) p], om_xy_[2 * (size_t) p + 1]), (uint32_t) ids.size()).first->second;
+      return ids.emplace(std::make_pair(hm.xy[2 * (size_t) p], hm.xy[2 * (size_t) p + 1]), (uint32_t) ids.size()).first->second;
     };
-    for (size_t i = 0; i + 1 < om_row_.size(); i++) {
-      const uint32_t b = om_row_[i], e = om_row_[i + 1];
+    for (size_t i = 0; i + 1 < hm.row.size(); i++) {
+      const uint32_t b = hm.row[i], e = hm.row[i + 1];
       const uint32_t first = id_of(b), last = id_of(e - 1);
-      fprintf(fp, "%zu %u %u %u %d %d\n", i + 1, e - b, first, last, om_left_[i], om_right_[i]);
-      for (uint32_t p = b; p < e; p++) fprintf(fp, "%.6f %.6f\n", sc.UnscaleX(om_xy_[2 * (size_t) p]), sc.UnscaleY(om_xy_[2 * (size_t) p + 1]));
+      fprintf(fp, "%zu %u %u %u %d %d\n", i + 1, e - b, first, last, hm.left[i], hm.right[i]);
+      for (uint32_t p = b; p < e; p++) fprintf(fp, "%.6f %.6f\n", sc.UnscaleX(hm.xy[2 * (size_t) p]), sc.UnscaleY(hm.xy[2 * (size_t) p + 1]));
     }
     fclose(fp);
   }
@@ -357,9 +420,7 @@ class MapOverlayLBVH {
   size_t cap_ = 0, n_xsects_ = 0;
   rj_xsect* xsects_dev_[2] = {nullptr, nullptr};
   std::vector<rj_overlay_face> face_rows_;
-  std::vector<int64_t> om_xy_;  // the device output map on the host (-output_map)
-  std::vector<uint32_t> om_row_;
-  std::vector<int32_t> om_left_, om_right_;
+  HostMap om_, cm_;  // the device output map on the host (-output_map), and the map of its rings (-coarse_map)
   std::vector<rj_polygon> pg_polygons_;  // the polygons on the host (-polygons), with the rings' points and the map's face pairs
   std::vector<uint32_t> pg_first_, pg_ring_, pg_row_;
   std::vector<int64_t> pg_xy_;
@@ -379,7 +440,7 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
   auto g2 = load_from(f.poly2, f.serialize, f.v);
   tm.next("Create App");
   Context ctx({g1, g2}, f.device, f.scale_fma);
-  MapOverlayLBVH overlay(ctx, f.xsect_factor, f.mode == "grid", f.grid_size, !f.face_table.empty() || !f.output_map.empty() || !f.polygons.empty());
+  MapOverlayLBVH overlay(ctx, f.xsect_factor, f.mode == "grid", f.grid_size, !f.face_table.empty() || !f.output_map.empty() || !f.polygons.empty() || !f.coarse_map.empty());
   overlay.SetOperation(f.how, f.by);
   overlay.SetMerge(f.merge);
   tm.next("Load Data");
@@ -408,6 +469,10 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
     tm.next("Compute polygons");
     overlay.ComputePolygons();
   }
+  if (!f.coarse_map.empty()) {
+    tm.next("Compute coarse map");
+    overlay.ComputeCoarseMap();
+  }
   if (f.check && f.mode != "grid") {  // run_overlay.cu:199-204: compare with -mode=grid
     tm.next("Check result");
     if (!overlay.CheckAgainstGrid(f.grid_size)) throw std::runtime_error("result differs from -mode=grid");
@@ -428,6 +493,10 @@ void RunOverlay(const Flags& f) {  // run_overlay.cu:143-228
     tm.next("Write polygons");
     overlay.WritePolygons(f.polygons.c_str());
   }
+  if (!f.coarse_map.empty()) {
+    tm.next("Write coarse map");
+    overlay.WriteCoarseMapFile(f.coarse_map.c_str());
+  }
   tm.end();
 }
 
@@ -438,7 +507,7 @@ int main(int argc, char* argv[]) {
     std::cerr << "Usage: " << argv[0] << " -poly1 <map0.cdb> -poly2 <map1.cdb> -mode lbvh|grid [-grid_size 2048] [-output <result.cdb>]\n"
               << "  [-serialize <dir>] [-xsect_factor 0.2] [-check] [-device 0] [-v 1]\n"
               << "  [-face_table <rows.txt>] [-output_map <map.cdb>] [-how intersection|union|difference|symmetric_difference|identity]\n"
-              << "  [-by pair|map0|map1] [-merge] [-polygons <polygons.txt>]\n";
+              << "  [-by pair|map0|map1] [-merge] [-polygons <polygons.txt>] [-coarse_map <map.cdb>]\n";
     return 1;
   }
   Flags f;

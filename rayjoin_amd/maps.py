@@ -306,6 +306,28 @@ class ScaledMap:
         return [(int(cuts[i]), int(cuts[i + 1])) for i in range(n)]
 
 
+def rings_of_polygons(polygons):
+    """Polygons -> the labelled rings that ops.rings_map takes: an iterable of (face, shell_points, [hole_points, ...]) in
+    scaled integers (what ops.DevicePolygons.polygons() returns, minus its area field; a closing point equal to the first is
+    not needed and not removed: it gives a zero-length edge that rj_rings_map drops) -> (ring_row uint32 [n_rings + 1],
+    ring_xy int64 [n_points, 2], ring_face int32 [n_rings]).  Every ring gets its face on the left of its walk: shells are
+    turned counter-clockwise, holes clockwise, by the exact sign of the shoelace sum in Python integers.  ValueError for a
+    shell or a hole of area 0: it has no orientation."""
+    row, pts, faces = [0], [], []
+    for k, (face, shell, holes) in enumerate(polygons):
+        for j, ring in enumerate([shell] + list(holes)):
+            p = [(int(x), int(y)) for x, y in np.asarray(ring).reshape(-1, 2).tolist()]
+            area2 = sum(a[0] * b[1] - a[1] * b[0] for a, b in zip(p, p[1:] + p[:1]))
+            if area2 == 0:
+                raise ValueError("polygon %d: %s has area 0" % (k, "the shell" if j == 0 else "hole %d" % (j - 1)))
+            if (area2 > 0) != (j == 0):
+                p.reverse()
+            pts += p
+            row.append(len(pts))
+            faces.append(int(face))
+    return np.array(row, np.uint32), np.array(pts, np.int64).reshape(-1, 2), np.array(faces, np.int32)
+
+
 class Context:
     """src/context.h:31-88: owns the (up to) two planar graphs, the joint bbox and the scaling."""
 

@@ -18,6 +18,9 @@
   face_rings(handle, ...) / DeviceOutputMap.Rings(handle) / DeviceContext.Rings(im) -> DeviceRings; .polygons()
       -- the closed boundaries of a chain map's faces, stitched on the device (rj_map_rings): what a consumer of an
          output map needs to draw or export a face
+  rings_map(handle, ...) / DeviceRings.Map(handle) -> DeviceChainMap; .to_host(); .Rings(handle)
+      -- the way back (rj_rings_map): labelled rings, the user's polygons (maps.rings_of_polygons) or the library's own
+         DeviceRings, become a chain map with maximal chains that DeviceContext.InstallMap takes
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -51,7 +54,8 @@ class DeviceContext:
         return self
 
     def InstallMap(self, im, output_map):
-        """An ops.DeviceOutputMap (MapOverlay.OutputMap(drop_degenerate=True)) becomes map `im` of this context without
+        """An ops.DeviceOutputMap (MapOverlay.OutputMap(drop_degenerate=True)) or an ops.DeviceChainMap (rings_map, DeviceRings.Map)
+        becomes map `im` of this context without
         leaving the GPU (rj_upload_map_dev), so that another MapOverlay can run: (A x B) x C.  The output map's faces
         are the new map's faces.  Its coordinates are scaled integers: the caller is responsible for ONE Scaling over
         all layers -- this context's Scaling must be the one the output map was computed under, and the other map of
@@ -451,10 +455,71 @@ class DeviceRings:
             raise
         return DevicePolygons(*bufs, self.n_rings, counts)
 
+    def Map(self, handle, dissolve=False):
+        """The chain map that these rings bound as a DeviceChainMap (rings_map): chains as long as the faces allow, whatever
+        pieces the map they came from was cut into.  Reads the faces of the ring records in place.  Needs the points."""
+        if self.ring_xy is None:
+            raise RuntimeError("DeviceRings.Map needs the points (points=True)")
+        return rings_map(handle, self.ring_row, self.ring_xy, self.n_points, self.rings, self.n_rings, face_stride=_capi.RING_DTYPE.itemsize,
+                         dissolve=dissolve)
+
     def free(self):
         for b in (self.rings, self.ring_first, self.ring_half, self.ring_row, self.ring_xy):
             if b is not None:
                 b.free()
+
+
+def rings_map(handle, ring_row, ring_xy, n_points, ring_face, n_rings, face_stride=4, dissolve=False, capacities=None):
+    """The chain map that labelled rings bound (rj_rings_map, the inverse of face_rings) as a DeviceChainMap: ring_row (uint32
+    CSR, n_rings + 1), ring_xy (int64 x,y pairs, scaled units) and ring_face in device memory; the face of ring r is the
+    int32 at byte r * face_stride of ring_face (4: a plain int32 array, 32: RING_DTYPE records in place) and lies on the left
+    of the ring's walk (shells counter-clockwise, holes clockwise: maps.rings_of_polygons).  dissolve (RJ_RMAP_DISSOLVE)
+    leaves out every edge with the same face on both sides.  capacities = (chains, points): RingsMapOverflow with the
+    true counts when one is too small; left open, a sizing call finds them."""
+    flags = _capi.RJ_RMAP_DISSOLVE if dissolve else 0
+    args = (ring_row, ring_xy, n_points, ring_face, face_stride, n_rings, flags)
+    if capacities is None:
+        try:
+            c = handle.rings_map(*args, (0, 0), None, None, None, None)
+        except _capi.RingsMapOverflow as e:
+            c = e.counts
+        capacities = (c["n_chains"], c["n_points"])
+    cc, pc = (int(v) for v in capacities)
+    bufs = [handle.alloc(16 * max(1, pc)), handle.alloc(4 * (cc + 1)), handle.alloc(4 * max(1, cc)), handle.alloc(4 * max(1, cc))]
+    try:
+        counts = handle.rings_map(*args, (cc, pc), *bufs)
+    except _capi.RayJoinError:
+        for b in bufs:
+            b.free()
+        raise
+    return DeviceChainMap(*bufs, counts)
+
+
+class DeviceChainMap:
+    """The chain map of a set of labelled rings in device memory (rj_rings_map): xy (int64 x,y pairs, scaled units),
+    row_index (uint32, n_chains + 1), left / right (int32 faces) as DeviceBuffers -- the arrays rj_upload_map_dev takes, so
+    DeviceContext.InstallMap takes it as it takes a DeviceOutputMap -- and the counts n_chains, n_points, n_edges, n_closed,
+    n_zero_edges, n_conflicts, n_dissolved."""
+
+    def __init__(self, xy, row_index, left, right, counts):
+        self.xy, self.row_index, self.left, self.right = xy, row_index, left, right
+        self.counts = dict(counts)
+        self.n_chains, self.n_points = int(counts["n_chains"]), int(counts["n_points"])
+
+    def to_host(self):
+        """-> (maps.ScaledMap of the map, the counts)"""
+        from .maps import ScaledMap
+        m = ScaledMap(0, self.xy.to_host(np.int64, 2 * self.n_points).reshape(-1, 2), self.row_index.to_host(np.uint32, self.n_chains + 1),
+                      self.left.to_host(np.int32, self.n_chains).astype(np.int64), self.right.to_host(np.int32, self.n_chains).astype(np.int64))
+        return m, dict(self.counts)
+
+    def Rings(self, handle, **kw):
+        """face_rings of this map, on the device"""
+        return face_rings(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, **kw)
+
+    def free(self):
+        for b in (self.xy, self.row_index, self.left, self.right):
+            b.free()
 
 
 class DevicePolygons:
