@@ -513,6 +513,60 @@ int rj_rings_map(rj_handle h, const uint32_t* ring_row_dev, const int64_t* ring_
                  int64_t* xy_dev, uint32_t* row_index_dev, int32_t* left_dev, int32_t* right_dev,
                  rj_rings_map_counts* counts);
 
+/* ---- crossings inside one map --------------------------------------------------------------- */
+/* rj_crossing kinds */
+#define RJ_CROSS_PROPER 1u  /* the segments cross in a point that is an end point of neither */
+#define RJ_CROSS_TOUCH 2u   /* an end point of one edge lies inside the other edge */
+#define RJ_CROSS_OVERLAP 3u /* collinear, more than one point in common, the end-point sets differ */
+#define RJ_CROSS_EQUAL 4u   /* the same two end points, in either direction (a chain that folds back a -> b -> a) */
+
+typedef struct {
+  uint32_t eid[2]; /* eid[0] < eid[1] */
+  uint32_t kind;   /* RJ_CROSS_* */
+  uint32_t _pad;
+} rj_crossing; /* 16 bytes */
+
+typedef struct {
+  uint64_t n_found, n_proper, n_touch, n_overlap, n_equal, n_edges, n_zero_edges;
+} rj_crossings_counts;
+
+/* extends: the check that a chain map is a planar subdivision, which every stage of the library assumes and none makes
+ * (the reference never validates a map either: Map::LoadFrom, src/map/map.h:162-233) -- all pairs of edges of ONE map
+ * that meet anywhere except in a shared end point, exactly, on the device, from a map in device memory: before
+ * rj_upload_map* of user polygons (self-crossing rings, overlapping polygons of one layer, a vertex inside a
+ * neighbour's edge), or between two overlays on rj_overlay_map's output.  rj_lsi_query cannot do this: it refuses
+ * base == query, and its simulation-of-simplicity predicate reports shared vertices.
+ * Input: xy_dev[2 np], row_index_dev[nc + 1], the contract of rj_map_rings (a chain may have a single point; faces are
+ * not needed).  Edge e = p - c joins points p and p + 1 of chain c (the numbering of every other call);
+ * ne = np - nc < 2^32 - 1.  An edge whose two points are equal is skipped and counted in n_zero_edges.  The definition,
+ * in full in rayjoin_amd/csrc/rj_crossings.h: for two distinct non-zero edges e < f let S be the intersection of their
+ * closed segments.  S empty, or one point that is an end point of both (consecutive edges of a chain, a junction): no
+ * record.  One point that is an end point of exactly one: RJ_CROSS_TOUCH; of neither: RJ_CROSS_PROPER.  More than one
+ * point: RJ_CROSS_EQUAL when the end-point sets match, else RJ_CROSS_OVERLAP.  Decided from four orientation signs
+ * (int128 cross products) and coordinate comparisons: no floating point, no division, no simulation of simplicity.
+ * Output: out_dev[capacity], caller-owned device memory: one record per unordered pair with a kind, every pair exactly
+ * once, ascending by ((uint64_t) eid[0] << 32) | eid[1] -- fully determined, independent of every tuning choice (the
+ * candidates come from a sparse uniform grid of the map's own, whose cell size is chosen from the edges' extents).
+ * counts: n_found = n_proper + n_touch + n_overlap + n_equal, n_edges = ne.  flags must be 0.  RJ_E_OVERFLOW when
+ * n_found > capacity: *counts holds the true counts, nothing beyond capacity is written and the contents of out_dev
+ * are unspecified; capacity 0 (out_dev may be NULL) is the sizing call.  nc == 0 and ne == 0 are valid.  RJ_E_INVALID
+ * for a row_index that does not start at 0, does not ascend or does not end at np, a coordinate outside
+ * [-2^46, 2^46), an unknown flag -- and for a map whose grid would need more than 2^36 pair tests (a few edges as long
+ * as the map over millions of short ones: minutes of a device that may be shared): the message names the largest
+ * cell and nothing is tested.  Runs on the handle's stream with four host syncs (the sums behind the grid's size, the
+ * number of pair tests, the number of records, the end): a check made once per map, not a step of a pipeline.  Scratch
+ * (48 bytes per edge, 33 per registration -- at most 4 ne + 1024 of them --, 24 per record up to capacity, plus the
+ * sorts' temporary storage) is allocated per call and freed; no map, index or option of the handle changes.
+ * For tests and tools, through rj_set_debug_option (0: the default; none can change a result): "cross_shift" 15..47
+ * forces the grid's shift, "cross_pair_budget" lowers the 2^36, "cross_extent_factor" / "cross_reg_factor" replace the 8
+ * and 4 of the choice of the shift (a cell is 8 mean edge extents wide; at most 4 ne + 1024 registrations).  What the
+ * last call chose and took, through rj_get_option: "cross_last_shift", "cross_last_registrations",
+ * "cross_last_largest_cell" (its edges), "cross_last_pair_tests", "cross_last_items", "cross_last_us0" .. "cross_last_us5"
+ * (HIP-event microseconds of the stages: edges and sums, registrations and their sort, runs and work items, the pair
+ * pass, the sort of the hits, all; -1: not reached). */
+int rj_map_crossings(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc,
+                     uint32_t flags, uint64_t capacity, rj_crossing* out_dev, rj_crossings_counts* counts);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

@@ -25,6 +25,7 @@ RJ_RINGS_SKIP_FACE0 = 1  # rj_map_rings flags
 RJ_RINGS_NO_POINTS = 2
 RJ_RING_MIXED = 1  # rj_ring flags
 RJ_RMAP_DISSOLVE = 1  # rj_rings_map flags
+RJ_CROSS_PROPER, RJ_CROSS_TOUCH, RJ_CROSS_OVERLAP, RJ_CROSS_EQUAL = 1, 2, 3, 4  # rj_crossing kinds
 RJ_T_BUILD, RJ_T_LSI_KERNEL, RJ_T_PIP_KERNEL, RJ_T_LSI_POINTS, RJ_T_SORT, RJ_T_ORDER = 0, 1, 2, 3, 4, 5
 RJ_T_BUILD_KEYS, RJ_T_BUILD_SORT, RJ_T_BUILD_LEAVES, RJ_T_BUILD_LEVELS, RJ_T_PIP_WALK, RJ_T_BUILD_RUNS = 6, 7, 8, 9, 10, 11
 MISS_EID = 0xFFFFFFFF
@@ -42,6 +43,9 @@ RJ_POLY_NONE = 0xFFFFFFFF  # rj_rings_polygons' parent of a ring of face 0 and o
 POLYGON_DTYPE = np.dtype([("face", "<i4"), ("shell", "<u4"), ("n_holes", "<u4"), ("_pad", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
 POLYGONS_COUNTS = ("n_polygons", "n_members", "n_holes", "n_orphans", "n_face0")
 RINGS_MAP_COUNTS = ("n_chains", "n_points", "n_edges", "n_closed", "n_zero_edges", "n_conflicts", "n_dissolved")
+# rj_crossing: two edges of one map that meet elsewhere than in a shared end point (eid[0] < eid[1]), and how (RJ_CROSS_*)
+CROSSING_DTYPE = np.dtype([("eid", "<u4", (2,)), ("kind", "<u4"), ("_pad", "<u4")])
+CROSSINGS_COUNTS = ("n_found", "n_proper", "n_touch", "n_overlap", "n_equal", "n_edges", "n_zero_edges")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
 _vp, _u64, _i64, _int = C.c_void_p, C.c_uint64, C.c_int64, C.c_int
@@ -92,6 +96,7 @@ SYMBOLS = {
     "rj_map_rings": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rj_rings_polygons": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "rj_rings_map": (_int, [_vp, _vp, _vp, _u64, _vp, _u64, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "rj_map_crossings": (_int, [_vp, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -184,6 +189,15 @@ class PolygonsOverflow(RayJoinError):
 
 class RingsMapOverflow(RayJoinError):
     """RJ_E_OVERFLOW of rj_rings_map: counts = dict(n_chains, n_points, n_edges, n_closed, n_zero_edges, n_conflicts, n_dissolved),
+    the true counts"""
+
+    def __init__(self, msg, counts):
+        super().__init__(RJ_E_OVERFLOW, msg)
+        self.counts = counts
+
+
+class CrossingsOverflow(RayJoinError):
+    """RJ_E_OVERFLOW of rj_map_crossings: counts = dict(n_found, n_proper, n_touch, n_overlap, n_equal, n_edges, n_zero_edges),
     the true counts"""
 
     def __init__(self, msg, counts):
@@ -551,6 +565,19 @@ class Handle:
         named = dict(zip(RINGS_MAP_COUNTS, (int(v) for v in counts)))
         if rc == RJ_E_OVERFLOW:
             raise RingsMapOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        self._check(rc)
+        return named
+
+    def map_crossings(self, xy_dev, n_points, row_index_dev, n_chains, capacity, out_dev, flags=0):
+        """rj_map_crossings of a chain map in device memory into the caller's device array of `capacity` rj_crossing records
+        (capacity 0, out_dev None: the sizing call).  Returns the counts as a dict (CROSSINGS_COUNTS); CrossingsOverflow (with
+        the true counts) past the capacity."""
+        counts = (_u64 * 7)()
+        rc = self.L.rj_map_crossings(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains), int(flags), int(capacity), _ptr(out_dev),
+                                     counts)
+        named = dict(zip(CROSSINGS_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise CrossingsOverflow(self.L.rj_last_error_string(self.h).decode(), named)
         self._check(rc)
         return named
 

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/rayjoin_amd.h"
+#include "rj_crossings.h"
 #include "rj_kernels.h"
 #include "rj_overlay_dev.h"
 #include "rj_overlay_ops.h"
@@ -267,6 +268,9 @@ struct rj_handle_s {
   int debug_run_cap = 0;     // experiments: edges per polyline run (0: by the mean chain length)
   int debug_pack_solo = 0;   // experiments: a run longer than this never shares its leaf (0: the default, 48)
   int debug_pack_spread = 0; // experiments: how many times larger than its runs a shared leaf may be (0: the default, 8)
+  // rj_map_crossings: 0 = choose / the default (tests force a shift and lower the budget; tools vary the two factors)
+  int debug_cross_shift = 0, debug_cross_pair_budget = 0, debug_cross_extent_factor = 0, debug_cross_reg_factor = 0;
+  CrossingsReport cross_report = {};  // what the last rj_map_crossings chose and took (reports only)
   uint32_t stitch_stats[4] = {0, 0, 0, 0};  // the last run cutting: ranking rounds, incidences on closed loops, rounds of the second ranking, closed chains
   char* strip_scratch = nullptr;  // grow-only temporaries of the column index's build
   size_t strip_scratch_bytes = 0;
@@ -612,6 +616,10 @@ const Option kOptions[] = {
     {"run_cap", true, &rj_handle_s::debug_run_cap, 2, 64, "run_cap: 0 or 2..64", nullptr, nullptr, 1, {0}},  // edges per polyline run of the next first build of a map (0: 64)
     {"pack_solo", true, &rj_handle_s::debug_pack_solo, 0, 64},  // a run longer than this never shares its leaf (0: 48)
     {"pack_spread", true, &rj_handle_s::debug_pack_spread, 0, 1000000},  // a shared leaf may be this many times as large as its runs (0: 8)
+    {"cross_shift", true, &rj_handle_s::debug_cross_shift, 15, 47, "cross_shift: 0 (choose) or 15..47", nullptr, nullptr, 1, {0}},  // rj_map_crossings: the grid's shift
+    {"cross_pair_budget", true, &rj_handle_s::debug_cross_pair_budget, 0, 1 << 30},  // ... pair tests it refuses above (0: 2^36)
+    {"cross_extent_factor", true, &rj_handle_s::debug_cross_extent_factor, 0, 1 << 20},  // ... a cell is this many mean extents wide (0: 8)
+    {"cross_reg_factor", true, &rj_handle_s::debug_cross_reg_factor, 0, 1 << 20},  // ... registrations per edge allowed (0: 4)
 };
 
 const Option* find_option(const char* name, bool debug) {
@@ -679,6 +687,12 @@ const Report kReports[] = {
     {"closed_chains", 2, RJ_READ(h->map[k].closed_chains)},
     {"stitch_rounds", 0, RJ_READ(h->stitch_stats[0])},     // the last run cutting: pointer-jumping rounds that had work
     {"stitch_loop_ends", 0, RJ_READ(h->stitch_stats[1])},  // ... chain ends on closed loops of paired chains
+    {"cross_last_shift", 0, RJ_READ(h->cross_report.shift)},  // the last rj_map_crossings: its grid, its work, its stages
+    {"cross_last_registrations", 0, RJ_READ(h->cross_report.registrations)},
+    {"cross_last_largest_cell", 0, RJ_READ(h->cross_report.largest_run)},
+    {"cross_last_pair_tests", 0, RJ_READ(h->cross_report.pair_tests)},
+    {"cross_last_items", 0, RJ_READ(h->cross_report.n_items)},
+    {"cross_last_us", 6, RJ_READ(h->cross_report.ms[k] < 0 ? -1 : (int64_t) (h->cross_report.ms[k] * 1000.0f))},  // edges and sums, registrations and sort, runs, pairs, hits, all
     {"comm_ranks", 0, read_comm_ranks},
     {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
     {"pip_share_blocks", 0, RJ_READ(h->last_pip_share ? h->last_pip_share : h->pip_share_blocks())},
@@ -761,7 +775,8 @@ int rj_create(int device_id, rj_handle* out) {
   // that would otherwise land in the first upload, the first index build and the first query)
   ok = ok && warm_query_kernels(h->stream) == hipSuccess && warm_grid_kernels(h->stream) == hipSuccess &&
        warm_stitch_kernels(h->stream) == hipSuccess && warm_strip_kernels(h->stream) == hipSuccess &&
-       warm_overlay_kernels(h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
+       warm_overlay_kernels(h->stream) == hipSuccess && warm_crossings_kernels(h->stream) == hipSuccess &&
+       hipStreamSynchronize(h->stream) == hipSuccess;
   if (!ok) { delete h; return RJ_E_HIP; }
   *out = h;
   return RJ_OK;
@@ -2804,6 +2819,47 @@ int rj_rings_map(rj_handle h, const uint32_t* ring_row_dev, const int64_t* ring_
   if (counts->n_chains > chain_capacity || counts->n_points > point_capacity)
     return fail(h, RJ_E_OVERFLOW, "rj_rings_map: %llu chains, %llu points; capacities %llu, %llu", (unsigned long long) counts->n_chains,
                 (unsigned long long) counts->n_points, (unsigned long long) chain_capacity, (unsigned long long) point_capacity);
+  return RJ_OK;
+}
+
+int rj_map_crossings(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc, uint32_t flags, uint64_t capacity,
+                     rj_crossing* out_dev, rj_crossings_counts* counts) {
+  static_assert(sizeof(rj_crossing) == 16 && sizeof(rj_crossings_counts) == sizeof(crossings::Counts), "layouts");
+  static_assert(RJ_CROSS_PROPER == crossings::kProper && RJ_CROSS_TOUCH == crossings::kTouch && RJ_CROSS_OVERLAP == crossings::kOverlap &&
+                    RJ_CROSS_EQUAL == crossings::kEqual,
+                "kinds");
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_map_crossings: counts is null");
+  memset(counts, 0, sizeof(*counts));
+  if (flags) return fail(h, RJ_E_INVALID, "rj_map_crossings: unknown flags 0x%x", flags);
+  if ((np && !xy_dev) || (nc && !row_index_dev)) return fail(h, RJ_E_INVALID, "rj_map_crossings: null input array");
+  if (np >= (1ull << 32) || nc > np || np - nc >= 0xFFFFFFFFull) return fail(h, RJ_E_INVALID, "rj_map_crossings: nc <= np < 2^32 and np - nc < 2^32 - 1");
+  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_crossings: points without chains");
+  if (capacity && !out_dev) return fail(h, RJ_E_INVALID, "rj_map_crossings: null output");
+  if (int r = set_device(h)) return r;
+  h->cross_report = CrossingsReport{};
+  if (nc == 0) return RJ_OK;
+  const CrossingsTuning tuning{h->debug_cross_shift, h->debug_cross_pair_budget ? (uint64_t) h->debug_cross_pair_budget : crossings::kPairBudget,
+                               h->debug_cross_extent_factor ? (uint64_t) h->debug_cross_extent_factor : crossings::kExtentFactor,
+                               h->debug_cross_reg_factor ? (uint64_t) h->debug_cross_reg_factor : crossings::kRegFactor};
+  crossings::Meta m;
+  RJ_HIP(h, map_crossings_device(h->stream, xy_dev, np, row_index_dev, nc, capacity, out_dev, tuning, &m, &h->cross_report));
+  if (m.bad == crossings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_crossings: row_index must start at 0");
+  if (m.bad == crossings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_crossings: row_index must end at np");
+  if (m.bad == crossings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_crossings: row_index must ascend (a chain has no point)");
+  if (m.bad) return fail(h, RJ_E_INVALID, "rj_map_crossings: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  memcpy(counts, &m.counts, sizeof(*counts));
+  const CrossingsReport& rep = h->cross_report;
+  if (rep.over_budget && !rep.pair_tests)
+    return fail(h, RJ_E_INVALID, "rj_map_crossings: the forced cross_shift %d gives 2^37 registrations or more", rep.shift);
+  if (rep.over_budget)
+    return fail(h, RJ_E_INVALID,
+                "rj_map_crossings: %llu pair tests%s exceed the budget of %llu (grid shift %d); the largest cell (%llu, %llu) holds %llu edges: "
+                "a few edges as long as the map over many short ones",
+                (unsigned long long) rep.pair_tests, rep.pair_tests >= crossings::kClamp ? " or more" : "", (unsigned long long) tuning.pair_budget, rep.shift,
+                (unsigned long long) (rep.largest_cell & 0xFFFFFFFFull), (unsigned long long) (rep.largest_cell >> 32), (unsigned long long) rep.largest_run);
+  if (counts->n_found > capacity)
+    return fail(h, RJ_E_OVERFLOW, "rj_map_crossings: %llu crossings; capacity %llu", (unsigned long long) counts->n_found, (unsigned long long) capacity);
   return RJ_OK;
 }
 

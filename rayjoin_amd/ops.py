@@ -21,6 +21,11 @@
   rings_map(handle, ...) / DeviceRings.Map(handle) -> DeviceChainMap; .to_host(); .Rings(handle)
       -- the way back (rj_rings_map): labelled rings, the user's polygons (maps.rings_of_polygons) or the library's own
          DeviceRings, become a chain map with maximal chains that DeviceContext.InstallMap takes
+  map_crossings(handle, ...) / DeviceOutputMap.Crossings(handle) / DeviceChainMap.Crossings(handle) /
+      DeviceContext.Crossings(im) -> (records, counts)
+      -- the check that a chain map is a planar subdivision (rj_map_crossings): every pair of edges of ONE map that
+         meets elsewhere than in a shared end point, exactly, on the device -- before InstallMap of user polygons,
+         between two overlays.  The reference never validates a map (src/map/map.h:162-233)
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -96,6 +101,19 @@ class DeviceContext:
                 h.alloc(4 * max(1, m.n_chains)).from_host(np.ascontiguousarray(m.right, dtype=np.int32))]
         try:
             return face_rings(h, bufs[0], m.n_points, bufs[1], bufs[2], bufs[3], m.n_chains, **kw)
+        finally:
+            for b in bufs:
+                b.free()
+
+    def Crossings(self, im, **kw):
+        """map_crossings of input map `im` (its host image goes to temporaries on the device): empty when the map is a
+        planar subdivision"""
+        m = self.get_map(im)
+        h = self.handle
+        bufs = [h.alloc(16 * max(1, m.n_points)).from_host(np.ascontiguousarray(m.pts, dtype=np.int64)),
+                h.alloc(4 * (m.n_chains + 1)).from_host(np.ascontiguousarray(m.row_index, dtype=np.uint32))]
+        try:
+            return map_crossings(h, bufs[0], m.n_points, bufs[1], m.n_chains, **kw)
         finally:
             for b in bufs:
                 b.free()
@@ -363,9 +381,38 @@ class DeviceOutputMap:
         """face_rings of this map: the closed boundaries of its faces (face k is row k - 1 of FaceTable()), on the device"""
         return face_rings(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, **kw)
 
+    def Crossings(self, handle, **kw):
+        """map_crossings of this map, on the device: does it still have no crossings (its cut points are truncated to integers)"""
+        return map_crossings(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
+
     def free(self):
         for b in (self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin):
             b.free()
+
+
+def map_crossings(handle, xy, n_points, row_index, n_chains, capacity=None):
+    """The crossings inside one chain map in device memory (rj_map_crossings; xy int64 pairs, row_index uint32 as
+    rj_upload_map_dev takes them; a chain may have a single point) -> (records, counts) on the host: records a
+    CROSSING_DTYPE array, one per pair of edges that meets elsewhere than in a shared end point (eid[0] < eid[1], kind
+    RJ_CROSS_PROPER / TOUCH / OVERLAP / EQUAL), ascending by (eid[0], eid[1]); counts a dict (CROSSINGS_COUNTS).  No
+    record: the map is a planar subdivision.  capacity: CrossingsOverflow with the true counts when it is too small;
+    left open, a sizing call finds it."""
+    args = (xy, n_points, row_index, n_chains)
+    if capacity is None:
+        try:
+            c = handle.map_crossings(*args, 0, None)
+        except _capi.CrossingsOverflow as e:
+            c = e.counts
+        if c["n_found"] == 0:
+            return np.zeros(0, _capi.CROSSING_DTYPE), c
+        capacity = c["n_found"]
+    capacity = int(capacity)
+    buf = handle.alloc(_capi.CROSSING_DTYPE.itemsize * max(1, capacity))
+    try:
+        counts = handle.map_crossings(*args, capacity, buf)
+        return buf.to_host(_capi.CROSSING_DTYPE, counts["n_found"]), counts
+    finally:
+        buf.free()
 
 
 def face_rings(handle, xy, n_points, row_index, left, right, n_chains, skip_face0=False, points=True, capacities=None):
@@ -516,6 +563,10 @@ class DeviceChainMap:
     def Rings(self, handle, **kw):
         """face_rings of this map, on the device"""
         return face_rings(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, **kw)
+
+    def Crossings(self, handle, **kw):
+        """map_crossings of this map, on the device: overlapping or self-crossing polygons show here"""
+        return map_crossings(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
 
     def free(self):
         for b in (self.xy, self.row_index, self.left, self.right):
