@@ -567,6 +567,48 @@ typedef struct {
 int rj_map_crossings(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc,
                      uint32_t flags, uint64_t capacity, rj_crossing* out_dev, rj_crossings_counts* counts);
 
+/* ---- noding: cut edges at the vertices that touch them ------------------------------------------ */
+#define RJ_NODE_DROP_LAST 1u /* every chain is written without its last point: the ring layout rj_rings_map takes */
+
+typedef struct {
+  uint64_t n_points, n_edges;   /* of the output; n_edges = ne + n_cuts in either layout */
+  uint64_t n_cuts, n_cut_edges, n_max_cuts; /* inserted points; input edges with a cut; the most on one edge */
+  uint64_t n_used, n_proper, n_equal;       /* records of kind TOUCH or OVERLAP; PROPER and EQUAL records, which cut nothing */
+} rj_node_counts;
+
+/* extends: the repair behind rj_map_crossings' answer where it can be made exactly -- T-junctions and half-shared
+ * borders (RJ_CROSS_TOUCH, RJ_CROSS_OVERLAP: one polygon has a vertex on a border that its neighbour's ring runs
+ * straight past), the commonest reason a polygon layer is no planar subdivision.  Every point to insert is already a
+ * vertex of the map; behind the call overlapping edges are equal edges, which rj_rings_map stores once.
+ * RJ_CROSS_PROPER records are counted (n_proper) and left alone: their point is no integer.  RJ_CROSS_EQUAL needs no cut.
+ * Input: the map as rj_map_crossings takes it, and cross_dev[n_cross], the records rj_map_crossings wrote for this very
+ * map (device memory).  The definition, in full in rayjoin_amd/csrc/rj_node.h: edge e = p - c runs from a (point p) to
+ * b (point p + 1); a point q lies inside e when e is not of zero length, orient(a, b, q) == 0 (an int128 cross product),
+ * q is in e's closed box and is neither a nor b.  The cut set C(e): the distinct points q such that some record (e, f)
+ * or (f, e) of kind TOUCH or OVERLAP exists, q is an end point of f and q lies inside e -- tested for all four (end
+ * point, other edge) combinations of every such record, so a record whose kind does not fit the geometry cannot put a
+ * point off an edge.
+ * Output, caller-owned device memory: out_xy_dev[2 point_capacity], out_row_index_dev[nc + 1]: every chain keeps its
+ * points in order, and after point p come the points of C(p - c), ascending by their distance from a (|q.x - a.x|, or
+ * |q.y - a.y| on a vertical edge), equal points once.  Chains, their number and their order do not change: the
+ * caller's left / right arrays stay valid.  edge_origin_dev[n_edges] (may be NULL): the input edge that output edge
+ * p' - c is a part of.  Under RJ_NODE_DROP_LAST every chain must have at least 2 points and its first point must equal
+ * its last; every chain is then written without its last point -- rj_rings_map's ring layout --, point slot k is
+ * output edge k, and edge_origin_dev[k] still applies.  Fully determined, independent of every tuning choice.
+ * point_capacity 0 (arrays may be NULL) is the sizing call; RJ_E_OVERFLOW when n_points > point_capacity: *counts holds
+ * the true counts and nothing is written.  nc == 0, n_cross == 0 and cross_dev == NULL with n_cross == 0 are valid;
+ * with no records the output is a copy of the input.  RJ_E_INVALID, with nothing written: the map checks of
+ * rj_map_crossings, an unknown flag bit, n_cross >= 2^31, np + n_cuts >= 2^32, a record with eid[0] >= eid[1],
+ * eid[1] >= ne or a kind outside 1..4, a record that names a zero-length edge, records that do not strictly ascend by
+ * ((uint64_t) eid[0] << 32) | eid[1], an open or one-point chain under RJ_NODE_DROP_LAST.  Runs on the handle's stream
+ * with one host sync, at the end, for the counts.  Scratch (80 bytes per record, 12 per edge, plus the sort's and the
+ * scans' temporary storage) is allocated per call and freed; no map, index or option of the handle changes.
+ * rj_get_option: "node_last_us0" .. "node_last_us5" (HIP-event microseconds of the stages: the check, the candidates,
+ * their sort and the kept cuts, the cuts per edge and their scan, the two scatters, all; -1: not reached). */
+int rj_map_node(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc,
+                const rj_crossing* cross_dev, uint64_t n_cross, uint32_t flags, uint64_t point_capacity,
+                int64_t* out_xy_dev, uint32_t* out_row_index_dev, uint32_t* edge_origin_dev, rj_node_counts* counts);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

@@ -46,6 +46,8 @@ RINGS_MAP_COUNTS = ("n_chains", "n_points", "n_edges", "n_closed", "n_zero_edges
 # rj_crossing: two edges of one map that meet elsewhere than in a shared end point (eid[0] < eid[1]), and how (RJ_CROSS_*)
 CROSSING_DTYPE = np.dtype([("eid", "<u4", (2,)), ("kind", "<u4"), ("_pad", "<u4")])
 CROSSINGS_COUNTS = ("n_found", "n_proper", "n_touch", "n_overlap", "n_equal", "n_edges", "n_zero_edges")
+RJ_NODE_DROP_LAST = 1  # rj_map_node flags
+NODE_COUNTS = ("n_points", "n_edges", "n_cuts", "n_cut_edges", "n_max_cuts", "n_used", "n_proper", "n_equal")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
 _vp, _u64, _i64, _int = C.c_void_p, C.c_uint64, C.c_int64, C.c_int
@@ -97,6 +99,7 @@ SYMBOLS = {
     "rj_rings_polygons": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "rj_rings_map": (_int, [_vp, _vp, _vp, _u64, _vp, _u64, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "rj_map_crossings": (_int, [_vp, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _vp, _vp]),
+    "rj_map_node": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -198,6 +201,15 @@ class RingsMapOverflow(RayJoinError):
 
 class CrossingsOverflow(RayJoinError):
     """RJ_E_OVERFLOW of rj_map_crossings: counts = dict(n_found, n_proper, n_touch, n_overlap, n_equal, n_edges, n_zero_edges),
+    the true counts"""
+
+    def __init__(self, msg, counts):
+        super().__init__(RJ_E_OVERFLOW, msg)
+        self.counts = counts
+
+
+class NodeOverflow(RayJoinError):
+    """RJ_E_OVERFLOW of rj_map_node: counts = dict(n_points, n_edges, n_cuts, n_cut_edges, n_max_cuts, n_used, n_proper, n_equal),
     the true counts"""
 
     def __init__(self, msg, counts):
@@ -578,6 +590,20 @@ class Handle:
         named = dict(zip(CROSSINGS_COUNTS, (int(v) for v in counts)))
         if rc == RJ_E_OVERFLOW:
             raise CrossingsOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        self._check(rc)
+        return named
+
+    def map_node(self, xy_dev, n_points, row_index_dev, n_chains, cross_dev, n_cross, flags, capacity, out_xy_dev, out_row_index_dev,
+                 edge_origin_dev=None):
+        """rj_map_node of a chain map and its rj_map_crossings records, both in device memory, into the caller's device arrays
+        of `capacity` points, n_chains + 1 row entries and (or None) n_edges origins (capacity 0, arrays None: the sizing
+        call).  Returns the counts as a dict (NODE_COUNTS); NodeOverflow (with the true counts) past the capacity."""
+        counts = (_u64 * 8)()
+        rc = self.L.rj_map_node(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains), _ptr(cross_dev), int(n_cross), int(flags),
+                                int(capacity), _ptr(out_xy_dev), _ptr(out_row_index_dev), _ptr(edge_origin_dev), counts)
+        named = dict(zip(NODE_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise NodeOverflow(self.L.rj_last_error_string(self.h).decode(), named)
         self._check(rc)
         return named
 

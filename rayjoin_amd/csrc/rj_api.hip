@@ -15,6 +15,7 @@
 
 #include "../../include/rayjoin_amd.h"
 #include "rj_crossings.h"
+#include "rj_node.h"
 #include "rj_kernels.h"
 #include "rj_overlay_dev.h"
 #include "rj_overlay_ops.h"
@@ -271,6 +272,7 @@ struct rj_handle_s {
   // rj_map_crossings: 0 = choose / the default (tests force a shift and lower the budget; tools vary the two factors)
   int debug_cross_shift = 0, debug_cross_pair_budget = 0, debug_cross_extent_factor = 0, debug_cross_reg_factor = 0;
   CrossingsReport cross_report = {};  // what the last rj_map_crossings chose and took (reports only)
+  NodeReport node_report = {{-1, -1, -1, -1, -1, -1}};  // what the stages of the last rj_map_node took (reports only)
   uint32_t stitch_stats[4] = {0, 0, 0, 0};  // the last run cutting: ranking rounds, incidences on closed loops, rounds of the second ranking, closed chains
   char* strip_scratch = nullptr;  // grow-only temporaries of the column index's build
   size_t strip_scratch_bytes = 0;
@@ -693,6 +695,7 @@ const Report kReports[] = {
     {"cross_last_pair_tests", 0, RJ_READ(h->cross_report.pair_tests)},
     {"cross_last_items", 0, RJ_READ(h->cross_report.n_items)},
     {"cross_last_us", 6, RJ_READ(h->cross_report.ms[k] < 0 ? -1 : (int64_t) (h->cross_report.ms[k] * 1000.0f))},  // edges and sums, registrations and sort, runs, pairs, hits, all
+    {"node_last_us", 6, RJ_READ(h->node_report.ms[k] < 0 ? -1 : (int64_t) (h->node_report.ms[k] * 1000.0f))},  // the last rj_map_node: check, candidates, sort, cuts per edge, scatters, all
     {"comm_ranks", 0, read_comm_ranks},
     {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
     {"pip_share_blocks", 0, RJ_READ(h->last_pip_share ? h->last_pip_share : h->pip_share_blocks())},
@@ -2860,6 +2863,50 @@ int rj_map_crossings(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint
                 (unsigned long long) (rep.largest_cell & 0xFFFFFFFFull), (unsigned long long) (rep.largest_cell >> 32), (unsigned long long) rep.largest_run);
   if (counts->n_found > capacity)
     return fail(h, RJ_E_OVERFLOW, "rj_map_crossings: %llu crossings; capacity %llu", (unsigned long long) counts->n_found, (unsigned long long) capacity);
+  return RJ_OK;
+}
+
+int rj_map_node(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc, const rj_crossing* cross_dev, uint64_t n_cross,
+                uint32_t flags, uint64_t point_capacity, int64_t* out_xy_dev, uint32_t* out_row_index_dev, uint32_t* edge_origin_dev,
+                rj_node_counts* counts) {
+  static_assert(sizeof(rj_crossing) == sizeof(node::Record) && sizeof(rj_node_counts) == sizeof(node::Counts) && RJ_NODE_DROP_LAST == node::kDropLast,
+                "layouts");
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_map_node: counts is null");
+  memset(counts, 0, sizeof(*counts));
+  if (flags & ~(uint32_t) RJ_NODE_DROP_LAST) return fail(h, RJ_E_INVALID, "rj_map_node: unknown flags 0x%x", flags);
+  if ((np && !xy_dev) || (nc && !row_index_dev) || (n_cross && !cross_dev)) return fail(h, RJ_E_INVALID, "rj_map_node: null input array");
+  if (np >= (1ull << 32) || nc > np || np - nc >= 0xFFFFFFFFull) return fail(h, RJ_E_INVALID, "rj_map_node: nc <= np < 2^32 and np - nc < 2^32 - 1");
+  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_node: points without chains");
+  if (n_cross >= (1ull << 31)) return fail(h, RJ_E_INVALID, "rj_map_node: n_cross < 2^31");
+  if (nc == 0 && n_cross) return fail(h, RJ_E_INVALID, "rj_map_node: a record names an edge that the map does not have");
+  if (point_capacity && (!out_xy_dev || !out_row_index_dev)) return fail(h, RJ_E_INVALID, "rj_map_node: null output");
+  if (int r = set_device(h)) return r;
+  h->node_report = NodeReport{{-1, -1, -1, -1, -1, -1}};
+  if (nc == 0) {  // no chains: the row's one entry, where the caller has an array
+    if (out_row_index_dev) {
+      RJ_HIP(h, hipMemsetAsync(out_row_index_dev, 0, 4, h->stream));
+      RJ_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return RJ_OK;
+  }
+  node::Meta m;
+  RJ_HIP(h, map_node_device(h->stream, xy_dev, np, row_index_dev, nc, cross_dev, n_cross, flags, point_capacity, out_xy_dev, out_row_index_dev,
+                            edge_origin_dev, &m, &h->node_report));
+  if (m.bad == crossings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_node: row_index must start at 0");
+  if (m.bad == crossings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_node: row_index must end at np");
+  if (m.bad == crossings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_node: row_index must ascend (a chain has no point)");
+  if (m.bad == crossings::kBadCoordinate) return fail(h, RJ_E_INVALID, "rj_map_node: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  if (m.bad == node::kBadOpenChain)
+    return fail(h, RJ_E_INVALID, "rj_map_node: RJ_NODE_DROP_LAST needs chains of two points or more whose first point equals the last");
+  if (m.bad == node::kBadRecord) return fail(h, RJ_E_INVALID, "rj_map_node: a record needs eid[0] < eid[1] < ne and a kind in 1..4");
+  if (m.bad == node::kBadZeroEdge) return fail(h, RJ_E_INVALID, "rj_map_node: a record names an edge of zero length");
+  if (m.bad) return fail(h, RJ_E_INVALID, "rj_map_node: the records must strictly ascend by (eid[0], eid[1])");
+  memcpy(counts, &m.counts, sizeof(*counts));
+  if (np + counts->n_cuts >= (1ull << 32))
+    return fail(h, RJ_E_INVALID, "rj_map_node: %llu points and %llu cuts: np + n_cuts < 2^32", (unsigned long long) np, (unsigned long long) counts->n_cuts);
+  if (counts->n_points > point_capacity)
+    return fail(h, RJ_E_OVERFLOW, "rj_map_node: %llu points; capacity %llu", (unsigned long long) counts->n_points, (unsigned long long) point_capacity);
   return RJ_OK;
 }
 

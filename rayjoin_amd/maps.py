@@ -328,6 +328,27 @@ def rings_of_polygons(polygons):
     return np.array(row, np.uint32), np.array(pts, np.int64).reshape(-1, 2), np.array(faces, np.int32)
 
 
+def closed_chains_of_rings(ring_row, ring_xy):
+    """Rings (ring_row uint32 [n_rings + 1], ring_xy int64 [n_points, 2]: rings_of_polygons) -> (row_index uint32
+    [n_rings + 1], xy int64 [n_points + n_rings, 2]): every ring as a closed chain, its first point repeated at its end --
+    what ops.map_crossings and ops.map_node (drop_last) take.  ValueError for an empty ring: it has no first point."""
+    row = np.asarray(ring_row, dtype=np.int64)
+    xy = np.ascontiguousarray(ring_xy, dtype=np.int64).reshape(-1, 2)
+    if len(row) == 0 or row[0] != 0 or row[-1] != len(xy):
+        raise ValueError("ring_row must start at 0 and end at the number of points")
+    sizes = np.diff(row)
+    if (sizes <= 0).any():
+        raise ValueError("ring %d is empty" % int(np.nonzero(sizes <= 0)[0][0]))
+    n = len(sizes)
+    out_row = row + np.arange(n + 1)
+    out = np.empty((len(xy) + n, 2), np.int64)
+    keep = np.ones(len(out), bool)
+    keep[out_row[1:] - 1] = False  # the closing slots
+    out[keep] = xy
+    out[out_row[1:] - 1] = xy[row[:-1]]
+    return out_row.astype(np.uint32), out
+
+
 class Context:
     """src/context.h:31-88: owns the (up to) two planar graphs, the joint bbox and the scaling."""
 

@@ -26,6 +26,10 @@
       -- the check that a chain map is a planar subdivision (rj_map_crossings): every pair of edges of ONE map that
          meets elsewhere than in a shared end point, exactly, on the device -- before InstallMap of user polygons,
          between two overlays.  The reference never validates a map (src/map/map.h:162-233)
+  map_node(handle, ...) / DeviceOutputMap.Node(handle) / DeviceChainMap.Node(handle) -> DeviceNodedMap; node_rings(handle, ...)
+      -- the repair behind that check where it is exact (rj_map_node): every edge cut at the vertices that lie inside it,
+         so that T-junctions and half-shared borders (RJ_CROSS_TOUCH, RJ_CROSS_OVERLAP) become shared vertices and equal
+         edges; node_rings takes the user's rings to the arrays rings_map takes.  Proper crossings are counted, not moved
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -385,6 +389,10 @@ class DeviceOutputMap:
         """map_crossings of this map, on the device: does it still have no crossings (its cut points are truncated to integers)"""
         return map_crossings(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
 
+    def Node(self, handle, **kw):
+        """map_node of this map, on the device: its edges cut at the vertices that lie inside them (left / right stay valid)"""
+        return map_node(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
+
     def free(self):
         for b in (self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin):
             b.free()
@@ -397,6 +405,18 @@ def map_crossings(handle, xy, n_points, row_index, n_chains, capacity=None):
     RJ_CROSS_PROPER / TOUCH / OVERLAP / EQUAL), ascending by (eid[0], eid[1]); counts a dict (CROSSINGS_COUNTS).  No
     record: the map is a planar subdivision.  capacity: CrossingsOverflow with the true counts when it is too small;
     left open, a sizing call finds it."""
+    buf, counts = _crossings_on_device(handle, xy, n_points, row_index, n_chains, capacity)
+    if buf is None:
+        return np.zeros(0, _capi.CROSSING_DTYPE), counts
+    try:
+        return buf.to_host(_capi.CROSSING_DTYPE, counts["n_found"]), counts
+    finally:
+        buf.free()
+
+
+def _crossings_on_device(handle, xy, n_points, row_index, n_chains, capacity=None):
+    """map_crossings whose records stay on the device -> (a DeviceBuffer of counts["n_found"] records, counts); no buffer
+    where a sizing call found no record"""
     args = (xy, n_points, row_index, n_chains)
     if capacity is None:
         try:
@@ -404,15 +424,92 @@ def map_crossings(handle, xy, n_points, row_index, n_chains, capacity=None):
         except _capi.CrossingsOverflow as e:
             c = e.counts
         if c["n_found"] == 0:
-            return np.zeros(0, _capi.CROSSING_DTYPE), c
+            return None, c
         capacity = c["n_found"]
     capacity = int(capacity)
     buf = handle.alloc(_capi.CROSSING_DTYPE.itemsize * max(1, capacity))
     try:
-        counts = handle.map_crossings(*args, capacity, buf)
-        return buf.to_host(_capi.CROSSING_DTYPE, counts["n_found"]), counts
-    finally:
+        return buf, handle.map_crossings(*args, capacity, buf)
+    except _capi.RayJoinError:
         buf.free()
+        raise
+
+
+def map_node(handle, xy, n_points, row_index, n_chains, records=None, drop_last=False, edge_origin=False, capacity=None):
+    """A chain map in device memory with every edge cut at the vertices that lie inside it (rj_map_node) as a
+    DeviceNodedMap: the exact repair of T-junctions and half-shared borders, the RJ_CROSS_TOUCH and RJ_CROSS_OVERLAP
+    records of map_crossings.  records: the host CROSSING_DTYPE array that map_crossings returned for this very map; None:
+    rj_map_crossings runs here and its records stay on the device.  Chains, their number and their order do not change: the
+    caller's left / right arrays go with the result as they are.  drop_last (RJ_NODE_DROP_LAST) takes closed chains (first
+    point == last) and writes each without its last point, the ring layout that rings_map takes.  edge_origin: also the
+    input edge of every output edge.  counts["n_proper"]: the crossings that noding cannot repair.  capacity (points):
+    NodeOverflow with the true counts when it is too small; left open, a sizing call finds it."""
+    flags = _capi.RJ_NODE_DROP_LAST if drop_last else 0
+    if records is None:
+        rec, c = _crossings_on_device(handle, xy, n_points, row_index, n_chains)
+        n_rec = c["n_found"]
+    else:
+        records = np.ascontiguousarray(records, dtype=_capi.CROSSING_DTYPE)
+        n_rec = len(records)
+        rec = handle.alloc(_capi.CROSSING_DTYPE.itemsize * n_rec).from_host(records) if n_rec else None
+    bufs = []
+    try:
+        args = (xy, n_points, row_index, n_chains, rec, n_rec, flags)
+        if capacity is None:
+            try:
+                capacity = handle.map_node(*args, 0, None, None)["n_points"]
+            except _capi.NodeOverflow as e:
+                capacity = e.counts["n_points"]
+        capacity = int(capacity)
+        bufs = [handle.alloc(16 * max(1, capacity)), handle.alloc(4 * (int(n_chains) + 1)), handle.alloc(4 * max(1, capacity)) if edge_origin else None]
+        counts = handle.map_node(*args, capacity, *bufs)
+    except _capi.RayJoinError:
+        for b in bufs:
+            if b is not None:
+                b.free()
+        raise
+    finally:
+        if rec is not None:
+            rec.free()
+    return DeviceNodedMap(*bufs, counts, n_chains, drop_last)
+
+
+class DeviceNodedMap:
+    """A noded chain map in device memory (rj_map_node): xy (int64 x,y pairs), row_index (uint32, n_chains + 1) and, where
+    asked for, edge_origin (uint32 per output edge: its input edge) as DeviceBuffers, the counts n_points, n_edges, n_cuts,
+    n_cut_edges, n_max_cuts, n_used, n_proper, n_equal, and drop_last: the chains are rings without their closing point."""
+
+    def __init__(self, xy, row_index, edge_origin, counts, n_chains, drop_last=False):
+        self.xy, self.row_index, self.edge_origin = xy, row_index, edge_origin
+        self.counts = dict(counts)
+        self.n_points, self.n_chains, self.n_edges = int(counts["n_points"]), int(n_chains), int(counts["n_edges"])
+        self.drop_last = bool(drop_last)
+
+    def to_host(self):
+        """-> (xy int64 [n_points, 2], row_index uint32 [n_chains + 1], edge_origin uint32 [n_edges] or None)"""
+        return (self.xy.to_host(np.int64, 2 * self.n_points).reshape(-1, 2), self.row_index.to_host(np.uint32, self.n_chains + 1),
+                self.edge_origin.to_host(np.uint32, self.n_edges) if self.edge_origin is not None else None)
+
+    def free(self):
+        for b in (self.xy, self.row_index, self.edge_origin):
+            if b is not None:
+                b.free()
+
+
+def node_rings(handle, ring_row, ring_xy):
+    """Host rings (ring_row uint32 CSR, ring_xy int64 pairs: maps.rings_of_polygons) noded against each other on the
+    device: closed into chains (maps.closed_chains_of_rings), uploaded, map_crossings, map_node with drop_last ->
+    (ring_row buffer, ring_xy buffer, n_points, counts), ready for rings_map with the caller's unchanged ring_face.
+    counts["n_proper"] is what noding could not repair: rings that cross each other properly."""
+    from .maps import closed_chains_of_rings
+    row, xy = closed_chains_of_rings(ring_row, ring_xy)
+    bufs = [handle.alloc(16 * max(1, len(xy))).from_host(xy), handle.alloc(4 * len(row)).from_host(row)]
+    try:
+        nm = map_node(handle, bufs[0], len(xy), bufs[1], len(row) - 1, drop_last=True)
+    finally:
+        for b in bufs:
+            b.free()
+    return nm.row_index, nm.xy, nm.n_points, nm.counts
 
 
 def face_rings(handle, xy, n_points, row_index, left, right, n_chains, skip_face0=False, points=True, capacities=None):
@@ -567,6 +664,10 @@ class DeviceChainMap:
     def Crossings(self, handle, **kw):
         """map_crossings of this map, on the device: overlapping or self-crossing polygons show here"""
         return map_crossings(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
+
+    def Node(self, handle, **kw):
+        """map_node of this map, on the device: its edges cut at the vertices that lie inside them (left / right stay valid)"""
+        return map_node(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
 
     def free(self):
         for b in (self.xy, self.row_index, self.left, self.right):
