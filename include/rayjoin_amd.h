@@ -609,6 +609,56 @@ int rj_map_node(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t*
                 const rj_crossing* cross_dev, uint64_t n_cross, uint32_t flags, uint64_t point_capacity,
                 int64_t* out_xy_dev, uint32_t* out_row_index_dev, uint32_t* edge_origin_dev, rj_node_counts* counts);
 
+/* ---- thinning: fewer points on every chain, the same chains ------------------------------------- */
+typedef struct {
+  uint64_t n_points, n_removed;  /* of the output; n_removed = np - n_points */
+  uint64_t n_rounds;             /* rounds that removed something */
+  uint64_t n_closed;             /* chains of 3 points or more whose first point equals the last */
+  uint64_t n_pinned_extra;       /* the m1 / m2 of closed chains that were pinned */
+  uint64_t n_max_round;          /* the most removals in one round */
+} rj_simplify_counts;
+
+/* extends: what makes a map smaller -- an overlay output or a layer of millions of edges is display, export or coarse
+ * pre-filter material only after thinning, and thinning the CHAINS is the one way that keeps neighbours together: a
+ * border that two faces share is stored once, so both polygons are thinned identically and no sliver or gap opens between
+ * them (what arc-based tools do on the host, and a per-polygon simplifier cannot).  Visvalingam-Whyatt by effective area,
+ * in rounds, on the device, on a map in device memory.  (The reference has no counterpart: its maps are loaded as they
+ * are, Map::LoadFrom, src/map/map.h:162-233.)
+ * Input: the map as rj_map_crossings takes it (a chain may have a single point), and tol = (tol_hi << 64) | tol_lo, an
+ * unsigned 128-bit number: twice an area in scaled units^2, the unit of rj_overlay_face.area2.  flags must be 0.
+ * The definition, in full in rayjoin_amd/csrc/rj_simplify.h: the first and the last point of every chain are pinned --
+ * junctions and the chain graph never change.  In a closed chain (3 points or more, first equal to last) with a its
+ * first point, m1, the interior point farthest from a (squared distance, ties to the lowest index), is pinned if that
+ * distance is > 0, and then m2, the interior point with the greatest |cross(m1 - a, q - a)| (ties to the lowest index),
+ * if that value is > 0: a ring never collapses below the triangle a, m1, m2.  A live unpinned point p between its live
+ * neighbours u and w weighs W(p) = |cross(p - u, w - u)| (int128, below 2^95) and is a candidate when W(p) <= tol; its
+ * key is (W(p), (uint32_t) (p * 2654435761u)), p the input point index.  A round removes, all at once, every candidate
+ * whose key is smaller than the key of each live neighbour that is also a candidate; rounds repeat until one has no
+ * candidate.  Integers only, exact, fully determined, independent of every tuning choice.
+ * Output, caller-owned device memory: out_xy_dev[2 point_capacity] the live points in input order,
+ * out_row_index_dev[nc + 1], origin_dev[n_points] (may be NULL): the input point of every output point.  Chains, their
+ * number and their order do not change: the caller's left / right arrays stay valid.  Every unpinned output point weighs
+ * more than tol in the output; a second call with the same tol removes nothing; tol = 2^128 - 1 leaves the pinned points
+ * (2 of an open chain); tol = 0 removes collinear runs and spikes a -> b -> a.  NOT promised: that the thinned map has
+ * no crossings -- thinning can push a chain across another one; rj_map_crossings tells.
+ * point_capacity 0 (arrays may be NULL) is the sizing call; RJ_E_OVERFLOW when n_points > point_capacity: *counts holds
+ * the true counts and nothing is written.  nc == 0 is valid.  RJ_E_INVALID, with nothing written: the map checks of
+ * rj_map_crossings, a nonzero flag, np >= 2^32.  Runs on the handle's stream with one host sync per round (the points
+ * it removed and the size of the next round's work list: two numbers) and one at the end.  After the first round a
+ * round looks only at its work list -- the candidates that stayed and the neighbours of the points just removed --, so
+ * a late round costs what it looks at, not np.  Scratch (38 bytes per point plus the scan's temporary storage) is
+ * allocated per call and freed; no map, index or option of the handle changes.
+ * For tests, through rj_set_debug_option: "simplify_all_points" 1 makes every round look at every point (the same
+ * result).  What the last call took, through rj_get_option: "simplify_last_us0" .. "simplify_last_us5" (HIP-event
+ * microseconds of the stages: the check, the links and the pins, the first round, the later rounds, the scan and the
+ * scatter, all; -1: not reached), "simplify_last_syncs", "simplify_last_list_sum" / "simplify_last_list_max" (the work
+ * lists behind the first round), "simplify_round_list0" .. "9" and "simplify_round_us0" .. "9" (the first ten rounds:
+ * the points looked at, the host's microseconds from the first launch to the sync), "simplify_late_rounds" /
+ * "simplify_late_list" / "simplify_late_us" (the rounds behind them, summed). */
+int rj_map_simplify(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc,
+                    uint64_t tol_lo, uint64_t tol_hi, uint32_t flags, uint64_t point_capacity, int64_t* out_xy_dev,
+                    uint32_t* out_row_index_dev, uint32_t* origin_dev /* may be NULL */, rj_simplify_counts* counts);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */
@@ -751,6 +801,8 @@ int rj_dev_alloc(rj_handle h, size_t bytes, void** out_dev);
 int rj_dev_free(rj_handle h, void* dev);
 int rj_memcpy_h2d(rj_handle h, void* dst_dev, const void* src, size_t bytes);
 int rj_memcpy_d2h(rj_handle h, void* dst, const void* src_dev, size_t bytes);
+/* device to device, synchronous like the two above (the faces of a map that go with a thinned copy of it) */
+int rj_memcpy_d2d(rj_handle h, void* dst_dev, const void* src_dev, size_t bytes);
 
 #ifdef __cplusplus
 }

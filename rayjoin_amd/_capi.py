@@ -48,6 +48,7 @@ CROSSING_DTYPE = np.dtype([("eid", "<u4", (2,)), ("kind", "<u4"), ("_pad", "<u4"
 CROSSINGS_COUNTS = ("n_found", "n_proper", "n_touch", "n_overlap", "n_equal", "n_edges", "n_zero_edges")
 RJ_NODE_DROP_LAST = 1  # rj_map_node flags
 NODE_COUNTS = ("n_points", "n_edges", "n_cuts", "n_cut_edges", "n_max_cuts", "n_used", "n_proper", "n_equal")
+SIMPLIFY_COUNTS = ("n_points", "n_removed", "n_rounds", "n_closed", "n_pinned_extra", "n_max_round")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
 _vp, _u64, _i64, _int = C.c_void_p, C.c_uint64, C.c_int64, C.c_int
@@ -100,6 +101,7 @@ SYMBOLS = {
     "rj_rings_map": (_int, [_vp, _vp, _vp, _u64, _vp, _u64, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "rj_map_crossings": (_int, [_vp, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _vp, _vp]),
     "rj_map_node": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
+    "rj_map_simplify": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -116,6 +118,7 @@ SYMBOLS = {
     "rj_dev_free": (_int, [_vp, _vp]),
     "rj_memcpy_h2d": (_int, [_vp, _vp, _vp, C.c_size_t]),
     "rj_memcpy_d2h": (_int, [_vp, _vp, _vp, C.c_size_t]),
+    "rj_memcpy_d2d": (_int, [_vp, _vp, _vp, C.c_size_t]),
 }
 
 
@@ -217,6 +220,15 @@ class NodeOverflow(RayJoinError):
         self.counts = counts
 
 
+class SimplifyOverflow(RayJoinError):
+    """RJ_E_OVERFLOW of rj_map_simplify: counts = dict(n_points, n_removed, n_rounds, n_closed, n_pinned_extra, n_max_round),
+    the true counts"""
+
+    def __init__(self, msg, counts):
+        super().__init__(RJ_E_OVERFLOW, msg)
+        self.counts = counts
+
+
 class QueueOverflow(RayJoinError):
     """RJ_E_OVERFLOW: n_found holds the true count (the reference only asserts, queue.h:37)."""
 
@@ -286,6 +298,13 @@ class DeviceBuffer:
         assert arr.nbytes <= self.nbytes
         if arr.nbytes:
             self.handle._check(load().rj_memcpy_h2d(self.handle.h, self.ptr, arr.ctypes.data, arr.nbytes))
+        return self
+
+    def from_device(self, src, nbytes):
+        """the first nbytes of another device array (a DeviceBuffer, a tensor, an address)"""
+        assert int(nbytes) <= self.nbytes
+        if nbytes:
+            self.handle._check(load().rj_memcpy_d2d(self.handle.h, self.ptr, _ptr(src), int(nbytes)))
         return self
 
     def free(self):
@@ -604,6 +623,22 @@ class Handle:
         named = dict(zip(NODE_COUNTS, (int(v) for v in counts)))
         if rc == RJ_E_OVERFLOW:
             raise NodeOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        self._check(rc)
+        return named
+
+    def map_simplify(self, xy_dev, n_points, row_index_dev, n_chains, tol, capacity, out_xy_dev, out_row_index_dev, origin_dev=None, flags=0):
+        """rj_map_simplify of a chain map in device memory into the caller's device arrays of `capacity` points, n_chains + 1
+        row entries and (or None) `capacity` origins (capacity 0, arrays None: the sizing call); tol a Python int in
+        [0, 2^128).  Returns the counts as a dict (SIMPLIFY_COUNTS); SimplifyOverflow (with the true counts) past the capacity."""
+        tol = int(tol)
+        if not 0 <= tol < 1 << 128:
+            raise ValueError("tol must lie in [0, 2^128), not %d" % tol)
+        counts = (_u64 * 6)()
+        rc = self.L.rj_map_simplify(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains), tol & 0xFFFFFFFFFFFFFFFF, tol >> 64,
+                                    int(flags), int(capacity), _ptr(out_xy_dev), _ptr(out_row_index_dev), _ptr(origin_dev), counts)
+        named = dict(zip(SIMPLIFY_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise SimplifyOverflow(self.L.rj_last_error_string(self.h).decode(), named)
         self._check(rc)
         return named
 

@@ -23,6 +23,7 @@
 #include "rj_polygons.h"
 #include "rj_ringmap.h"
 #include "rj_rings.h"
+#include "rj_simplify.h"
 
 using namespace rj;
 
@@ -273,6 +274,8 @@ struct rj_handle_s {
   int debug_cross_shift = 0, debug_cross_pair_budget = 0, debug_cross_extent_factor = 0, debug_cross_reg_factor = 0;
   CrossingsReport cross_report = {};  // what the last rj_map_crossings chose and took (reports only)
   NodeReport node_report = {{-1, -1, -1, -1, -1, -1}};  // what the stages of the last rj_map_node took (reports only)
+  int debug_simplify_all_points = 0;  // rj_map_simplify: 1 = every round looks at every point, no work list (tests: the same result)
+  SimplifyReport simplify_report = {{-1, -1, -1, -1, -1, -1}};  // what the last rj_map_simplify took (reports only)
   uint32_t stitch_stats[4] = {0, 0, 0, 0};  // the last run cutting: ranking rounds, incidences on closed loops, rounds of the second ranking, closed chains
   char* strip_scratch = nullptr;  // grow-only temporaries of the column index's build
   size_t strip_scratch_bytes = 0;
@@ -622,6 +625,7 @@ const Option kOptions[] = {
     {"cross_pair_budget", true, &rj_handle_s::debug_cross_pair_budget, 0, 1 << 30},  // ... pair tests it refuses above (0: 2^36)
     {"cross_extent_factor", true, &rj_handle_s::debug_cross_extent_factor, 0, 1 << 20},  // ... a cell is this many mean extents wide (0: 8)
     {"cross_reg_factor", true, &rj_handle_s::debug_cross_reg_factor, 0, 1 << 20},  // ... registrations per edge allowed (0: 4)
+    {"simplify_all_points", true, &rj_handle_s::debug_simplify_all_points, 0, 1},  // rj_map_simplify: every round over all points (0: the work list)
 };
 
 const Option* find_option(const char* name, bool debug) {
@@ -696,6 +700,15 @@ const Report kReports[] = {
     {"cross_last_items", 0, RJ_READ(h->cross_report.n_items)},
     {"cross_last_us", 6, RJ_READ(h->cross_report.ms[k] < 0 ? -1 : (int64_t) (h->cross_report.ms[k] * 1000.0f))},  // edges and sums, registrations and sort, runs, pairs, hits, all
     {"node_last_us", 6, RJ_READ(h->node_report.ms[k] < 0 ? -1 : (int64_t) (h->node_report.ms[k] * 1000.0f))},  // the last rj_map_node: check, candidates, sort, cuts per edge, scatters, all
+    {"simplify_last_us", 6, RJ_READ(h->simplify_report.ms[k] < 0 ? -1 : (int64_t) (h->simplify_report.ms[k] * 1000.0f))},  // the last rj_map_simplify: check, links and pins, first round, later rounds, scan and scatter, all
+    {"simplify_last_syncs", 0, RJ_READ(h->simplify_report.n_syncs)},        // ... its host syncs
+    {"simplify_last_list_sum", 0, RJ_READ(h->simplify_report.list_sum)},    // ... the work lists of the rounds behind the first, summed
+    {"simplify_last_list_max", 0, RJ_READ(h->simplify_report.list_max)},    // ... and the longest
+    {"simplify_round_list", 10, RJ_READ(h->simplify_report.round_list[k])},  // ... round k: the points it looked at,
+    {"simplify_round_us", 10, RJ_READ((int64_t) (h->simplify_report.round_ms[k] * 1000.0f))},  // the host's time from its first launch to its sync
+    {"simplify_late_rounds", 0, RJ_READ(h->simplify_report.late_rounds)},   // ... the rounds from the eleventh on: how many,
+    {"simplify_late_list", 0, RJ_READ(h->simplify_report.late_list)},       // the points they looked at,
+    {"simplify_late_us", 0, RJ_READ((int64_t) (h->simplify_report.late_ms * 1000.0f))},  // their time
     {"comm_ranks", 0, read_comm_ranks},
     {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
     {"pip_share_blocks", 0, RJ_READ(h->last_pip_share ? h->last_pip_share : h->pip_share_blocks())},
@@ -2910,6 +2923,40 @@ int rj_map_node(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t*
   return RJ_OK;
 }
 
+int rj_map_simplify(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc, uint64_t tol_lo, uint64_t tol_hi,
+                    uint32_t flags, uint64_t point_capacity, int64_t* out_xy_dev, uint32_t* out_row_index_dev, uint32_t* origin_dev,
+                    rj_simplify_counts* counts) {
+  static_assert(sizeof(rj_simplify_counts) == sizeof(simplify::Counts), "layouts");
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_map_simplify: counts is null");
+  memset(counts, 0, sizeof(*counts));
+  if (flags) return fail(h, RJ_E_INVALID, "rj_map_simplify: unknown flags 0x%x", flags);
+  if ((np && !xy_dev) || (nc && !row_index_dev)) return fail(h, RJ_E_INVALID, "rj_map_simplify: null input array");
+  if (np >= (1ull << 32) || nc > np) return fail(h, RJ_E_INVALID, "rj_map_simplify: nc <= np < 2^32");
+  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_simplify: points without chains");
+  if (point_capacity && (!out_xy_dev || !out_row_index_dev)) return fail(h, RJ_E_INVALID, "rj_map_simplify: null output");
+  if (int r = set_device(h)) return r;
+  h->simplify_report = SimplifyReport{{-1, -1, -1, -1, -1, -1}};
+  if (nc == 0) {  // no chains: the row's one entry, where the caller has an array
+    if (out_row_index_dev) {
+      RJ_HIP(h, hipMemsetAsync(out_row_index_dev, 0, 4, h->stream));
+      RJ_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return RJ_OK;
+  }
+  simplify::Meta m;
+  RJ_HIP(h, map_simplify_device(h->stream, xy_dev, np, row_index_dev, nc, tol_lo, tol_hi, h->debug_simplify_all_points != 0, point_capacity, out_xy_dev,
+                                out_row_index_dev, origin_dev, &m, &h->simplify_report));
+  if (m.bad == crossings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_simplify: row_index must start at 0");
+  if (m.bad == crossings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_simplify: row_index must end at np");
+  if (m.bad == crossings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_simplify: row_index must ascend (a chain has no point)");
+  if (m.bad) return fail(h, RJ_E_INVALID, "rj_map_simplify: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  memcpy(counts, &m.counts, sizeof(*counts));
+  if (counts->n_points > point_capacity)
+    return fail(h, RJ_E_OVERFLOW, "rj_map_simplify: %llu points; capacity %llu", (unsigned long long) counts->n_points, (unsigned long long) point_capacity);
+  return RJ_OK;
+}
+
 int rj_last_ms(rj_handle h, int which, float* ms) {
   RJ_CHECK_H(h);
   if (which < 0 || which >= kNumTimers || !ms) return fail(h, RJ_E_INVALID, "rj_last_ms: bad timer");
@@ -2973,6 +3020,14 @@ int rj_memcpy_d2h(rj_handle h, void* dst, const void* src_dev, size_t bytes) {
   RJ_CHECK_H(h);
   if (int r = set_device(h)) return r;
   if (bytes) RJ_HIP(h, hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, h->stream));
+  RJ_HIP(h, hipStreamSynchronize(h->stream));
+  return RJ_OK;
+}
+
+int rj_memcpy_d2d(rj_handle h, void* dst_dev, const void* src_dev, size_t bytes) {
+  RJ_CHECK_H(h);
+  if (int r = set_device(h)) return r;
+  if (bytes) RJ_HIP(h, hipMemcpyAsync(dst_dev, src_dev, bytes, hipMemcpyDeviceToDevice, h->stream));
   RJ_HIP(h, hipStreamSynchronize(h->stream));
   return RJ_OK;
 }

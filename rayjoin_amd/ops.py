@@ -30,6 +30,12 @@
       -- the repair behind that check where it is exact (rj_map_node): every edge cut at the vertices that lie inside it,
          so that T-junctions and half-shared borders (RJ_CROSS_TOUCH, RJ_CROSS_OVERLAP) become shared vertices and equal
          edges; node_rings takes the user's rings to the arrays rings_map takes.  Proper crossings are counted, not moved
+  map_simplify(handle, ...) -> DeviceSimplifiedMap; DeviceOutputMap.Simplify(handle, tol) / DeviceChainMap.Simplify(handle, tol)
+      -> DeviceChainMap
+      -- what makes a map smaller (rj_map_simplify): the chains thinned by effective area, Visvalingam-Whyatt in rounds on
+         the device.  A border that two faces share is one chain: both polygons are thinned identically, no sliver or gap
+         opens, the ends of every chain stay, left / right stay valid.  It may push a chain across another one: check=True
+         also returns the counts of Crossings() on the result
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -393,6 +399,12 @@ class DeviceOutputMap:
         """map_node of this map, on the device: its edges cut at the vertices that lie inside them (left / right stay valid)"""
         return map_node(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
 
+    def Simplify(self, handle, tol, check=False, capacity=None):
+        """map_simplify of this map, on the device, as a DeviceChainMap of its own (copies of left / right: the chains do not
+        change): what InstallMap, Rings() and Crossings() take; its counts are those of rj_map_simplify with n_chains and
+        n_edges.  check: -> (the map, the counts of Crossings() on it) -- thinning can push a chain across another one"""
+        return _simplified_chain_map(handle, self, tol, check, capacity)
+
     def free(self):
         for b in (self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin):
             b.free()
@@ -432,6 +444,69 @@ def _crossings_on_device(handle, xy, n_points, row_index, n_chains, capacity=Non
         return buf, handle.map_crossings(*args, capacity, buf)
     except _capi.RayJoinError:
         buf.free()
+        raise
+
+
+def map_simplify(handle, xy, n_points, row_index, n_chains, tol, origin=False, capacity=None):
+    """A chain map in device memory with its chains thinned by effective area (rj_map_simplify) as a DeviceSimplifiedMap.
+    tol: a Python int in [0, 2^128), twice an area in scaled units^2 (the unit of FaceTable()'s area2): in rounds, every
+    unpinned point whose triangle with its two neighbours has at most that doubled area goes, the least first.  The ends of
+    every chain stay, and a closed chain keeps a triangle: chains, their number and their order do not change, and the
+    caller's left / right arrays go with the result as they are.  origin: also the input point of every output point.
+    capacity (points): SimplifyOverflow with the true counts when it is too small; left open, a sizing call finds it."""
+    bufs = []
+    args = (xy, n_points, row_index, n_chains, tol)
+    try:
+        if capacity is None:
+            try:
+                capacity = handle.map_simplify(*args, 0, None, None)["n_points"]
+            except _capi.SimplifyOverflow as e:
+                capacity = e.counts["n_points"]
+        capacity = int(capacity)
+        bufs = [handle.alloc(16 * max(1, capacity)), handle.alloc(4 * (int(n_chains) + 1)), handle.alloc(4 * max(1, capacity)) if origin else None]
+        counts = handle.map_simplify(*args, capacity, *bufs)
+    except _capi.RayJoinError:
+        for b in bufs:
+            if b is not None:
+                b.free()
+        raise
+    return DeviceSimplifiedMap(*bufs, counts, n_chains)
+
+
+class DeviceSimplifiedMap:
+    """A thinned chain map in device memory (rj_map_simplify): xy (int64 x,y pairs), row_index (uint32, n_chains + 1) and,
+    where asked for, origin (uint32 per output point: its input point) as DeviceBuffers, and the counts n_points,
+    n_removed, n_rounds, n_closed, n_pinned_extra, n_max_round."""
+
+    def __init__(self, xy, row_index, origin, counts, n_chains):
+        self.xy, self.row_index, self.origin = xy, row_index, origin
+        self.counts = dict(counts)
+        self.n_points, self.n_chains = int(counts["n_points"]), int(n_chains)
+
+    def to_host(self):
+        """-> (xy int64 [n_points, 2], row_index uint32 [n_chains + 1], origin uint32 [n_points] or None)"""
+        return (self.xy.to_host(np.int64, 2 * self.n_points).reshape(-1, 2), self.row_index.to_host(np.uint32, self.n_chains + 1),
+                self.origin.to_host(np.uint32, self.n_points) if self.origin is not None else None)
+
+    def free(self):
+        for b in (self.xy, self.row_index, self.origin):
+            if b is not None:
+                b.free()
+
+
+def _simplified_chain_map(handle, m, tol, check, capacity):
+    """DeviceOutputMap.Simplify / DeviceChainMap.Simplify: the thinned map with device copies of m's left / right"""
+    sm = map_simplify(handle, m.xy, m.n_points, m.row_index, m.n_chains, tol, capacity=capacity)
+    sides = []
+    try:
+        sides = [handle.alloc(4 * max(1, m.n_chains)).from_device(b, 4 * m.n_chains) for b in (m.left, m.right)]
+        counts = dict(sm.counts, n_chains=m.n_chains, n_edges=sm.n_points - m.n_chains)
+        out = DeviceChainMap(sm.xy, sm.row_index, sides[0], sides[1], counts)
+        return (out, out.Crossings(handle)[1]) if check else out
+    except _capi.RayJoinError:
+        for b in sides:
+            b.free()
+        sm.free()
         raise
 
 
@@ -668,6 +743,12 @@ class DeviceChainMap:
     def Node(self, handle, **kw):
         """map_node of this map, on the device: its edges cut at the vertices that lie inside them (left / right stay valid)"""
         return map_node(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
+
+    def Simplify(self, handle, tol, check=False, capacity=None):
+        """map_simplify of this map, on the device, as a DeviceChainMap of its own (copies of left / right: the chains do not
+        change): what InstallMap, Rings() and Crossings() take; its counts are those of rj_map_simplify with n_chains and
+        n_edges.  check: -> (the map, the counts of Crossings() on it) -- thinning can push a chain across another one"""
+        return _simplified_chain_map(handle, self, tol, check, capacity)
 
     def free(self):
         for b in (self.xy, self.row_index, self.left, self.right):
