@@ -79,7 +79,13 @@ const char* rj_version(void);
 /* replaces: Context::LoadToDevice -> Map::LoadFrom (src/context.h:76-88, src/map/map.h:162-233).
  * xy: np scaled points (x,y interleaved); row_index[nc+1]: first point of each chain + sentinel;
  * left/right[nc]: face ids of each chain (truncated to 32 bits like dev::Edge, map.h:45).
- * Edge eid of chain c, point p is p - c (map.h:200-203).  Host arrays are copied. */
+ * Edge eid of chain c, point p is p - c (map.h:200-203).  Host arrays are copied.
+ * Both uploads also prepare the map for being the QUERY map of rj_pip_query*: its vertices quantised (8 bytes each) and
+ * the extent of every 64 of them (16 bytes), which a PIP query over a range of the map's own vertices then reads
+ * instead of the int64 points ("pip_last_prepared").  That is 8 np + 16 ceil(np / 64) bytes of device memory per map
+ * on top of the map itself -- 245 MB for a map of 30 M vertices -- for EACH of the two map slots, whether or not the
+ * map is ever the query map of a PIP query: two maps of 30 M vertices pay it twice.  When they cannot be allocated the
+ * upload still succeeds and such queries read the int64 points, as they do for a caller's array. */
 int rj_upload_map(rj_handle h, int map_id, const int64_t* xy, uint64_t np,
                   const uint32_t* row_index, const int64_t* left, const int64_t* right,
                   uint64_t nc);
@@ -96,6 +102,11 @@ int rj_map_num_edges(rj_handle h, int map_id, uint64_t* ne);
 int rj_map_num_points(rj_handle h, int map_id, uint64_t* np);
 /* device pointer to the uploaded scaled points (int64 x,y pairs), owned by the handle */
 int rj_map_points_dev(rj_handle h, int map_id, const int64_t** pts_dev);
+/* inspection: device pointers to what the upload prepared of the map's vertices (see rj_upload_map), owned by the handle
+ * and valid until the next upload of map_id: qpts[np][2] = (x + 2^46) >> 16, (y + 2^46) >> 16 of every vertex, and
+ * qext[ceil(np / 64)][4] = {min x, max x, min y, 0} of those over the vertices 64 b .. 64 b + 63 that exist.  Both
+ * NULL when there was no memory for them; either argument may be NULL. */
+int rj_map_prepared_dev(rj_handle h, int map_id, const int32_t** qpts_dev, const int32_t** qext_dev);
 /* inspection: the polyline runs rj_build_lbvh cut for this map on the device ("leaf_order" 1; the analogue of the
  * reference's RT grouping, src/rt/primitive.h:120-260) -- piece p = eids [piece_begin[p], + piece_len[p]), run r =
  * pieces [run_first[r], run_first[r + 1]).  Host arrays, any of them NULL to fetch only the counts. */
@@ -774,7 +785,10 @@ int rj_last_stats(rj_handle h, uint64_t stats[16]);
  *   "pip_schedule" (0 turns, 1 shared, 2 full grids, -1 still trying), "pip_schedule_trials", "pip_schedule_us0/1/2",
  *   "lsi_share_blocks", "pip_share_blocks"                      what "pip_concurrent" 2 measured and settled on
  *   "lsi_last_segments", "pip_last_walk_points", "pip_last_passes", "lsi_points_last_split", "lsi_points_gcd_pairs",
- *   "pip_rest", "pip_rest_aux", "query_last_ordered", "pip_last_columns"            what the last query ran
+ *   "pip_rest", "pip_rest_aux", "query_last_ordered", "pip_last_columns", "pip_last_prepared"   what the last query ran
+ *     ("pip_last_prepared": what the walk read -- 0 the int64 points, 1 the query map's prepared points with a computed
+ *     extent per group, 2 prepared points and prepared extents: a range of the query map's own vertices, in their own
+ *     order, through k_pip_walk2; extents where pt_begin is a multiple of 64)
  *   "comm_ranks"                                                the ranks RCCL counts in the handle's communicator (0: none) */
 int rj_set_option(rj_handle h, const char* name, int64_t value);
 int rj_get_option(rj_handle h, const char* name, int64_t* value);

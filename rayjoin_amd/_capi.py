@@ -65,6 +65,7 @@ SYMBOLS = {
     "rj_map_num_edges": (_int, [_vp, _int, C.POINTER(_u64)]),
     "rj_map_num_points": (_int, [_vp, _int, C.POINTER(_u64)]),
     "rj_map_points_dev": (_int, [_vp, _int, C.POINTER(_vp)]),
+    "rj_map_prepared_dev": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(_vp)]),
     "rj_invalidate": (_int, [_vp]),
     "rj_map_runs": (_int, [_vp, _int, _vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "rj_build_lbvh": (_int, [_vp, _int]),
@@ -398,6 +399,20 @@ class Handle:
         p = _vp()
         self._check(self.L.rj_map_points_dev(self.h, map_id, C.byref(p)))
         return p.value
+
+    def map_prepared(self, map_id):
+        """-> (qpts [np, 2], qext [ceil(np / 64), 4]) int32 host copies of the map's prepared points, or None where the
+        upload had no memory for them"""
+        qp, qe = _vp(), _vp()
+        self._check(self.L.rj_map_prepared_dev(self.h, map_id, C.byref(qp), C.byref(qe)))
+        if not qp.value or not qe.value:
+            return None
+        n = self.map_num_points(map_id)
+        qpts = np.empty((n, 2), dtype=np.int32)
+        qext = np.empty(((n + 63) // 64, 4), dtype=np.int32)
+        self._check(self.L.rj_memcpy_d2h(self.h, qpts.ctypes.data, qp.value, qpts.nbytes))
+        self._check(self.L.rj_memcpy_d2h(self.h, qext.ctypes.data, qe.value, qext.nbytes))
+        return qpts, qext
 
     def invalidate(self):
         self._check(self.L.rj_invalidate(self.h))

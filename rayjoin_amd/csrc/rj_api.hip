@@ -39,6 +39,11 @@ struct MapState {
   uint32_t* left = nullptr;
   uint32_t* right = nullptr;
   uint32_t* edge_begin = nullptr;  // [nc + 1] first eid of every chain (+ sentinel): row_index[c] - c
+  // what a PIP walk over this map's own vertices reads instead of pts (k_prepare_points; ONE block, the extents first):
+  // qext[(np + 63) / 64] {min x, max x, min y, 0} of the quantised points of every 64 positions, qpts[np] {quant(x),
+  // quant(y)}.  nullptr: no memory for them at the upload -- the walk then reads pts as it does for a caller's array
+  int4* qext = nullptr;
+  int2* qpts = nullptr;
   // "leaf_order" 1: the polyline runs of this map, cut ON THE DEVICE (rj_stitch.hip) the first time an index of it is
   // built and kept: piece p = eids [piece_begin[p], + piece_len[p]), run r = pieces [run_first[r], run_first[r + 1])
   bool runs_cut = false;
@@ -171,6 +176,7 @@ struct rj_handle_s {
   // PIP in two passes (rj_kernels.hip, k_pip_walk): the integer-only walk settles what it can, k_pip takes the rest
   int pip_walk = 1;                        // "pip_walk": 1 auto (default), 0 k_pip alone, 2 always both passes
   int last_walk_points = 1;                // ... and how many points a lane of its walk took
+  int last_prepared = 0;                   // ... and what it read: 0 the int64 points, 1 the query map's prepared points, 2 and its prepared extents
   int last_passes = 0;                     // kernels of the last PIP query (3 or 1)
   int flip_walk[2] = {0, 0};
   // list sets: [0] main stream, [1] aux, [2] aux again -- "pip_exact_stream" alternates [1] and [2], so that the walk of
@@ -332,6 +338,7 @@ struct rj_handle_s {
       uint64_t epoch = 0, n = 0, rest_hint = ~0ull;
       LaunchNote first = {"", 0, 0};
       int passes = 0, order = 0, exact_blocks = 0, locate_blocks = 0;
+      int prepared = 0;  // "pip_last_prepared" of that query
       const char* why = "";
     } pip;
   } plan;
@@ -370,6 +377,7 @@ int dev_alloc(rj_handle h, T** p, uint64_t count) {
 
 void free_map(MapState& m) {
   (void) hipFree(m.pts); (void) hipFree(m.seg); (void) hipFree(m.edge_chain); (void) hipFree(m.ccode); (void) hipFree(m.left); (void) hipFree(m.right); (void) hipFree(m.edge_begin);
+  (void) hipFree(m.qext);  // (qpts lies behind it in the same block)
   (void) hipFree(m.piece_begin); (void) hipFree(m.piece_len); (void) hipFree(m.run_first);
   (void) hipFree(m.run_len); (void) hipFree(m.leaf_first); (void) hipFree(m.pack_tmp); (void) hipFree(m.run_box);
   m = MapState();
@@ -675,6 +683,7 @@ const Report kReports[] = {
     {"pip_schedule_us", 3, RJ_READ(h->co_best[k] < 1e29f ? (int64_t) (h->co_best[k] * 1000.0f) : -1)},  // best span seen per schedule, microseconds (-1: not measured)
     {"lsi_last_segments", 0, RJ_READ(h->last_lsi_segments)},
     {"pip_last_walk_points", 0, RJ_READ(h->last_walk_points)},
+    {"pip_last_prepared", 0, RJ_READ(h->last_prepared)},
     {"lsi_points_last_split", 0, RJ_READ(h->last_points_split)},
     {"lsi_points_gcd_pairs", 0, read_gcd_pairs},
     {"pip_last_passes", 0, RJ_READ(h->last_passes)},  // how the last PIP query ran: 3 = walk + exact + k_pip, 1 = k_pip alone
@@ -928,10 +937,10 @@ int rj_get_plan(rj_handle h, char* buf, size_t cap, size_t* need) {
   }
   if (P.pip.ran) {
     add(", \"pip\": {\"epoch\": %llu, \"current\": %s, \"points\": %llu, \"points_from\": \"%s\", \"stream\": \"%s\", \"on_shared_grid\": %s, \"order\": \"%s\", "
-        "\"passes\": %d, \"first_pass\": {\"kernel\": \"%s\", \"blocks\": %d, \"points_per_lane\": %d}",
+        "\"passes\": %d, \"first_pass\": {\"kernel\": \"%s\", \"blocks\": %d, \"points_per_lane\": %d}, \"prepared_points\": %d",
         (unsigned long long) P.pip.epoch, P.pip.epoch == P.epoch ? "true" : "false", (unsigned long long) P.pip.n, P.pip.caller ? "a caller-owned array" : "the query map's vertices",
         P.pip.aux ? "second (beside the LSI query)" : "main", P.pip.shared ? "true" : "false", kOrder[P.pip.order], P.pip.passes, P.pip.first.kernel, P.pip.first.grid,
-        P.pip.first.per_lane);
+        P.pip.first.per_lane, P.pip.prepared);
     if (P.pip.passes == 3)
       add(", \"second_pass\": {\"kernel\": \"k_pip_exact\", \"blocks\": %d, \"locate_blocks\": %d}, \"left_over_by_last_query_of_this_size\": %lld", P.pip.exact_blocks,
           P.pip.locate_blocks, P.pip.rest_hint == ~0ull ? -1ll : (long long) P.pip.rest_hint);
@@ -999,6 +1008,17 @@ static int install_map(rj_handle h, int map_id, uint64_t np, uint64_t nc, const 
   if (!rc) {
     e = fill(m);
     if (e == hipSuccess) e = launch_build_segs(h->stream, m.pts, m.edge_begin, (uint32_t) nc, m.ne, m.seg, m.edge_chain, m.ccode);
+    // the prepared points (8 bytes per vertex + 16 per 64): without the memory for them the map is as usable as before
+    if (e == hipSuccess && np) {
+      const uint64_t nblocks = (np + 63) / 64;
+      if (hipMalloc((void**) &m.qext, 16 * nblocks + 8 * np) != hipSuccess) {
+        (void) hipGetLastError();
+        m.qext = nullptr;
+      } else {
+        m.qpts = reinterpret_cast<int2*>(m.qext + nblocks);
+        e = launch_prepare_points(h->stream, m.pts, np, m.qpts, m.qext);
+      }
+    }
     // whatever was enqueued may read the caller's host vectors: drain the stream before they go away
     const hipError_t es = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) e = es;
@@ -1113,6 +1133,14 @@ int rj_map_points_dev(rj_handle h, int map_id, const int64_t** pts_dev) {
   RJ_CHECK_H(h);
   if (map_id < 0 || map_id > 1 || !pts_dev || !h->map[map_id].present) return fail(h, RJ_E_INVALID, "map not uploaded");
   *pts_dev = h->map[map_id].pts;
+  return RJ_OK;
+}
+
+int rj_map_prepared_dev(rj_handle h, int map_id, const int32_t** qpts_dev, const int32_t** qext_dev) {
+  RJ_CHECK_H(h);
+  if (map_id < 0 || map_id > 1 || !h->map[map_id].present) return fail(h, RJ_E_INVALID, "map not uploaded");
+  if (qpts_dev) *qpts_dev = reinterpret_cast<const int32_t*>(h->map[map_id].qpts);
+  if (qext_dev) *qext_dev = reinterpret_cast<const int32_t*>(h->map[map_id].qext);
   return RJ_OK;
 }
 
@@ -1970,6 +1998,7 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
   a.stats = h->stats_on ? h->d_stats : nullptr;
   a.rest = nullptr; a.rest_count = nullptr; a.next_rest_count = nullptr; a.n_dev = nullptr;
   a.todo = nullptr; a.todo_mask = nullptr;
+  a.qpts = nullptr; a.qext = nullptr;
   // (k_pip_walk keeps 8 blocks per CU resident where k_pip keeps 6: the shared schedule leaves k_lsi the same room)
   const int walk_full = h->cus * pip_walk_blocks_per_cu(h->bvh[base_map_id].top);
   int walk_blocks = h->max_blocks;
@@ -2028,6 +2057,7 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
   }
   h->last_passes = walk ? 3 : 1;
   h->last_walk_points = 1;
+  h->last_prepared = 0;
   tic(h, RJ_T_PIP_KERNEL, st);
   if (n && walk) {
     const int wflip = h->flip_walk[si];
@@ -2069,6 +2099,14 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
     } else if (two) {
       if (aux && h->lsi_shared && !h->pip_share_set)
         walk_blocks = h->cus * pip_walk2_blocks_beside(w.bvh.top, walk_share_of_this_pair / h->cus < 1 ? 1 : walk_share_of_this_pair / h->cus);
+      // the query map's own vertices in their own order: what its upload prepared (caller-owned arrays, re-ordered sets
+      // and the instrumented kernel read the int64 points)
+      const MapState& q = h->map[query_map_id];
+      if (!pts_dev && !order && !h->stats_on && q.qpts) {
+        w.qpts = q.qpts + pt_begin;
+        h->last_prepared = 1;
+        if (pt_begin % 64 == 0) { w.qext = q.qext + pt_begin / 64; h->last_prepared = 2; }
+      }
       RJ_HIP(h, launch_pip_walk2(st, w, walk_blocks, h->cus, h->stats_on));
       h->last_walk_points = 2;
     } else {
@@ -2129,6 +2167,7 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
     pp.ran = n > 0; pp.epoch = h->plan.epoch; pp.n = n; pp.aux = aux; pp.caller = pts_dev != nullptr;
     pp.shared = aux && h->lsi_shared; pp.passes = h->last_passes; pp.rest_hint = seen; pp.why = why;
     pp.order = order ? (h->order_fresh ? 2 : 1) : 0;
+    pp.prepared = h->last_prepared;
   }
   toc(h, RJ_T_PIP_KERNEL, own ? h->exact_stream : st);
   // a caller-owned array: the estimate the next query over it will go by, behind this query's kernels on their stream

@@ -72,6 +72,12 @@ struct PipArgs {
   unsigned long long* rest_count;        // (walk) zero when the kernel starts; (k_pip) nullable: where it reports the count it found
   unsigned long long* next_rest_count;   // (walk) the next walk's counter on this stream: cleared by this walk
   const unsigned long long* n_dev;       // (k_pip only) nullable: process min(n, *n_dev) queries
+  // k_pip_walk2 only, both nullable: what the query map's upload prepared (launch_prepare_points), offset to the first
+  // point like `pts`.  qpts: {quant(x), quant(y)} per point -- the walk reads these 8 bytes instead of 16 and quantises
+  // nothing.  qext: {min x, max x, min y, 0} of every 64 positions -- a group's extent is two scalar loads instead of a
+  // wave reduction (only where the first point is a multiple of 64; requires qpts and order == nullptr)
+  const int2* qpts;
+  const int4* qext;
 };
 
 // ---- -mode=grid on the device (rj_grid.hip) ------------------------------------------------
@@ -106,6 +112,8 @@ hipError_t launch_pip_grid(hipStream_t st, const GridPipArgs& a);
 
 hipError_t launch_build_segs(hipStream_t st, const int64_t* pts, const uint32_t* edge_begin,
                              uint32_t nc, uint64_t ne, Seg* seg, uint32_t* edge_chain, uint32_t* ccode);
+// the prepared points of an uploaded map (PipArgs::qpts, qext): qpts[np], qext[(np + 63) / 64]
+hipError_t launch_prepare_points(hipStream_t st, const int64_t* pts, uint64_t np, int2* qpts, int4* qext);
 hipError_t launch_morton(hipStream_t st, const Seg* seg, uint64_t ne, MortonKey* keys, uint32_t* vals);
 hipError_t sort_morton_pairs(hipStream_t st, void* temp, size_t& temp_bytes, const MortonKey* kin, MortonKey* kout,
                              const uint32_t* vin, uint32_t* vout, uint64_t n);

@@ -46,6 +46,28 @@ __global__ __launch_bounds__(256) void k_build_segs(const int64_t* __restrict__ 
   }
 }
 
+// What a PIP walk over a map's own vertices needs of a point, made once at the upload (the LSI side's ccode): the quantised
+// point, and per 64 absolute positions the {min x, max x, min y} a query group starts its traversal from (positions
+// past the end count for nothing: the last block's entry covers the points it has, an empty block keeps the empty box).
+// One wave per 64 positions.
+__global__ __launch_bounds__(256) void k_prepare_points(const int64_t* __restrict__ pts, uint64_t np, int2* __restrict__ qpts,
+                                                        int4* __restrict__ qext) {
+  const int lane = lane_id();
+  const uint64_t nblocks = (np + 63) / 64;
+  for (uint64_t b = blockIdx.x * 4ull + (threadIdx.x >> 6); b < nblocks; b += (uint64_t) gridDim.x * 4) {
+    const uint64_t i = b * 64 + lane;
+    int32_t x0 = kEmptyMin, x1 = kEmptyMax, y0 = kEmptyMin;
+    if (i < np) {
+      const longlong2 p = reinterpret_cast<const longlong2*>(pts)[i];
+      const int32_t qx = quant(p.x), qy = quant(p.y);
+      qpts[i] = make_int2(qx, qy);
+      x0 = qx; x1 = qx; y0 = qy;
+    }
+    wave_min_max_min(x0, x1, y0);
+    if (lane == 0) qext[b] = make_int4(x0, x1, y0, 0);
+  }
+}
+
 // =============================================================================================
 // LBVH build
 // =============================================================================================
@@ -2024,7 +2046,7 @@ __host__ __device__ __forceinline__ size_t walk2_wave_lds(int top, int P = 2) { 
 //  schedule's walk + k_lsi2 blocks per CU no longer fit -- the skyline pointer took it to 100: 0.785 -> 0.852 ms.
 //  256 threads x 9 blocks: the compiler then aims below 57 VGPRs -- at 56, six blocks fit beside two of k_lsi2's 80)
 constexpr int kWalkCycleStamps = 7777;  // "stack_cap" value that turns the instrumented walk's counters into cycle stamps (tools/walk_stats_probe.py --cycles)
-template <bool STATS, int P>
+template <bool STATS, int P, bool PREP = false>
 __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
   extern __shared__ uint4 walk_smem[];
   const int lane = lane_id();
@@ -2067,25 +2089,69 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
     // end read the last point: no branch around a load, so the compiler batches them) and the root's boxes, which do not
     // depend on the points at all.  Left in `if (valid)` regions each load was waited for inside its own region: three
     // memory round trips before the first test, of the 23 k cycles a group's critical path is long.
+    // Prepared points (the query map's own vertices in their own order, quantised at its upload: PipArgs::qpts): 8 bytes
+    // per point and no arithmetic.  A FULL group -- all of its 128 positions exist: every group but the last -- needs no
+    // clamp and no select either, and its two loads share one address.  Prepared extents on top: a full group takes
+    // its {min x, max x, min y} as the two 16-byte entries of its 64-position halves, through the scalar cache (the
+    // constant address space: the table is written before this kernel starts), instead of reducing them over the wave.
+    // All of it wave-uniform.
+    typedef int i2_t __attribute__((ext_vector_type(2)));
+    typedef int i4_t __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(4))) i4_t* ext_ptr_t;
+    constexpr bool prep = PREP;  // (a kernel of its own: k_pip_walk2 has no register to spare for both heads)
+    const uint32_t gu = __builtin_amdgcn_readfirstlane(g32);
+    const bool full = prep && gu < (uint32_t) (A.n / GP);  // (a walk's n is below 2^32)
+    const bool ext = full && A.qext != nullptr;
     uint32_t ipl[P];
+    if (full) {
 #pragma unroll
-    for (int p = 0; p < P; p++) {
-      const uint64_t ipos = (uint64_t) g32 * GP + (uint64_t) p * 64 + lane;
-      valid[p] = ipos < A.n;
-      const uint64_t ipc = valid[p] ? ipos : A.n - 1;
-      ipl[p] = A.order ? A.order[ipc] : (uint32_t) ipc;
+      for (int p = 0; p < P; p++) { valid[p] = true; ipl[p] = 0; }
+    } else {
+#pragma unroll
+      for (int p = 0; p < P; p++) {
+        const uint64_t ipos = (uint64_t) g32 * GP + (uint64_t) p * 64 + lane;
+        valid[p] = ipos < A.n;
+        const uint64_t ipc = valid[p] ? ipos : A.n - 1;
+        ipl[p] = !prep && A.order ? A.order[ipc] : (uint32_t) ipc;
+      }
+    }
+    i4_t ext0 = {0, 0, 0, 0}, ext1 = {0, 0, 0, 0};
+    if (ext) {
+      const ext_ptr_t E = (ext_ptr_t) (uintptr_t) A.qext + (uint64_t) gu * P;
+      ext0 = E[0];
+      ext1 = E[1];
     }
     ll2_t ptl[P];
+    i2_t qpl[P];
+    if (full) {
+      const i2_t* const q = reinterpret_cast<const i2_t*>(A.qpts) + (uint64_t) gu * GP + lane;
 #pragma unroll
-    for (int p = 0; p < P; p++) ptl[p] = __builtin_nontemporal_load(reinterpret_cast<const ll2_t*>(A.pts) + ipl[p]);
+      for (int p = 0; p < P; p++) qpl[p] = __builtin_nontemporal_load(q + 64 * p);
+    } else if (prep) {
+#pragma unroll
+      for (int p = 0; p < P; p++) qpl[p] = __builtin_nontemporal_load(reinterpret_cast<const i2_t*>(A.qpts) + ipl[p]);
+    } else {
+#pragma unroll
+      for (int p = 0; p < P; p++) ptl[p] = __builtin_nontemporal_load(reinterpret_cast<const ll2_t*>(A.pts) + ipl[p]);
+    }
     const QBox root_box = T.lvl[T.top][lane];
     const uint64_t root_higher = sibling_order(T, T.top)[lane];
     if (STATS && cyc) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); RJ_CK(ck_load, ck); }
 #pragma unroll
     for (int p = 0; p < P; p++) {
-      qx[p] = valid[p] ? quant(ptl[p].x) : 0;
-      qy[p] = valid[p] ? quant(ptl[p].y) : 0;
-      qbest[p] = valid[p] ? 0x7FFFFFFF : -1;
+      if (full) {
+        qx[p] = qpl[p].x;
+        qy[p] = qpl[p].y;
+        qbest[p] = 0x7FFFFFFF;
+      } else if (prep) {
+        qx[p] = valid[p] ? qpl[p].x : 0;
+        qy[p] = valid[p] ? qpl[p].y : 0;
+        qbest[p] = valid[p] ? 0x7FFFFFFF : -1;
+      } else {
+        qx[p] = valid[p] ? quant(ptl[p].x) : 0;
+        qy[p] = valid[p] ? quant(ptl[p].y) : 0;
+        qbest[p] = valid[p] ? 0x7FFFFFFF : -1;
+      }
       cand_base[p] = (uint32_t) lane + (uint32_t) p * (kWalkList * 64);
       cand_at[p] = cand_base[p];
       sure_y0[p] = INT32_MIN;
@@ -2097,7 +2163,20 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
         if (sky[(uint32_t) qx[p] >> kSkyShift] <= (uint32_t) qy[p]) qbest[p] = -1;
     }
     int32_t gx0, gx1, gy0;
-    {
+    // (the prepared extent is the extent of ALL of the group's positions: a group with a lane the skyline has dismissed
+    //  computes its own, as does the group that holds the end of the range -- the traversal is the same either way)
+    bool ext_ok = ext;
+    if (ext && sky) {
+      bool gone = qbest[0] < 0;
+#pragma unroll
+      for (int p = 1; p < P; p++) gone = gone || qbest[p] < 0;
+      ext_ok = !__ballot(gone);
+    }
+    if (ext_ok) {
+      gx0 = ext0.x < ext1.x ? ext0.x : ext1.x;
+      gx1 = ext0.y > ext1.y ? ext0.y : ext1.y;
+      gy0 = ext0.z < ext1.z ? ext0.z : ext1.z;
+    } else {
       const bool l0 = qbest[0] >= 0, l1 = qbest[1] >= 0;
       const int32_t a0 = l0 ? qx[0] : kEmptyMin, a1 = l1 ? qx[1] : kEmptyMin;
       const int32_t b0 = l0 ? qx[0] : kEmptyMax, b1 = l1 ? qx[1] : kEmptyMax;
@@ -2109,8 +2188,8 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
         const int32_t ap = lp ? qx[p] : kEmptyMin, bp = lp ? qx[p] : kEmptyMax, cp = lp ? qy[p] : kEmptyMin;
         gx0 = gx0 < ap ? gx0 : ap; gx1 = gx1 > bp ? gx1 : bp; gy0 = gy0 < cp ? gy0 : cp;
       }
+      wave_min_max_min(gx0, gx1, gy0);
     }
-    wave_min_max_min(gx0, gx1, gy0);
     int32_t gbest = 0x7FFFFFFF;  // wave max of both sets' qbest
     bool gbest_stale = false;    // ... some lane's bound has dropped since it was last reduced (wave-uniform)
 
@@ -2296,7 +2375,7 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
       const uint64_t ipos = (uint64_t) g32 * GP + (uint64_t) p * 64 + lane;
       // (the point's index is read again rather than held in a register through the traversal: the kernel keeps to 56
       //  VGPRs, six of its blocks fit beside two of k_lsi2)
-      ipv[p] = A.order ? A.order[valid[p] ? ipos : A.n - 1] : (uint32_t) ipos;
+      ipv[p] = !PREP && A.order ? A.order[valid[p] ? ipos : A.n - 1] : (uint32_t) ipos;
       donev[p] = valid[p] && !ovf && (cand_at[p] == cand_base[p] || sure_y0[p] != INT32_MIN);
       const bool hit = donev[p] && cand_at[p] != cand_base[p];
       const uint32_t slot = hit ? cand[cand_base[p]] : 0u;
@@ -2383,6 +2462,8 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
 // of its blocks fit beside two of k_lsi2's 80 on a SIMD's 512.
 __global__ __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(96))) __attribute__((amdgpu_num_vgpr(28))) void k_pip_walk2(PipArgs A) { pip_walk_many<false, 2>(A); }
 __global__ __launch_bounds__(256, 4) __attribute__((amdgpu_num_sgpr(96))) void k_pip_walk2_stats(PipArgs A) { pip_walk_many<true, 2>(A); }
+// ... over the query map's prepared points (PipArgs::qpts, qext): the same body and budget with the other head
+__global__ __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(96))) __attribute__((amdgpu_num_vgpr(28))) void k_pip_walk2_prepared(PipArgs A) { pip_walk_many<false, 2, true>(A); }
 
 
 // The walk's leftovers: the exact predicate (pip.h:36-95, as in k_pip's evaluate) over each listed point's complete
@@ -2523,6 +2604,12 @@ hipError_t launch_build_segs(hipStream_t st, const int64_t* pts, const uint32_t*
   if (ne == 0) return hipSuccess;
   hipLaunchKernelGGL(k_build_segs, dim3(grid_for(ne, 256, 8192)), dim3(256), 0, st, pts, edge_begin,
                      nc, ne, seg, edge_chain, ccode);
+  return hipGetLastError();
+}
+
+hipError_t launch_prepare_points(hipStream_t st, const int64_t* pts, uint64_t np, int2* qpts, int4* qext) {
+  if (np == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_prepare_points, dim3(grid_for(np, 256, 8192)), dim3(256), 0, st, pts, np, qpts, qext);
   return hipGetLastError();
 }
 
@@ -2825,6 +2912,8 @@ hipError_t launch_pip_walk2(hipStream_t st, const PipArgs& a_in, int max_blocks,
   note("k_pip_walk2", grid, 2);
   if (stats)
     hipLaunchKernelGGL(k_pip_walk2_stats, dim3(grid), dim3(256), lds, st, a);
+  else if (a.qpts)
+    hipLaunchKernelGGL(k_pip_walk2_prepared, dim3(grid), dim3(256), lds, st, a);  // (the plan and the profiles' tables know both as k_pip_walk2)
   else
     hipLaunchKernelGGL(k_pip_walk2, dim3(grid), dim3(256), lds, st, a);
   return hipGetLastError();

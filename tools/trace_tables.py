@@ -18,6 +18,10 @@ for r in csv.DictReader(open(a.csv)):
     grid = int(r.get("Grid_Size_X", r.get("Grid_Size", 0)) or 0)
     rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), name, grid // max(1, wg)))
 rows.sort()
+# k_pip_walk2_prepared (the same body over the query map's prepared points) is what the plan calls k_pip_walk2: in a trace
+# that holds it, it takes that name and k_pip_walk2 proper (caller-owned arrays) is told apart as "k_pip_walk2 (int64)"
+if any(r[2] == "k_pip_walk2_prepared" for r in rows):
+    rows = [(s, e, {"k_pip_walk2_prepared": "k_pip_walk2", "k_pip_walk2": "k_pip_walk2 (int64)"}.get(n, n), b) for s, e, n, b in rows]
 if a.regimes:
     acc = collections.defaultdict(list)
     for s, e, n, b in rows:
