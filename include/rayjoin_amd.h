@@ -670,6 +670,53 @@ int rj_map_simplify(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint3
                     uint64_t tol_lo, uint64_t tol_hi, uint32_t flags, uint64_t point_capacity, int64_t* out_xy_dev,
                     uint32_t* out_row_index_dev, uint32_t* origin_dev /* may be NULL */, rj_simplify_counts* counts);
 
+/* extends: the faces of a chain map computed from its geometry alone, on the device -- the label side of "a user's data
+ * in, a valid planar map out".  Input: xy_dev[2 np], row_index_dev[nc + 1], the contract and the size limits of
+ * rj_map_rings, without labels: chains meet only at their end points, a chain may have a single point.  flags must be 0.
+ * The definition, in full in rayjoin_amd/csrc/rj_faces.h: the rings of the map are those of rj_map_rings with no face
+ * involved, ascending by leader; a ring with area2 > 0 is a shell, every other ring a hole (the outside of a connected
+ * component, or an isolated tree).  A hole's ray goes up from its top, its largest (y, x); the first ceiling edge above
+ * it (the half-open rule and the exact order of rj_rings_polygons, over the ceiling edges of ALL rings) names the ring
+ * above; following that until a shell is reached gives the hole's face, and a walk that ends with nothing above puts it
+ * in face 0, the unbounded face.  Face k (1-based) is the k-th shell by ascending leader.
+ * Output, caller-owned device memory: left_dev[nc] / right_dev[nc] = the face of the ring of half-chain 2 c / 2 c + 1 (0
+ * for a chain whose points are all equal: n_skipped); faces_dev[face_capacity] (may be NULL), record k - 1 for face k:
+ * its shell's leader, its holes, area2 = the shell's plus its holes' = twice the face's area (an exact int128), its label.
+ * Counts: n_faces (shells), n_rings, n_holes (holes inside a shell), n_outer (holes of face 0), n_skipped, n_dangling
+ * (chains that are not skipped with left == right: bridges and dangles), n_conflicts.
+ * in_left_dev / in_right_dev: both NULL, or both given -- the labels to check.  Then label of face k = the given label of
+ * its shell's leader half-chain (face 0: 0), and n_conflicts = the half-chains that are not skipped and whose given label
+ * differs from the label of their computed face: 0 means the labels and the geometry describe the same partition
+ * (whether label is injective the caller reads from faces_dev).  Without labels every label is 0.
+ * faces_dev NULL: no records, face_capacity is ignored, nothing overflows.  Otherwise RJ_E_OVERFLOW when n_faces >
+ * face_capacity: *counts holds the true counts, left_dev / right_dev are written in full, nothing is written beyond the
+ * capacity.  nc == 0 is valid.  RJ_E_INVALID, with nothing written: a map that fails the checks of rj_map_rings, a
+ * nonzero flag, one label pointer without the other.  RJ_E_INTERNAL when a round budget of 33 runs out.  On a map
+ * without RJ_CROSS_OVERLAP / RJ_CROSS_EQUAL records the result equals rj_map_rings with one constant label followed by
+ * rj_rings_polygons' parent[]; it is fully determined for every input.  Runs on the handle's stream with one host sync,
+ * at the end; scratch (rj_faces.h has the bytes per chain, point and registration) is allocated per call and freed; no
+ * map, index or option of the handle changes.
+ * Coordinates are expected scaled to the range: the grid that keeps a hole from testing every edge has cells of at
+ * least 2^15 units, so a map drawn in single units lies in one cell and costs holes x edges -- with the same result.
+ * For tests, through rj_set_debug_option: "faces_shift" (15..47, 0: choose) is where the search for the grid's shift
+ * starts; the registration bound can still make it coarser, never the result different.  What the last call took,
+ * through rj_get_option: "faces_last_shift", "faces_last_registrations", "faces_last_ray_tests" (candidate tests),
+ * "faces_last_cells" (cells that rays visited), "faces_last_us0" .. "faces_last_us5" (HIP-event microseconds: the ring
+ * stages, tops and kinds, the grid, the rays, parents and faces, all; -1: not reached). */
+typedef struct {
+  uint32_t leader, n_holes;
+  int32_t label;
+  uint32_t _pad;
+  uint64_t area2_lo;
+  int64_t area2_hi;
+} rj_face; /* 32 bytes */
+typedef struct {
+  uint64_t n_faces, n_rings, n_holes, n_outer, n_skipped, n_dangling, n_conflicts;
+} rj_faces_counts;
+int rj_map_faces(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc,
+                 const int32_t* in_left_dev, const int32_t* in_right_dev, uint32_t flags, uint64_t face_capacity,
+                 int32_t* left_dev, int32_t* right_dev, rj_face* faces_dev /* may be NULL */, rj_faces_counts* counts);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

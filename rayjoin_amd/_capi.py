@@ -49,6 +49,9 @@ CROSSINGS_COUNTS = ("n_found", "n_proper", "n_touch", "n_overlap", "n_equal", "n
 RJ_NODE_DROP_LAST = 1  # rj_map_node flags
 NODE_COUNTS = ("n_points", "n_edges", "n_cuts", "n_cut_edges", "n_max_cuts", "n_used", "n_proper", "n_equal")
 SIMPLIFY_COUNTS = ("n_points", "n_removed", "n_rounds", "n_closed", "n_pinned_extra", "n_max_round")
+# rj_face: one face of rj_map_faces -- its shell's leader half-chain, its holes, its label, twice its area
+MAP_FACE_DTYPE = np.dtype([("leader", "<u4"), ("n_holes", "<u4"), ("label", "<i4"), ("_pad", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
+MAP_FACES_COUNTS = ("n_faces", "n_rings", "n_holes", "n_outer", "n_skipped", "n_dangling", "n_conflicts")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
 _vp, _u64, _i64, _int = C.c_void_p, C.c_uint64, C.c_int64, C.c_int
@@ -103,6 +106,7 @@ SYMBOLS = {
     "rj_map_crossings": (_int, [_vp, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _vp, _vp]),
     "rj_map_node": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
     "rj_map_simplify": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
+    "rj_map_faces": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -215,6 +219,15 @@ class CrossingsOverflow(RayJoinError):
 class NodeOverflow(RayJoinError):
     """RJ_E_OVERFLOW of rj_map_node: counts = dict(n_points, n_edges, n_cuts, n_cut_edges, n_max_cuts, n_used, n_proper, n_equal),
     the true counts"""
+
+    def __init__(self, msg, counts):
+        super().__init__(RJ_E_OVERFLOW, msg)
+        self.counts = counts
+
+
+class FacesOverflow(RayJoinError):
+    """RJ_E_OVERFLOW of rj_map_faces: counts = dict(n_faces, n_rings, n_holes, n_outer, n_skipped, n_dangling, n_conflicts), the
+    true counts; left / right are written in full"""
 
     def __init__(self, msg, counts):
         super().__init__(RJ_E_OVERFLOW, msg)
@@ -654,6 +667,20 @@ class Handle:
         named = dict(zip(SIMPLIFY_COUNTS, (int(v) for v in counts)))
         if rc == RJ_E_OVERFLOW:
             raise SimplifyOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        self._check(rc)
+        return named
+
+    def map_faces(self, xy_dev, n_points, row_index_dev, n_chains, left_dev, right_dev, faces_dev=None, face_capacity=0, in_left_dev=None,
+                  in_right_dev=None, flags=0):
+        """rj_map_faces of a chain map in device memory: the computed faces into left_dev / right_dev (n_chains int32 each) and,
+        where faces_dev is given, `face_capacity` rj_face records; in_left_dev / in_right_dev: the labels to check, or None.
+        Returns the counts as a dict (MAP_FACES_COUNTS); FacesOverflow (with the true counts) past the capacity."""
+        counts = (_u64 * 7)()
+        rc = self.L.rj_map_faces(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains), _ptr(in_left_dev), _ptr(in_right_dev),
+                                 int(flags), int(face_capacity), _ptr(left_dev), _ptr(right_dev), _ptr(faces_dev), counts)
+        named = dict(zip(MAP_FACES_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise FacesOverflow(self.L.rj_last_error_string(self.h).decode(), named)
         self._check(rc)
         return named
 

@@ -15,6 +15,7 @@
 
 #include "../../include/rayjoin_amd.h"
 #include "rj_crossings.h"
+#include "rj_faces.h"
 #include "rj_node.h"
 #include "rj_kernels.h"
 #include "rj_overlay_dev.h"
@@ -282,6 +283,8 @@ struct rj_handle_s {
   NodeReport node_report = {{-1, -1, -1, -1, -1, -1}};  // what the stages of the last rj_map_node took (reports only)
   int debug_simplify_all_points = 0;  // rj_map_simplify: 1 = every round looks at every point, no work list (tests: the same result)
   SimplifyReport simplify_report = {{-1, -1, -1, -1, -1, -1}};  // what the last rj_map_simplify took (reports only)
+  int debug_faces_shift = 0;  // rj_map_faces: where the search for the grid's shift starts (0: choose; tests: the same result)
+  FacesReport faces_report = {{-1, -1, -1, -1, -1, -1}, 0, 0, 0, 0};  // what the last rj_map_faces chose and took (reports only)
   uint32_t stitch_stats[4] = {0, 0, 0, 0};  // the last run cutting: ranking rounds, incidences on closed loops, rounds of the second ranking, closed chains
   char* strip_scratch = nullptr;  // grow-only temporaries of the column index's build
   size_t strip_scratch_bytes = 0;
@@ -634,6 +637,7 @@ const Option kOptions[] = {
     {"cross_extent_factor", true, &rj_handle_s::debug_cross_extent_factor, 0, 1 << 20},  // ... a cell is this many mean extents wide (0: 8)
     {"cross_reg_factor", true, &rj_handle_s::debug_cross_reg_factor, 0, 1 << 20},  // ... registrations per edge allowed (0: 4)
     {"simplify_all_points", true, &rj_handle_s::debug_simplify_all_points, 0, 1},  // rj_map_simplify: every round over all points (0: the work list)
+    {"faces_shift", true, &rj_handle_s::debug_faces_shift, 15, 47, "faces_shift: 0 (choose) or 15..47", nullptr, nullptr, 1, {0}},  // rj_map_faces: the grid's shift
 };
 
 const Option* find_option(const char* name, bool debug) {
@@ -718,6 +722,11 @@ const Report kReports[] = {
     {"simplify_late_rounds", 0, RJ_READ(h->simplify_report.late_rounds)},   // ... the rounds from the eleventh on: how many,
     {"simplify_late_list", 0, RJ_READ(h->simplify_report.late_list)},       // the points they looked at,
     {"simplify_late_us", 0, RJ_READ((int64_t) (h->simplify_report.late_ms * 1000.0f))},  // their time
+    {"faces_last_shift", 0, RJ_READ(h->faces_report.shift)},  // the last rj_map_faces: its grid, its work, its stages
+    {"faces_last_registrations", 0, RJ_READ(h->faces_report.registrations)},
+    {"faces_last_ray_tests", 0, RJ_READ(h->faces_report.ray_tests)},
+    {"faces_last_cells", 0, RJ_READ(h->faces_report.cells)},
+    {"faces_last_us", 6, RJ_READ(h->faces_report.ms[k] < 0 ? -1 : (int64_t) (h->faces_report.ms[k] * 1000.0f))},  // rings, tops and kinds, grid, rays, parents and faces, all
     {"comm_ranks", 0, read_comm_ranks},
     {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
     {"pip_share_blocks", 0, RJ_READ(h->last_pip_share ? h->last_pip_share : h->pip_share_blocks())},
@@ -2993,6 +3002,40 @@ int rj_map_simplify(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint3
   memcpy(counts, &m.counts, sizeof(*counts));
   if (counts->n_points > point_capacity)
     return fail(h, RJ_E_OVERFLOW, "rj_map_simplify: %llu points; capacity %llu", (unsigned long long) counts->n_points, (unsigned long long) point_capacity);
+  return RJ_OK;
+}
+
+int rj_map_faces(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc, const int32_t* in_left_dev,
+                 const int32_t* in_right_dev, uint32_t flags, uint64_t face_capacity, int32_t* left_dev, int32_t* right_dev, rj_face* faces_dev,
+                 rj_faces_counts* counts) {
+  static_assert(sizeof(rj_face) == 32 && sizeof(faces::Face) == 32 && sizeof(rj_faces_counts) == sizeof(faces::Counts), "layouts");
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_map_faces: counts is null");
+  memset(counts, 0, sizeof(*counts));
+  if (flags) return fail(h, RJ_E_INVALID, "rj_map_faces: unknown flags 0x%x", flags);
+  if (!in_left_dev != !in_right_dev) return fail(h, RJ_E_INVALID, "rj_map_faces: the labels to check are both null or both given");
+  if ((np && !xy_dev) || (nc && !row_index_dev)) return fail(h, RJ_E_INVALID, "rj_map_faces: null input array");
+  if (nc >= (1ull << 31) || np >= (1ull << 32) || nc > np || 2 * (np - nc) >= (1ull << 32))
+    return fail(h, RJ_E_INVALID, "rj_map_faces: nc < 2^31, nc <= np < 2^32 and 2 (np - nc) < 2^32");
+  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_faces: points without chains");
+  if (nc && (!left_dev || !right_dev)) return fail(h, RJ_E_INVALID, "rj_map_faces: null output");
+  if (int r = set_device(h)) return r;
+  h->faces_report = FacesReport{{-1, -1, -1, -1, -1, -1}, 0, 0, 0, 0};
+  if (nc == 0) return RJ_OK;
+  rings::Meta rm;
+  polygons::Meta pm;
+  faces::Meta m;
+  RJ_HIP(h, map_faces_device(h->stream, xy_dev, np, row_index_dev, nc, in_left_dev, in_right_dev, h->debug_faces_shift, face_capacity, left_dev,
+                             right_dev, reinterpret_cast<faces::Face*>(faces_dev), &rm, &pm, &m, &h->faces_report));
+  if (rm.bad_map == rings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_faces: row_index must start at 0");
+  if (rm.bad_map == rings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_faces: row_index must end at np");
+  if (rm.bad_map == rings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_faces: row_index must ascend (a chain has no point)");
+  if (rm.bad_map) return fail(h, RJ_E_INVALID, "rj_map_faces: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  if (rm.unfinished) return fail(h, RJ_E_INTERNAL, "rj_map_faces: a ring was not closed within %d doubling steps", rings::kMaxRounds);
+  if (pm.unfinished) return fail(h, RJ_E_INTERNAL, "rj_map_faces: a hole did not reach its shell within %d jumping steps", faces::kMaxRounds);
+  memcpy(counts, &m.counts, sizeof(*counts));
+  if (faces_dev && counts->n_faces > face_capacity)
+    return fail(h, RJ_E_OVERFLOW, "rj_map_faces: %llu faces; capacity %llu", (unsigned long long) counts->n_faces, (unsigned long long) face_capacity);
   return RJ_OK;
 }
 

@@ -132,7 +132,8 @@ RJ_RHD U128 sub(U128 a, U128 b) {
 RJ_RHD U128 limbs(__int128 v) { return U128{(uint64_t) v, (uint64_t) (v >> 64)}; }
 RJ_RHD __int128 cross(int64_t ax, int64_t ay, int64_t bx, int64_t by) { return (__int128) ax * by - (__int128) ay * bx; }
 
-RJ_RHD int32_t face_of(uint32_t h, const int32_t* left, const int32_t* right) { return (h & 1) ? right[h >> 1] : left[h >> 1]; }
+// (left null: a map without labels, every face 0 -- rj_faces.h runs the ring stages that way)
+RJ_RHD int32_t face_of(uint32_t h, const int32_t* left, const int32_t* right) { return !left ? 0 : ((h & 1) ? right[h >> 1] : left[h >> 1]); }
 RJ_RHD uint32_t edges_of(uint32_t h, const uint32_t* row) { return row[(h >> 1) + 1] - row[h >> 1] - 1; }
 RJ_RHD bool skipped(const Inc& a) { return a.dx == 0 && a.dy == 0; }
 RJ_RHD bool same_point(const Inc& a, const Inc& b) { return a.x == b.x && a.y == b.y; }
@@ -357,6 +358,11 @@ RJ_RHD bool ring_emit(uint32_t r, const uint64_t* skeys, const Slots* base, cons
 // round budget).  Allocates and frees its scratch; synchronises the stream once, at the end.
 hipError_t map_rings_device(hipStream_t st, const int64_t* xy, uint64_t np, const uint32_t* row_index, const int32_t* left,
                             const int32_t* right, uint64_t nc, uint32_t flags, const rings::Out& out, rings::Meta* result);
+// the same stages enqueued without a wait, in the caller's scratch (rj_rings.hip has the contract): rj_map_faces runs them
+// in front of its own, with left and right null
+hipError_t map_rings_enqueue(hipStream_t st, const int64_t* xy, uint64_t np, const uint32_t* row_index, const int32_t* left,
+                             const int32_t* right, uint64_t nc, uint32_t flags, const rings::Out& out, char* scratch, size_t* bytes,
+                             rings::Meta** meta_dev);
 #endif
 
 }  // namespace rj

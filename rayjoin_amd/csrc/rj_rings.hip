@@ -153,20 +153,17 @@ __global__ __launch_bounds__(kThreads) void k_rg_emit(uint32_t ni, const uint64_
 
 }  // namespace
 
-hipError_t map_rings_device(hipStream_t st, const int64_t* xy, uint64_t np, const uint32_t* row, const int32_t* left, const int32_t* right,
-                            uint64_t nc64, uint32_t flags, const Out& out, Meta* result) {
-  memset(result, 0, sizeof(Meta));
+// the stages of rj_map_rings enqueued on st without a wait (nc64 > 0).  scratch null: only *bytes, the scratch this map
+// needs, is set.  Otherwise the stages run in `scratch` (that many bytes), *meta_dev is where their Meta lies in it, and
+// the caller waits for the stream before it reads that or lets the scratch go.  left / right null: every face is 0 (the
+// rings then ascend by leader alone).
+hipError_t map_rings_enqueue(hipStream_t st, const int64_t* xy, uint64_t np, const uint32_t* row, const int32_t* left, const int32_t* right,
+                             uint64_t nc64, uint32_t flags, const Out& out, char* scratch, size_t* bytes, Meta** meta_dev) {
   Out o = out;
   if (flags & kNoPoints) {
     o.ring_row = nullptr;
     o.ring_xy = nullptr;
     o.point_cap = 0;
-  }
-  if (nc64 == 0) {  // no rings: the CSRs' one entry, where the caller has arrays
-    hipError_t e = hipSuccess;
-    if (o.ring_first) e = hipMemsetAsync(o.ring_first, 0, 4, st);
-    if (e == hipSuccess && o.ring_row) e = hipMemsetAsync(o.ring_row, 0, 4, st);
-    return e == hipSuccess ? hipStreamSynchronize(st) : e;
   }
   const uint32_t nc = (uint32_t) nc64, ni = 2 * nc;
   const uint64_t n1 = (uint64_t) ni + 1;
@@ -213,11 +210,12 @@ hipError_t map_rings_device(hipStream_t st, const int64_t* xy, uint64_t np, cons
     temp = A.take<char>(temp_bytes);
   };
   carve();
-  char* scratch = nullptr;
-  hipError_t e = hipMalloc((void**) &scratch, A.used);
-  if (e != hipSuccess) return e;
+  *bytes = A.used;
+  if (!scratch) return hipSuccess;
   A.base = scratch;
   carve();
+  *meta_dev = meta;
+  hipError_t e = hipSuccess;
   // the five junction arrays are dead once next[] is known: the ring keys and their sorted form live there later
   uint32_t *iota = junction, *sv = junction + ni, *pos = junction + 2 * (uint64_t) ni, *head = junction + 3 * (uint64_t) ni,
            *begin = junction + 4 * (uint64_t) ni, *last_of = head;  // (head[] is dead behind its scan)
@@ -267,11 +265,30 @@ hipError_t map_rings_device(hipStream_t st, const int64_t* xy, uint64_t np, cons
     if ((e = rocprim::exclusive_scan(temp, tb, (const U128*) cross_at, xbase, U128{0, 0}, (size_t) n1, U128Sum(), st)) != hipSuccess) break;
     hipLaunchKernelGGL(k_rg_emit, dim3(Br), dim3(kThreads), 0, st, ni, (const uint64_t*) skeys, (const Slots*) base, (const U128*) xbase,
                        (const uint32_t*) mixed, o, meta);
-    if ((e = hipGetLastError()) != hipSuccess) break;
-    // the one read-back
-    if ((e = hipMemcpyAsync(result, meta, sizeof(Meta), hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-    e = hipStreamSynchronize(st);
+    e = hipGetLastError();
   } while (0);
+  return e;
+}
+
+hipError_t map_rings_device(hipStream_t st, const int64_t* xy, uint64_t np, const uint32_t* row, const int32_t* left, const int32_t* right,
+                            uint64_t nc64, uint32_t flags, const Out& out, Meta* result) {
+  memset(result, 0, sizeof(Meta));
+  if (nc64 == 0) {  // no rings: the CSRs' one entry, where the caller has arrays
+    hipError_t e = hipSuccess;
+    if (out.ring_first) e = hipMemsetAsync(out.ring_first, 0, 4, st);
+    if (e == hipSuccess && out.ring_row && !(flags & kNoPoints)) e = hipMemsetAsync(out.ring_row, 0, 4, st);
+    return e == hipSuccess ? hipStreamSynchronize(st) : e;
+  }
+  size_t bytes = 0;
+  Meta* meta = nullptr;
+  hipError_t e = map_rings_enqueue(st, xy, np, row, left, right, nc64, flags, out, nullptr, &bytes, &meta);
+  if (e != hipSuccess) return e;
+  char* scratch = nullptr;
+  if ((e = hipMalloc((void**) &scratch, bytes)) != hipSuccess) return e;
+  e = map_rings_enqueue(st, xy, np, row, left, right, nc64, flags, out, scratch, &bytes, &meta);
+  // the one read-back
+  if (e == hipSuccess) e = hipMemcpyAsync(result, meta, sizeof(Meta), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) (void) hipStreamSynchronize(st);  // (nothing of this call still runs when its scratch goes)
   const hipError_t fe = hipFree(scratch);
   return e != hipSuccess ? e : fe;

@@ -36,6 +36,10 @@
          the device.  A border that two faces share is one chain: both polygons are thinned identically, no sliver or gap
          opens, the ends of every chain stay, left / right stay valid.  It may push a chain across another one: check=True
          also returns the counts of Crossings() on the result
+  map_faces(handle, ...) / DeviceChainMap.Faces(handle, check=) / DeviceNodedMap.Faces(handle) -> DeviceFacedMap
+      -- the label side (rj_map_faces): the faces of a chain map computed from its geometry alone, a face number on each
+         side of every chain, the face records with exact areas; check=True tells whether a map's own labels describe the
+         partition its geometry has (counts["n_conflicts"])
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -565,6 +569,13 @@ class DeviceNodedMap:
         return (self.xy.to_host(np.int64, 2 * self.n_points).reshape(-1, 2), self.row_index.to_host(np.uint32, self.n_chains + 1),
                 self.edge_origin.to_host(np.uint32, self.n_edges) if self.edge_origin is not None else None)
 
+    def Faces(self, handle, left=None, right=None):
+        """map_faces of this map, on the device: the faces of the noded linework from its geometry alone, as a DeviceFacedMap.
+        left / right (device int32 arrays, both or neither): the caller's labels, which noding left valid, to check"""
+        if (left is None) != (right is None):
+            raise ValueError("left and right go together")
+        return map_faces(handle, self.xy, self.n_points, self.row_index, self.n_chains, labels=None if left is None else (left, right))
+
     def free(self):
         for b in (self.xy, self.row_index, self.edge_origin):
             if b is not None:
@@ -750,9 +761,72 @@ class DeviceChainMap:
         n_edges.  check: -> (the map, the counts of Crossings() on it) -- thinning can push a chain across another one"""
         return _simplified_chain_map(handle, self, tol, check, capacity)
 
+    def Faces(self, handle, check=False):
+        """map_faces of this map, on the device: its faces computed from the geometry alone, as a DeviceFacedMap of its own.
+        check: this map's own left / right go in as the labels to check -- counts["n_conflicts"] == 0 tells that they and
+        the geometry describe the same partition, and the records' label is the given label of every computed face"""
+        return map_faces(handle, self.xy, self.n_points, self.row_index, self.n_chains, labels=(self.left, self.right) if check else None)
+
     def free(self):
         for b in (self.xy, self.row_index, self.left, self.right):
             b.free()
+
+
+def map_faces(handle, xy, n_points, row_index, n_chains, labels=None, records=True):
+    """The faces of a chain map in device memory computed from its geometry alone (rj_map_faces; int64 xy, uint32
+    row_index, no labels needed) as a DeviceFacedMap: a DeviceChainMap with copies of xy / row_index whose left / right are
+    the computed faces -- 0 the unbounded face, k the k-th bounded face by its outer ring's leader half-chain -- so Rings(),
+    Crossings(), Simplify() and DeviceContext.InstallMap take it.  labels = (left, right) device arrays: the labels to
+    check, counts["n_conflicts"] the half-chains whose given label is not that of their computed face.  records: also the
+    face records (.faces, MAP_FACE_DTYPE rows: leader, n_holes, label, area2).  One call of rj_map_faces either way: the
+    records are written into room for 2 n_chains of them (no map has more rings; 64 bytes per chain until the call
+    returns) and copied to a buffer of their own size.  counts: MAP_FACES_COUNTS with n_chains, n_points, n_edges.
+    The grid of rj_map_faces has cells of at least 2^15 units: coordinates are expected scaled to the range, a map drawn
+    in single units gets the same faces at the cost of every hole against every edge (rj_faces.h, UNITS)."""
+    n_points, n_chains = int(n_points), int(n_chains)
+    in_left, in_right = labels if labels is not None else (None, None)
+    rec = _capi.MAP_FACE_DTYPE.itemsize
+    bufs, faces, room, done = [], None, None, False
+    try:
+        bufs.append(handle.alloc(16 * max(1, n_points)).from_device(xy, 16 * n_points))
+        bufs.append(handle.alloc(4 * (n_chains + 1)))
+        bufs.append(handle.alloc(4 * max(1, n_chains)))
+        bufs.append(handle.alloc(4 * max(1, n_chains)))
+        if n_chains:
+            bufs[1].from_device(row_index, 4 * (n_chains + 1))
+        else:
+            bufs[1].from_host(np.zeros(1, np.uint32))
+        if records:
+            room = handle.alloc(rec * max(1, 2 * n_chains))
+        counts = handle.map_faces(bufs[0], n_points, bufs[1], n_chains, bufs[2], bufs[3], room, 2 * n_chains, in_left, in_right)
+        if records:
+            faces = handle.alloc(rec * max(1, counts["n_faces"]))
+            if counts["n_faces"]:
+                faces.from_device(room, rec * counts["n_faces"])
+        done = True
+    finally:
+        for b in [room] + ([] if done else bufs + [faces]):
+            if b is not None:
+                b.free()
+    return DeviceFacedMap(*bufs, dict(counts, n_chains=n_chains, n_points=n_points, n_edges=n_points - n_chains), faces)
+
+
+class DeviceFacedMap(DeviceChainMap):
+    """A chain map in device memory whose left / right are the faces that rj_map_faces computed, with faces (MAP_FACE_DTYPE rows
+    as a DeviceBuffer, or None) and the counts n_faces, n_rings, n_holes, n_outer, n_skipped, n_dangling, n_conflicts."""
+
+    def __init__(self, xy, row_index, left, right, counts, faces):
+        super().__init__(xy, row_index, left, right, counts)
+        self.faces, self.n_faces = faces, int(counts["n_faces"])
+
+    def faces_to_host(self):
+        """-> the face records (MAP_FACE_DTYPE), record k - 1 for face k"""
+        return self.faces.to_host(_capi.MAP_FACE_DTYPE, self.n_faces)
+
+    def free(self):
+        super().free()
+        if self.faces is not None:
+            self.faces.free()
 
 
 class DevicePolygons:
