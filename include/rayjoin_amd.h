@@ -620,6 +620,58 @@ int rj_map_node(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t*
                 const rj_crossing* cross_dev, uint64_t n_cross, uint32_t flags, uint64_t point_capacity,
                 int64_t* out_xy_dev, uint32_t* out_row_index_dev, uint32_t* edge_origin_dev, rj_node_counts* counts);
 
+/* ---- snapping: cut edges at their rounded proper crossings too ----------------------------------- */
+#define RJ_SNAP_DROP_LAST 1u /* as RJ_NODE_DROP_LAST */
+
+typedef struct {
+  uint64_t n_points, n_edges;   /* as rj_node_counts: of the output; n_edges = ne + n_cuts in either layout */
+  uint64_t n_cuts, n_cut_edges, n_max_cuts; /* inserted points of all kinds; input edges with a cut; the most on one edge */
+  uint64_t n_used, n_proper, n_equal;       /* records of kind TOUCH or OVERLAP; PROPER records (stale ones included); EQUAL records */
+  uint64_t n_exact;   /* PROPER records whose crossing point is an integer point: nothing was rounded */
+  uint64_t n_at_end;  /* (PROPER record, edge) combinations left uncut because the rounded point is an end point of that edge */
+  uint64_t n_stale;   /* PROPER records that do not fit the geometry: they cut nothing */
+} rj_snap_counts;
+
+/* extends: the missing link between "this map has crossings" and "a planar map" -- a layer whose polygons overlap, a
+ * self-crossing ring, an overlay output whose truncated cut points made a crossing.  rj_map_node plus one cut at the
+ * rounded point of every RJ_CROSS_PROPER record: both edges are cut at the same integer point and the crossing becomes a
+ * shared vertex.  Moving a point by up to half a unit can make new crossings, so ONE call does not promise a planar
+ * map: the caller repeats rj_map_crossings and rj_map_snap until a check finds nothing (ops.map_snap_rounds).  That the
+ * rounds end is measured, not guaranteed (two or three on ordinary input, many on fans of near-parallel long
+ * edges); the counts of both calls report the progress.
+ * Input: the map and cross_dev[n_cross] exactly as rj_map_node takes them, with the same checks and the same codes;
+ * RJ_SNAP_DROP_LAST means what RJ_NODE_DROP_LAST means.  The definition, in full in rayjoin_amd/csrc/rj_snap.h:
+ * TOUCH and OVERLAP records cut exactly as in rj_map_node (four tests per record, a cut only where the geometry holds).
+ * A PROPER record (e, f), e < f, with A, B the points of e, C, D the points of f, r = B - A, s = D - C: den = r x s,
+ * tn = (C - A) x s, un = (C - A) x r (int128, below 2^95), all three negated when den < 0.  den == 0, or not
+ * 0 < tn < den, or not 0 < un < den: the record is stale, cuts nothing and is counted in n_stale.  Otherwise
+ * q = A + (rnd(r.x tn / den), rnd(r.y tn / den)) with rnd(v) = floor(v + 1/2) -- halves toward +infinity whatever the
+ * direction of the edge, exact in integers, always computed from the lower-numbered edge.  q is inserted into e unless
+ * it equals A or B and into f unless it equals C or D; each such drop counts once in n_at_end and the other edge is
+ * still cut there.  q lies in the closed boxes of both edges: coordinates stay in range.  n_exact: the records whose
+ * point needed no rounding.
+ * Output, caller-owned device memory, in the layout of rj_map_node: out_xy_dev[2 point_capacity],
+ * out_row_index_dev[nc + 1], edge_origin_dev[n_edges] (may be NULL).  After point p come the cuts of edge p - c,
+ * ascending by the pair (|q.major - a.major|, |q.minor - a.minor|), the major axis of an edge being x when |dx| >= |dy|,
+ * else y -- a monotone function of the exact parameter along the edge for points on it and for rounded crossing points;
+ * equal pairs are equal points, which appear once.  Chains, their number and their order do not change: the caller's
+ * left / right arrays stay valid as chain labels (what they mean where polygons overlapped is rj_map_faces' question).
+ * On records without a PROPER kind the output arrays and the eight counts shared with rj_node_counts equal
+ * rj_map_node's bit for bit.  Fully determined, independent of every tuning choice.
+ * point_capacity 0 (arrays may be NULL) is the sizing call; RJ_E_OVERFLOW when n_points > point_capacity: *counts holds
+ * the true counts and nothing is written.  nc == 0, n_cross == 0 and cross_dev == NULL with n_cross == 0 are valid;
+ * with no records the output is a copy of the input.  RJ_E_INVALID, with nothing written: every case of rj_map_node
+ * (the map checks of rj_map_crossings, an unknown flag bit, n_cross >= 2^31, np + n_cuts >= 2^32, a record with
+ * eid[0] >= eid[1], eid[1] >= ne or a kind outside 1..4, a record that names a zero-length edge, records that do not
+ * strictly ascend, an open or one-point chain under RJ_SNAP_DROP_LAST).  Runs on the handle's stream with one host
+ * sync, at the end, for the counts.  Scratch (144 bytes per record -- a cut carries its point --, 12 per edge, plus the
+ * sort's and the scans' temporary storage) is allocated per call and freed; no map, index or option of the handle
+ * changes.  rj_get_option: "snap_last_us0" .. "snap_last_us5" (HIP-event microseconds of the stages: the check, the
+ * candidates, their sort and the kept cuts, the cuts per edge and their scan, the two scatters, all; -1: not reached). */
+int rj_map_snap(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc,
+                const rj_crossing* cross_dev, uint64_t n_cross, uint32_t flags, uint64_t point_capacity,
+                int64_t* out_xy_dev, uint32_t* out_row_index_dev, uint32_t* edge_origin_dev, rj_snap_counts* counts);
+
 /* ---- thinning: fewer points on every chain, the same chains ------------------------------------- */
 typedef struct {
   uint64_t n_points, n_removed;  /* of the output; n_removed = np - n_points */

@@ -48,6 +48,10 @@ CROSSING_DTYPE = np.dtype([("eid", "<u4", (2,)), ("kind", "<u4"), ("_pad", "<u4"
 CROSSINGS_COUNTS = ("n_found", "n_proper", "n_touch", "n_overlap", "n_equal", "n_edges", "n_zero_edges")
 RJ_NODE_DROP_LAST = 1  # rj_map_node flags
 NODE_COUNTS = ("n_points", "n_edges", "n_cuts", "n_cut_edges", "n_max_cuts", "n_used", "n_proper", "n_equal")
+RJ_SNAP_DROP_LAST = 1  # rj_map_snap flags
+SNAP_COUNTS = NODE_COUNTS + ("n_exact", "n_at_end", "n_stale")
+# rj_snap_counts as one record (what a tool that keeps the counts of many rounds stores)
+SNAP_COUNTS_DTYPE = np.dtype([(name, "<u8") for name in SNAP_COUNTS])
 SIMPLIFY_COUNTS = ("n_points", "n_removed", "n_rounds", "n_closed", "n_pinned_extra", "n_max_round")
 # rj_face: one face of rj_map_faces -- its shell's leader half-chain, its holes, its label, twice its area
 MAP_FACE_DTYPE = np.dtype([("leader", "<u4"), ("n_holes", "<u4"), ("label", "<i4"), ("_pad", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
@@ -105,6 +109,7 @@ SYMBOLS = {
     "rj_rings_map": (_int, [_vp, _vp, _vp, _u64, _vp, _u64, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "rj_map_crossings": (_int, [_vp, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _vp, _vp]),
     "rj_map_node": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
+    "rj_map_snap": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
     "rj_map_simplify": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
     "rj_map_faces": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
@@ -219,6 +224,15 @@ class CrossingsOverflow(RayJoinError):
 class NodeOverflow(RayJoinError):
     """RJ_E_OVERFLOW of rj_map_node: counts = dict(n_points, n_edges, n_cuts, n_cut_edges, n_max_cuts, n_used, n_proper, n_equal),
     the true counts"""
+
+    def __init__(self, msg, counts):
+        super().__init__(RJ_E_OVERFLOW, msg)
+        self.counts = counts
+
+
+class SnapOverflow(RayJoinError):
+    """RJ_E_OVERFLOW of rj_map_snap: counts = a dict of SNAP_COUNTS (rj_node_counts' fields, n_exact, n_at_end, n_stale), the
+    true counts"""
 
     def __init__(self, msg, counts):
         super().__init__(RJ_E_OVERFLOW, msg)
@@ -651,6 +665,20 @@ class Handle:
         named = dict(zip(NODE_COUNTS, (int(v) for v in counts)))
         if rc == RJ_E_OVERFLOW:
             raise NodeOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        self._check(rc)
+        return named
+
+    def map_snap(self, xy_dev, n_points, row_index_dev, n_chains, cross_dev, n_cross, flags, capacity, out_xy_dev, out_row_index_dev,
+                 edge_origin_dev=None):
+        """rj_map_snap of a chain map and its rj_map_crossings records, both in device memory, into the caller's device arrays
+        of `capacity` points, n_chains + 1 row entries and (or None) n_edges origins (capacity 0, arrays None: the sizing
+        call).  Returns the counts as a dict (SNAP_COUNTS); SnapOverflow (with the true counts) past the capacity."""
+        counts = (_u64 * len(SNAP_COUNTS))()
+        rc = self.L.rj_map_snap(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains), _ptr(cross_dev), int(n_cross), int(flags),
+                                int(capacity), _ptr(out_xy_dev), _ptr(out_row_index_dev), _ptr(edge_origin_dev), counts)
+        named = dict(zip(SNAP_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise SnapOverflow(self.L.rj_last_error_string(self.h).decode(), named)
         self._check(rc)
         return named
 

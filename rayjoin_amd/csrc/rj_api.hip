@@ -25,6 +25,7 @@
 #include "rj_ringmap.h"
 #include "rj_rings.h"
 #include "rj_simplify.h"
+#include "rj_snap.h"
 
 using namespace rj;
 
@@ -281,6 +282,7 @@ struct rj_handle_s {
   int debug_cross_shift = 0, debug_cross_pair_budget = 0, debug_cross_extent_factor = 0, debug_cross_reg_factor = 0;
   CrossingsReport cross_report = {};  // what the last rj_map_crossings chose and took (reports only)
   NodeReport node_report = {{-1, -1, -1, -1, -1, -1}};  // what the stages of the last rj_map_node took (reports only)
+  SnapReport snap_report = {{-1, -1, -1, -1, -1, -1}};  // what the stages of the last rj_map_snap took (reports only)
   int debug_simplify_all_points = 0;  // rj_map_simplify: 1 = every round looks at every point, no work list (tests: the same result)
   SimplifyReport simplify_report = {{-1, -1, -1, -1, -1, -1}};  // what the last rj_map_simplify took (reports only)
   int debug_faces_shift = 0;  // rj_map_faces: where the search for the grid's shift starts (0: choose; tests: the same result)
@@ -713,6 +715,7 @@ const Report kReports[] = {
     {"cross_last_items", 0, RJ_READ(h->cross_report.n_items)},
     {"cross_last_us", 6, RJ_READ(h->cross_report.ms[k] < 0 ? -1 : (int64_t) (h->cross_report.ms[k] * 1000.0f))},  // edges and sums, registrations and sort, runs, pairs, hits, all
     {"node_last_us", 6, RJ_READ(h->node_report.ms[k] < 0 ? -1 : (int64_t) (h->node_report.ms[k] * 1000.0f))},  // the last rj_map_node: check, candidates, sort, cuts per edge, scatters, all
+    {"snap_last_us", 6, RJ_READ(h->snap_report.ms[k] < 0 ? -1 : (int64_t) (h->snap_report.ms[k] * 1000.0f))},  // the last rj_map_snap: check, candidates, sort, cuts per edge, scatters, all
     {"simplify_last_us", 6, RJ_READ(h->simplify_report.ms[k] < 0 ? -1 : (int64_t) (h->simplify_report.ms[k] * 1000.0f))},  // the last rj_map_simplify: check, links and pins, first round, later rounds, scan and scatter, all
     {"simplify_last_syncs", 0, RJ_READ(h->simplify_report.n_syncs)},        // ... its host syncs
     {"simplify_last_list_sum", 0, RJ_READ(h->simplify_report.list_sum)},    // ... the work lists of the rounds behind the first, summed
@@ -2968,6 +2971,50 @@ int rj_map_node(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t*
     return fail(h, RJ_E_INVALID, "rj_map_node: %llu points and %llu cuts: np + n_cuts < 2^32", (unsigned long long) np, (unsigned long long) counts->n_cuts);
   if (counts->n_points > point_capacity)
     return fail(h, RJ_E_OVERFLOW, "rj_map_node: %llu points; capacity %llu", (unsigned long long) counts->n_points, (unsigned long long) point_capacity);
+  return RJ_OK;
+}
+
+int rj_map_snap(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc, const rj_crossing* cross_dev, uint64_t n_cross,
+                uint32_t flags, uint64_t point_capacity, int64_t* out_xy_dev, uint32_t* out_row_index_dev, uint32_t* edge_origin_dev,
+                rj_snap_counts* counts) {
+  static_assert(sizeof(rj_crossing) == sizeof(node::Record) && sizeof(rj_snap_counts) == sizeof(snap::Counts) && RJ_SNAP_DROP_LAST == snap::kDropLast,
+                "layouts");
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_map_snap: counts is null");
+  memset(counts, 0, sizeof(*counts));
+  if (flags & ~(uint32_t) RJ_SNAP_DROP_LAST) return fail(h, RJ_E_INVALID, "rj_map_snap: unknown flags 0x%x", flags);
+  if ((np && !xy_dev) || (nc && !row_index_dev) || (n_cross && !cross_dev)) return fail(h, RJ_E_INVALID, "rj_map_snap: null input array");
+  if (np >= (1ull << 32) || nc > np || np - nc >= 0xFFFFFFFFull) return fail(h, RJ_E_INVALID, "rj_map_snap: nc <= np < 2^32 and np - nc < 2^32 - 1");
+  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_snap: points without chains");
+  if (n_cross >= (1ull << 31)) return fail(h, RJ_E_INVALID, "rj_map_snap: n_cross < 2^31");
+  if (nc == 0 && n_cross) return fail(h, RJ_E_INVALID, "rj_map_snap: a record names an edge that the map does not have");
+  if (point_capacity && (!out_xy_dev || !out_row_index_dev)) return fail(h, RJ_E_INVALID, "rj_map_snap: null output");
+  if (int r = set_device(h)) return r;
+  h->snap_report = SnapReport{{-1, -1, -1, -1, -1, -1}};
+  if (nc == 0) {  // no chains: the row's one entry, where the caller has an array
+    if (out_row_index_dev) {
+      RJ_HIP(h, hipMemsetAsync(out_row_index_dev, 0, 4, h->stream));
+      RJ_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return RJ_OK;
+  }
+  snap::Meta m;
+  RJ_HIP(h, map_snap_device(h->stream, xy_dev, np, row_index_dev, nc, cross_dev, n_cross, flags, point_capacity, out_xy_dev, out_row_index_dev,
+                            edge_origin_dev, &m, &h->snap_report));
+  if (m.bad == crossings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_snap: row_index must start at 0");
+  if (m.bad == crossings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_snap: row_index must end at np");
+  if (m.bad == crossings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_snap: row_index must ascend (a chain has no point)");
+  if (m.bad == crossings::kBadCoordinate) return fail(h, RJ_E_INVALID, "rj_map_snap: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  if (m.bad == node::kBadOpenChain)
+    return fail(h, RJ_E_INVALID, "rj_map_snap: RJ_SNAP_DROP_LAST needs chains of two points or more whose first point equals the last");
+  if (m.bad == node::kBadRecord) return fail(h, RJ_E_INVALID, "rj_map_snap: a record needs eid[0] < eid[1] < ne and a kind in 1..4");
+  if (m.bad == node::kBadZeroEdge) return fail(h, RJ_E_INVALID, "rj_map_snap: a record names an edge of zero length");
+  if (m.bad) return fail(h, RJ_E_INVALID, "rj_map_snap: the records must strictly ascend by (eid[0], eid[1])");
+  memcpy(counts, &m.counts, sizeof(*counts));
+  if (np + counts->n_cuts >= (1ull << 32))
+    return fail(h, RJ_E_INVALID, "rj_map_snap: %llu points and %llu cuts: np + n_cuts < 2^32", (unsigned long long) np, (unsigned long long) counts->n_cuts);
+  if (counts->n_points > point_capacity)
+    return fail(h, RJ_E_OVERFLOW, "rj_map_snap: %llu points; capacity %llu", (unsigned long long) counts->n_points, (unsigned long long) point_capacity);
   return RJ_OK;
 }
 

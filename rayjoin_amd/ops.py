@@ -30,6 +30,12 @@
       -- the repair behind that check where it is exact (rj_map_node): every edge cut at the vertices that lie inside it,
          so that T-junctions and half-shared borders (RJ_CROSS_TOUCH, RJ_CROSS_OVERLAP) become shared vertices and equal
          edges; node_rings takes the user's rings to the arrays rings_map takes.  Proper crossings are counted, not moved
+  map_snap(handle, ...) -> DeviceNodedMap; map_snap_rounds(handle, ...) / DeviceOutputMap.Snap(handle) /
+      DeviceChainMap.Snap(handle) / DeviceNodedMap.Snap(handle) -> DeviceNodedMap with rounds, clean, remaining; snap_rings(handle, ...)
+      -- the repair of proper crossings too (rj_map_snap): map_node plus a cut at the rounded point of every
+         RJ_CROSS_PROPER record; map_snap_rounds repeats the check and the cut until the map is clean or a round cap is
+         hit and reports both -- overlapping polygons, self-crossing rings and overlay outputs with crossings become
+         planar linework whose faces map_faces labels.  That the rounds end is measured, not guaranteed
   map_simplify(handle, ...) -> DeviceSimplifiedMap; DeviceOutputMap.Simplify(handle, tol) / DeviceChainMap.Simplify(handle, tol)
       -> DeviceChainMap
       -- what makes a map smaller (rj_map_simplify): the chains thinned by effective area, Visvalingam-Whyatt in rounds on
@@ -403,6 +409,11 @@ class DeviceOutputMap:
         """map_node of this map, on the device: its edges cut at the vertices that lie inside them (left / right stay valid)"""
         return map_node(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
 
+    def Snap(self, handle, **kw):
+        """map_snap_rounds of this map, on the device: cut at its touches, overlaps and rounded proper crossings until a check
+        finds none (.clean) or max_rounds is hit; the chains stay, so left / right stay valid as chain labels"""
+        return map_snap_rounds(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
+
     def Simplify(self, handle, tol, check=False, capacity=None):
         """map_simplify of this map, on the device, as a DeviceChainMap of its own (copies of left / right: the chains do not
         change): what InstallMap, Rings() and Crossings() take; its counts are those of rj_map_simplify with n_chains and
@@ -553,10 +564,95 @@ def map_node(handle, xy, n_points, row_index, n_chains, records=None, drop_last=
     return DeviceNodedMap(*bufs, counts, n_chains, drop_last)
 
 
+def _snap_call(handle, xy, n_points, row_index, n_chains, rec, n_rec, flags, edge_origin, capacity):
+    """rj_map_snap with the records in device memory (rec may be None with n_rec == 0) -> DeviceNodedMap"""
+    bufs = []
+    try:
+        args = (xy, n_points, row_index, n_chains, rec, n_rec, flags)
+        if capacity is None:
+            try:
+                capacity = handle.map_snap(*args, 0, None, None)["n_points"]
+            except _capi.SnapOverflow as e:
+                capacity = e.counts["n_points"]
+        capacity = int(capacity)
+        bufs = [handle.alloc(16 * max(1, capacity)), handle.alloc(4 * (int(n_chains) + 1)), handle.alloc(4 * max(1, capacity)) if edge_origin else None]
+        counts = handle.map_snap(*args, capacity, *bufs)
+    except _capi.RayJoinError:
+        for b in bufs:
+            if b is not None:
+                b.free()
+        raise
+    return DeviceNodedMap(*bufs, counts, n_chains, bool(flags & _capi.RJ_SNAP_DROP_LAST))
+
+
+def map_snap(handle, xy, n_points, row_index, n_chains, records=None, drop_last=False, edge_origin=False, capacity=None):
+    """map_node that also cuts at proper crossings (rj_map_snap), as a DeviceNodedMap with the wider counts (SNAP_COUNTS):
+    every RJ_CROSS_PROPER record cuts both of its edges at the crossing point rounded to integers (halves toward
+    +infinity), the other kinds cut as in map_node.  One call: the rounding can make new crossings -- map_snap_rounds
+    repeats it.  records, drop_last, edge_origin, capacity: as map_node (SnapOverflow past the capacity)."""
+    flags = _capi.RJ_SNAP_DROP_LAST if drop_last else 0
+    if records is None:
+        rec, c = _crossings_on_device(handle, xy, n_points, row_index, n_chains)
+        n_rec = c["n_found"]
+    else:
+        records = np.ascontiguousarray(records, dtype=_capi.CROSSING_DTYPE)
+        n_rec = len(records)
+        rec = handle.alloc(_capi.CROSSING_DTYPE.itemsize * n_rec).from_host(records) if n_rec else None
+    try:
+        return _snap_call(handle, xy, n_points, row_index, n_chains, rec, n_rec, flags, edge_origin, capacity)
+    finally:
+        if rec is not None:
+            rec.free()
+
+
+def map_snap_rounds(handle, xy, n_points, row_index, n_chains, max_rounds=8, drop_last=False):
+    """A chain map in device memory cut until it has no crossing left, or max_rounds times: map_crossings, then map_snap
+    on its records, again on the result, every intermediate map freed.  It stops when a check finds no RJ_CROSS_PROPER,
+    TOUCH or OVERLAP record (EQUAL records are edges stored twice: rings_map's business) or when max_rounds cutting
+    calls were made; one last check then tells what is left.  -> a DeviceNodedMap with three more attributes: rounds, a
+    list of dict(crossings=the check's counts, snap=the cut's counts) per cutting call; clean, whether the last check
+    found nothing to cut; remaining, that last check's counts.  The rounds converge in practice (two or three on
+    ordinary input) but nothing guarantees it: read clean.  edge_origin is not composed across rounds and not returned.
+    drop_last: the input's chains are closed (first point == last) and stay so through every round -- each round's input
+    is a valid map --; a final copying call (rj_map_snap with RJ_SNAP_DROP_LAST and no records) writes them without
+    their last point, the ring layout rings_map takes.  Without a cutting round the result is such a copy as well: the
+    caller owns it either way."""
+    flags = _capi.RJ_SNAP_DROP_LAST if drop_last else 0
+    rounds, cur = [], None
+    try:
+        while True:
+            at = (xy, n_points, row_index) if cur is None else (cur.xy, cur.n_points, cur.row_index)
+            rec, c = _crossings_on_device(handle, at[0], at[1], at[2], n_chains)
+            try:
+                if c["n_proper"] + c["n_touch"] + c["n_overlap"] == 0 or len(rounds) >= max_rounds:
+                    break
+                nm = _snap_call(handle, at[0], at[1], at[2], n_chains, rec, c["n_found"], 0, False, None)
+            finally:
+                if rec is not None:
+                    rec.free()
+            rounds.append(dict(crossings=c, snap=nm.counts))
+            if cur is not None:
+                cur.free()
+            cur = nm
+        if cur is None or drop_last:
+            at = (xy, n_points, row_index) if cur is None else (cur.xy, cur.n_points, cur.row_index)
+            nm = _snap_call(handle, at[0], at[1], at[2], n_chains, None, 0, flags, False, None)
+            if cur is not None:
+                cur.free()
+            cur = nm
+    except _capi.RayJoinError:
+        if cur is not None:
+            cur.free()
+        raise
+    cur.rounds, cur.clean, cur.remaining = rounds, c["n_proper"] + c["n_touch"] + c["n_overlap"] == 0, c
+    return cur
+
+
 class DeviceNodedMap:
     """A noded chain map in device memory (rj_map_node): xy (int64 x,y pairs), row_index (uint32, n_chains + 1) and, where
     asked for, edge_origin (uint32 per output edge: its input edge) as DeviceBuffers, the counts n_points, n_edges, n_cuts,
-    n_cut_edges, n_max_cuts, n_used, n_proper, n_equal, and drop_last: the chains are rings without their closing point."""
+    n_cut_edges, n_max_cuts, n_used, n_proper, n_equal (from map_snap also n_exact, n_at_end, n_stale), and drop_last: the
+    chains are rings without their closing point.  From map_snap_rounds also rounds, clean and remaining."""
 
     def __init__(self, xy, row_index, edge_origin, counts, n_chains, drop_last=False):
         self.xy, self.row_index, self.edge_origin = xy, row_index, edge_origin
@@ -575,6 +671,13 @@ class DeviceNodedMap:
         if (left is None) != (right is None):
             raise ValueError("left and right go together")
         return map_faces(handle, self.xy, self.n_points, self.row_index, self.n_chains, labels=None if left is None else (left, right))
+
+    def Snap(self, handle, **kw):
+        """map_snap_rounds of this map (not one written with drop_last: its chains must be whole): the proper crossings
+        that noding left are cut in rounds"""
+        if self.drop_last:
+            raise ValueError("a map written with drop_last has no closing points: snap before dropping them")
+        return map_snap_rounds(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
 
     def free(self):
         for b in (self.xy, self.row_index, self.edge_origin):
@@ -596,6 +699,22 @@ def node_rings(handle, ring_row, ring_xy):
         for b in bufs:
             b.free()
     return nm.row_index, nm.xy, nm.n_points, nm.counts
+
+
+def snap_rings(handle, ring_row, ring_xy, max_rounds=8):
+    """node_rings for rings that may cross each other or themselves: closed into chains, uploaded, map_snap_rounds with
+    drop_last -> (ring_row buffer, ring_xy buffer, n_points, clean, rounds), the first three ready for rings_map with the
+    caller's unchanged ring_face -- where polygons overlapped, the labels of the chain map that comes out conflict
+    (its counts tell) and map_faces labels the linework from its geometry.  clean / rounds: as map_snap_rounds."""
+    from .maps import closed_chains_of_rings
+    row, xy = closed_chains_of_rings(ring_row, ring_xy)
+    bufs = [handle.alloc(16 * max(1, len(xy))).from_host(xy), handle.alloc(4 * len(row)).from_host(row)]
+    try:
+        nm = map_snap_rounds(handle, bufs[0], len(xy), bufs[1], len(row) - 1, max_rounds=max_rounds, drop_last=True)
+    finally:
+        for b in bufs:
+            b.free()
+    return nm.row_index, nm.xy, nm.n_points, nm.clean, nm.rounds
 
 
 def face_rings(handle, xy, n_points, row_index, left, right, n_chains, skip_face0=False, points=True, capacities=None):
@@ -754,6 +873,11 @@ class DeviceChainMap:
     def Node(self, handle, **kw):
         """map_node of this map, on the device: its edges cut at the vertices that lie inside them (left / right stay valid)"""
         return map_node(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
+
+    def Snap(self, handle, **kw):
+        """map_snap_rounds of this map, on the device: cut at its touches, overlaps and rounded proper crossings until a check
+        finds none (.clean) or max_rounds is hit; the chains stay, so left / right stay valid as chain labels"""
+        return map_snap_rounds(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
 
     def Simplify(self, handle, tol, check=False, capacity=None):
         """map_simplify of this map, on the device, as a DeviceChainMap of its own (copies of left / right: the chains do not
