@@ -769,6 +769,69 @@ int rj_map_faces(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t
                  const int32_t* in_left_dev, const int32_t* in_right_dev, uint32_t flags, uint64_t face_capacity,
                  int32_t* left_dev, int32_t* right_dev, rj_face* faces_dev /* may be NULL */, rj_faces_counts* counts);
 
+/* ---- eliminating slivers: a small face joins the neighbour with the longest shared border ------------ */
+#define RJ_ELIM_DROP 1u            /* write the map without the chains whose two labels became equal */
+/* rj_elim_face flags */
+#define RJ_ELIM_SLIVER     1u      /* 0 <= area2 <= tol */
+#define RJ_ELIM_ELIMINATED 2u      /* target != label */
+#define RJ_ELIM_ISLAND     4u      /* a sliver with no eligible neighbour: it stays */
+#define RJ_ELIM_NEGATIVE   8u      /* area2 < 0: inconsistent labels; never a sliver, may be a target */
+typedef struct { int32_t label, target, best; uint32_t flags; uint64_t area2_lo; int64_t area2_hi; } rj_elim_face; /* 32 bytes */
+typedef struct { uint64_t n_faces, n_slivers, n_eliminated, n_islands, n_mutual, n_negative,
+                 n_chains, n_points, n_dropped; } rj_eliminate_counts;
+
+/* extends: what removes slivers -- the overlay truncates cut points to integers, rj_map_snap turns near misses into thin
+ * triangles, two layers thinned separately and overlaid leave faces of a few units^2 along every almost-shared border.
+ * This is the operation GIS users know as Eliminate: a face whose area is at most a tolerance joins the neighbour it
+ * shares the longest border with, on the device, on a labelled chain map in device memory.  (The reference has no
+ * counterpart: its WriteOutputChain writes whatever the cuts produced.)
+ * Input: xy_dev[2 np], row_index_dev[nc + 1], left_dev[nc], right_dev[nc] with the contract, the checks and the size limits
+ * of rj_map_rings (a chain may have a single point); labels are any int32.  tol = (tol_hi << 64) | tol_lo, an unsigned
+ * 128-bit number: twice an area in scaled units^2, as in rj_map_simplify.
+ * The definition, in full in rayjoin_amd/csrc/rj_eliminate.h:
+ *   a face is a label value other than 0 that occurs in left or right (a multi-part polygon with one label is one face;
+ *   faces from geometry: rj_map_faces first).  Faces are numbered by ascending (uint32_t) label, and "smaller label" means
+ *   that unsigned order.  Of chain c: S(c) = the sum of cross(p_i, p_i+1) over its edges (int128), L(c) = the sum of
+ *   floor(sqrt(dx^2 + dy^2)) over its edges (the exact integer square root; an unsigned 128-bit sum).
+ *   area2(f) = the sum of S(c) over left[c] == f minus the sum over right[c] == f (the rule of rj_overlay_faces: exact for
+ *   consistent labels, holes subtract themselves).  f is a sliver when 0 <= area2(f) <= tol; area2(f) < 0 sets
+ *   RJ_ELIM_NEGATIVE and f is never a sliver.  Faces f != g, both not 0, are neighbours when some chain has
+ *   {left, right} = {f, g}; w(f, g) = the sum of L(c) over those chains, and a pair with w = 0 is still a pair.  Face 0 is
+ *   never a neighbour, a sliver or a target; chains with left == right contribute nothing.
+ *   best(f) of a sliver = the neighbour with the largest w, ties to the smaller min(f, g), then the smaller max(f, g); a
+ *   sliver without a neighbour is an island (RJ_ELIM_ISLAND) and stays; every other face has no best (its record holds
+ *   its own label).  When best(f) = g and best(g) = f (a mutual pair, n_mutual) the one with the larger area2 stays as
+ *   a root, a tie goes to the smaller label, and the other points at it.  target(f) = the root reached by following
+ *   best; roots are the non-slivers, the islands and the winners of mutual pairs; target(0) = 0.
+ *   ONE CALL IS ONE ROUND: a merged group may still be at most tol, and the caller repeats the call.
+ * Output, caller-owned device memory: out_left_dev[c] = target(left[c]), out_right_dev[c] = target(right[c]);
+ * faces_dev[face_capacity] (may be NULL: no records, face_capacity is ignored), record k of the k-th face: its label,
+ * target, best, flags and its own area2 (a two's-complement int128).  Without RJ_ELIM_DROP out_left_dev / out_right_dev
+ * are [nc] (chain_capacity >= nc), out_xy_dev, out_row_index_dev, chain_origin_dev and point_capacity are ignored,
+ * n_chains = nc and n_points = np.  With RJ_ELIM_DROP a chain is dropped, and counted in n_dropped, exactly when its
+ * input labels differ and its output labels are equal (bridges and dangles that came with left == right stay); the kept
+ * chains are written in input order with their points into out_xy_dev[2 point_capacity] and
+ * out_row_index_dev[chain_capacity + 1], their labels into out_left_dev / out_right_dev[chain_capacity], and
+ * chain_origin_dev[k] (may be NULL) is the input chain of output chain k.  Chains are NOT re-joined at vertices that
+ * drop to degree 2: that is rj_map_rings followed by rj_rings_map, as for every other map.
+ * All capacities 0 (arrays may be NULL) is the sizing call.  RJ_E_OVERFLOW when a count exceeds its capacity: *counts
+ * holds the true counts and nothing is written.  nc == 0 is valid.  RJ_E_INVALID, with nothing written: the map checks
+ * of rj_map_rings and an unknown flag bit.  RJ_E_INTERNAL when the budget of 33 jumping rounds runs out (the order on
+ * pairs is strict, so the pointers have no cycle but the mutual pairs: cannot happen).  Integers only, exact, fully
+ * determined.  Runs on the handle's stream with one host sync, at the end; scratch (rj_eliminate.h has the bytes per
+ * chain) is allocated per call and freed; no map, index or option of the handle changes.  For tests and sweeps, through
+ * rj_set_debug_option: "elim_point_blocks" (0: by size) is the grid of the two passes over the points, the chain sums
+ * and the scatter; any grid gives the same result.  rj_get_option:
+ * "elim_last_us0" .. "elim_last_us5" (HIP-event microseconds of the stages: the check and the chain sums, the faces,
+ * the pairs and the choice, the pointers, the new labels and the scatter, all; -1: not reached). */
+int rj_map_eliminate(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev,
+                     const int32_t* left_dev, const int32_t* right_dev, uint64_t nc,
+                     uint64_t tol_lo, uint64_t tol_hi, uint32_t flags,
+                     uint64_t face_capacity, uint64_t chain_capacity, uint64_t point_capacity,
+                     rj_elim_face* faces_dev /* may be NULL */, int32_t* out_left_dev, int32_t* out_right_dev,
+                     int64_t* out_xy_dev, uint32_t* out_row_index_dev, uint32_t* chain_origin_dev /* may be NULL */,
+                     rj_eliminate_counts* counts);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

@@ -56,6 +56,11 @@ SIMPLIFY_COUNTS = ("n_points", "n_removed", "n_rounds", "n_closed", "n_pinned_ex
 # rj_face: one face of rj_map_faces -- its shell's leader half-chain, its holes, its label, twice its area
 MAP_FACE_DTYPE = np.dtype([("leader", "<u4"), ("n_holes", "<u4"), ("label", "<i4"), ("_pad", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
 MAP_FACES_COUNTS = ("n_faces", "n_rings", "n_holes", "n_outer", "n_skipped", "n_dangling", "n_conflicts")
+RJ_ELIM_DROP = 1  # rj_map_eliminate flags
+RJ_ELIM_SLIVER, RJ_ELIM_ELIMINATED, RJ_ELIM_ISLAND, RJ_ELIM_NEGATIVE = 1, 2, 4, 8  # rj_elim_face flags
+# rj_elim_face: one face (a label) of rj_map_eliminate -- the face it joins, the neighbour it chose, RJ_ELIM_*, twice its own area
+ELIM_FACE_DTYPE = np.dtype([("label", "<i4"), ("target", "<i4"), ("best", "<i4"), ("flags", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
+ELIMINATE_COUNTS = ("n_faces", "n_slivers", "n_eliminated", "n_islands", "n_mutual", "n_negative", "n_chains", "n_points", "n_dropped")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
 _vp, _u64, _i64, _int = C.c_void_p, C.c_uint64, C.c_int64, C.c_int
@@ -112,6 +117,7 @@ SYMBOLS = {
     "rj_map_snap": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
     "rj_map_simplify": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
     "rj_map_faces": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
+    "rj_map_eliminate": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _u64, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -251,6 +257,14 @@ class FacesOverflow(RayJoinError):
 class SimplifyOverflow(RayJoinError):
     """RJ_E_OVERFLOW of rj_map_simplify: counts = dict(n_points, n_removed, n_rounds, n_closed, n_pinned_extra, n_max_round),
     the true counts"""
+
+    def __init__(self, msg, counts):
+        super().__init__(RJ_E_OVERFLOW, msg)
+        self.counts = counts
+
+
+class EliminateOverflow(RayJoinError):
+    """RJ_E_OVERFLOW of rj_map_eliminate: counts = a dict of ELIMINATE_COUNTS, the true counts; nothing is written"""
 
     def __init__(self, msg, counts):
         super().__init__(RJ_E_OVERFLOW, msg)
@@ -709,6 +723,27 @@ class Handle:
         named = dict(zip(MAP_FACES_COUNTS, (int(v) for v in counts)))
         if rc == RJ_E_OVERFLOW:
             raise FacesOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        self._check(rc)
+        return named
+
+    def map_eliminate(self, xy_dev, n_points, row_index_dev, left_dev, right_dev, n_chains, tol, capacities, out_left_dev, out_right_dev,
+                      out_xy_dev=None, out_row_index_dev=None, chain_origin_dev=None, faces_dev=None, flags=0):
+        """rj_map_eliminate of a labelled chain map in device memory: the new labels into out_left_dev / out_right_dev and,
+        under RJ_ELIM_DROP, the kept chains into out_xy_dev / out_row_index_dev / (or None) chain_origin_dev; where faces_dev
+        is given, the rj_elim_face records.  capacities = (faces, chains, points); (0, 0, 0) with arrays None is the sizing
+        call.  tol a Python int in [0, 2^128).  Returns the counts as a dict (ELIMINATE_COUNTS); EliminateOverflow (with the
+        true counts) past a capacity."""
+        tol = int(tol)
+        if not 0 <= tol < 1 << 128:
+            raise ValueError("tol must lie in [0, 2^128), not %d" % tol)
+        fc, cc, pc = (int(v) for v in capacities)
+        counts = (_u64 * len(ELIMINATE_COUNTS))()
+        rc = self.L.rj_map_eliminate(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev), int(n_chains),
+                                     tol & 0xFFFFFFFFFFFFFFFF, tol >> 64, int(flags), fc, cc, pc, _ptr(faces_dev), _ptr(out_left_dev), _ptr(out_right_dev),
+                                     _ptr(out_xy_dev), _ptr(out_row_index_dev), _ptr(chain_origin_dev), counts)
+        named = dict(zip(ELIMINATE_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise EliminateOverflow(self.L.rj_last_error_string(self.h).decode(), named)
         self._check(rc)
         return named
 

@@ -15,6 +15,7 @@
 
 #include "../../include/rayjoin_amd.h"
 #include "rj_crossings.h"
+#include "rj_eliminate.h"
 #include "rj_faces.h"
 #include "rj_node.h"
 #include "rj_kernels.h"
@@ -287,6 +288,8 @@ struct rj_handle_s {
   SimplifyReport simplify_report = {{-1, -1, -1, -1, -1, -1}};  // what the last rj_map_simplify took (reports only)
   int debug_faces_shift = 0;  // rj_map_faces: where the search for the grid's shift starts (0: choose; tests: the same result)
   FacesReport faces_report = {{-1, -1, -1, -1, -1, -1}, 0, 0, 0, 0};  // what the last rj_map_faces chose and took (reports only)
+  int debug_elim_point_blocks = 0;  // rj_map_eliminate: the grid of the chain sums and of the point scatter (0: by size; tests and sweeps: the same result)
+  EliminateReport eliminate_report = {{-1, -1, -1, -1, -1, -1}};  // what the last rj_map_eliminate took (reports only)
   uint32_t stitch_stats[4] = {0, 0, 0, 0};  // the last run cutting: ranking rounds, incidences on closed loops, rounds of the second ranking, closed chains
   char* strip_scratch = nullptr;  // grow-only temporaries of the column index's build
   size_t strip_scratch_bytes = 0;
@@ -640,6 +643,7 @@ const Option kOptions[] = {
     {"cross_reg_factor", true, &rj_handle_s::debug_cross_reg_factor, 0, 1 << 20},  // ... registrations per edge allowed (0: 4)
     {"simplify_all_points", true, &rj_handle_s::debug_simplify_all_points, 0, 1},  // rj_map_simplify: every round over all points (0: the work list)
     {"faces_shift", true, &rj_handle_s::debug_faces_shift, 15, 47, "faces_shift: 0 (choose) or 15..47", nullptr, nullptr, 1, {0}},  // rj_map_faces: the grid's shift
+    {"elim_point_blocks", true, &rj_handle_s::debug_elim_point_blocks, 0, 1 << 20},  // rj_map_eliminate: blocks of its two passes over the points (0: by size)
 };
 
 const Option* find_option(const char* name, bool debug) {
@@ -730,6 +734,7 @@ const Report kReports[] = {
     {"faces_last_ray_tests", 0, RJ_READ(h->faces_report.ray_tests)},
     {"faces_last_cells", 0, RJ_READ(h->faces_report.cells)},
     {"faces_last_us", 6, RJ_READ(h->faces_report.ms[k] < 0 ? -1 : (int64_t) (h->faces_report.ms[k] * 1000.0f))},  // rings, tops and kinds, grid, rays, parents and faces, all
+    {"elim_last_us", 6, RJ_READ(h->eliminate_report.ms[k] < 0 ? -1 : (int64_t) (h->eliminate_report.ms[k] * 1000.0f))},  // the last rj_map_eliminate: check and chain sums, faces, pairs and choice, pointers, labels and scatter, all
     {"comm_ranks", 0, read_comm_ranks},
     {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
     {"pip_share_blocks", 0, RJ_READ(h->last_pip_share ? h->last_pip_share : h->pip_share_blocks())},
@@ -3083,6 +3088,53 @@ int rj_map_faces(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t
   memcpy(counts, &m.counts, sizeof(*counts));
   if (faces_dev && counts->n_faces > face_capacity)
     return fail(h, RJ_E_OVERFLOW, "rj_map_faces: %llu faces; capacity %llu", (unsigned long long) counts->n_faces, (unsigned long long) face_capacity);
+  return RJ_OK;
+}
+
+int rj_map_eliminate(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, const int32_t* left_dev, const int32_t* right_dev,
+                     uint64_t nc, uint64_t tol_lo, uint64_t tol_hi, uint32_t flags, uint64_t face_capacity, uint64_t chain_capacity, uint64_t point_capacity,
+                     rj_elim_face* faces_dev, int32_t* out_left_dev, int32_t* out_right_dev, int64_t* out_xy_dev, uint32_t* out_row_index_dev,
+                     uint32_t* chain_origin_dev, rj_eliminate_counts* counts) {
+  static_assert(sizeof(rj_elim_face) == 32 && sizeof(eliminate::Face) == 32 && sizeof(rj_eliminate_counts) == sizeof(eliminate::Counts), "layouts");
+  static_assert(RJ_ELIM_DROP == eliminate::kDrop && RJ_ELIM_SLIVER == eliminate::kSliver && RJ_ELIM_ELIMINATED == eliminate::kEliminated &&
+                    RJ_ELIM_ISLAND == eliminate::kIsland && RJ_ELIM_NEGATIVE == eliminate::kNegative,
+                "flags");
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_map_eliminate: counts is null");
+  memset(counts, 0, sizeof(*counts));
+  if (flags & ~(uint32_t) RJ_ELIM_DROP) return fail(h, RJ_E_INVALID, "rj_map_eliminate: unknown flags 0x%x", flags);
+  const bool drop = (flags & RJ_ELIM_DROP) != 0;
+  if (!drop) point_capacity = 0;
+  if (!faces_dev) face_capacity = 0;
+  if ((np && !xy_dev) || (nc && (!row_index_dev || !left_dev || !right_dev))) return fail(h, RJ_E_INVALID, "rj_map_eliminate: null input array");
+  if (nc >= (1ull << 31) || np >= (1ull << 32) || nc > np || 2 * (np - nc) >= (1ull << 32))
+    return fail(h, RJ_E_INVALID, "rj_map_eliminate: nc < 2^31, nc <= np < 2^32 and 2 (np - nc) < 2^32");
+  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_eliminate: points without chains");
+  if ((chain_capacity && (!out_left_dev || !out_right_dev || (drop && !out_row_index_dev))) || (point_capacity && !out_xy_dev))
+    return fail(h, RJ_E_INVALID, "rj_map_eliminate: null output");
+  if (int r = set_device(h)) return r;
+  h->eliminate_report = EliminateReport{{-1, -1, -1, -1, -1, -1}};
+  if (nc == 0) {  // no chains: under RJ_ELIM_DROP the row's one entry, where the caller has an array
+    if (drop && out_row_index_dev) {
+      RJ_HIP(h, hipMemsetAsync(out_row_index_dev, 0, 4, h->stream));
+      RJ_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return RJ_OK;
+  }
+  eliminate::Meta m;
+  RJ_HIP(h, map_eliminate_device(h->stream, xy_dev, np, row_index_dev, left_dev, right_dev, nc, tol_lo, tol_hi, flags, face_capacity, chain_capacity,
+                                 point_capacity, reinterpret_cast<eliminate::Face*>(faces_dev), out_left_dev, out_right_dev, out_xy_dev, out_row_index_dev,
+                                 chain_origin_dev, h->debug_elim_point_blocks, &m, &h->eliminate_report));
+  if (m.bad == rings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_eliminate: row_index must start at 0");
+  if (m.bad == rings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_eliminate: row_index must end at np");
+  if (m.bad == rings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_eliminate: row_index must ascend (a chain has no point)");
+  if (m.bad) return fail(h, RJ_E_INVALID, "rj_map_eliminate: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  if (m.unfinished) return fail(h, RJ_E_INTERNAL, "rj_map_eliminate: a face did not reach its target within %d jumping steps", eliminate::kMaxRounds);
+  memcpy(counts, &m.counts, sizeof(*counts));
+  if (!m.emit)
+    return fail(h, RJ_E_OVERFLOW, "rj_map_eliminate: %llu faces, %llu chains, %llu points; capacities %llu, %llu, %llu", (unsigned long long) counts->n_faces,
+                (unsigned long long) counts->n_chains, (unsigned long long) counts->n_points, (unsigned long long) face_capacity,
+                (unsigned long long) chain_capacity, (unsigned long long) point_capacity);
   return RJ_OK;
 }
 

@@ -46,6 +46,10 @@
       -- the label side (rj_map_faces): the faces of a chain map computed from its geometry alone, a face number on each
          side of every chain, the face records with exact areas; check=True tells whether a map's own labels describe the
          partition its geometry has (counts["n_conflicts"])
+  map_eliminate(handle, ...) / map_eliminate_rounds(handle, ...) / DeviceOutputMap.Eliminate(handle, tol) /
+      DeviceChainMap.Eliminate(handle, tol) -> DeviceEliminatedMap
+      -- what removes slivers (rj_map_eliminate): every face of at most tol joins the neighbour it shares the longest
+         border with, exactly, on the device; the chains between merged faces are dropped, rounds repeat the call
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -419,6 +423,12 @@ class DeviceOutputMap:
         change): what InstallMap, Rings() and Crossings() take; its counts are those of rj_map_simplify with n_chains and
         n_edges.  check: -> (the map, the counts of Crossings() on it) -- thinning can push a chain across another one"""
         return _simplified_chain_map(handle, self, tol, check, capacity)
+
+    def Eliminate(self, handle, tol, rounds=1, faces=False):
+        """map_eliminate of this map, on the device, as a DeviceEliminatedMap of its own: every face of area2 <= tol merged
+        into the neighbour with the longest shared border, the chains between merged faces dropped.  rounds > 1: repeated
+        (map_eliminate_rounds) until a round eliminates nothing or `rounds` have run; .rounds holds the counts of each"""
+        return _eliminated(handle, self, tol, rounds, faces)
 
     def free(self):
         for b in (self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin):
@@ -885,6 +895,12 @@ class DeviceChainMap:
         n_edges.  check: -> (the map, the counts of Crossings() on it) -- thinning can push a chain across another one"""
         return _simplified_chain_map(handle, self, tol, check, capacity)
 
+    def Eliminate(self, handle, tol, rounds=1, faces=False):
+        """map_eliminate of this map, on the device, as a DeviceEliminatedMap of its own: every face of area2 <= tol merged
+        into the neighbour with the longest shared border, the chains between merged faces dropped.  rounds > 1: repeated
+        (map_eliminate_rounds) until a round eliminates nothing or `rounds` have run; .rounds holds the counts of each"""
+        return _eliminated(handle, self, tol, rounds, faces)
+
     def Faces(self, handle, check=False):
         """map_faces of this map, on the device: its faces computed from the geometry alone, as a DeviceFacedMap of its own.
         check: this map's own left / right go in as the labels to check -- counts["n_conflicts"] == 0 tells that they and
@@ -951,6 +967,103 @@ class DeviceFacedMap(DeviceChainMap):
         super().free()
         if self.faces is not None:
             self.faces.free()
+
+
+def map_eliminate(handle, xy, n_points, row_index, left, right, n_chains, tol, drop=True, faces=False):
+    """A labelled chain map in device memory with its sliver faces merged into a neighbour (rj_map_eliminate) as a
+    DeviceEliminatedMap.  tol: a Python int in [0, 2^128), twice an area in scaled units^2: a face (a label other than 0)
+    whose area2 lies in [0, tol] joins the neighbour it shares the longest border with -- ties to the smaller pair of
+    labels, unsigned; two slivers that choose each other merge into the larger; chains of choices are followed to their
+    root.  One call is one round: a merged group may still be at most tol (map_eliminate_rounds repeats).  drop
+    (RJ_ELIM_DROP): the chains whose two labels became equal are left out, .origin holds the input chain of every output
+    chain; without it the map keeps its chains and only left / right change (xy / row_index are copies).  faces: also the
+    face records (.faces, ELIM_FACE_DTYPE rows ascending by unsigned label: label, target, best, flags, area2).  A sizing
+    call finds the capacities.  counts: ELIMINATE_COUNTS with n_edges."""
+    n_points, n_chains = int(n_points), int(n_chains)
+    flags = _capi.RJ_ELIM_DROP if drop else 0
+    args = (xy, n_points, row_index, left, right, n_chains, tol)
+    try:
+        c = handle.map_eliminate(*args, (0, 0, 0), None, None, flags=flags)
+    except _capi.EliminateOverflow as e:
+        c = e.counts
+    fc, cc, pc = c["n_faces"] if faces else 0, c["n_chains"], c["n_points"]
+    bufs, records, origin, done = [], None, None, False
+    try:
+        bufs.append(handle.alloc(16 * max(1, pc)))
+        bufs.append(handle.alloc(4 * (cc + 1)))
+        bufs.append(handle.alloc(4 * max(1, cc)))
+        bufs.append(handle.alloc(4 * max(1, cc)))
+        if drop:
+            origin = handle.alloc(4 * max(1, cc))
+        else:
+            if n_points:
+                bufs[0].from_device(xy, 16 * n_points)
+            if n_chains:
+                bufs[1].from_device(row_index, 4 * (n_chains + 1))
+        if not n_chains:
+            bufs[1].from_host(np.zeros(1, np.uint32))
+        if faces:
+            records = handle.alloc(_capi.ELIM_FACE_DTYPE.itemsize * max(1, fc))
+        counts = handle.map_eliminate(*args, (fc, cc, pc), bufs[2], bufs[3], bufs[0] if drop else None, bufs[1] if drop else None, origin, records,
+                                      flags=flags)
+        done = True
+    finally:
+        if not done:
+            for b in bufs + [records, origin]:
+                if b is not None:
+                    b.free()
+    return DeviceEliminatedMap(*bufs, dict(counts, n_edges=counts["n_points"] - counts["n_chains"]), records, origin)
+
+
+def map_eliminate_rounds(handle, xy, n_points, row_index, left, right, n_chains, tol, max_rounds=8, faces=False):
+    """map_eliminate with drop, repeated on its own result until a round has n_eliminated == 0 or max_rounds is hit -> the
+    last round's DeviceEliminatedMap with .rounds, the counts of every round that ran (the last one eliminated nothing
+    where the rounds ended: .rounds[-1]["n_eliminated"] == 0).  .origin is the last round's (chains of the round before)."""
+    per_round, m = [], None
+    args = (xy, n_points, row_index, left, right, n_chains)
+    for _ in range(max(1, int(max_rounds))):
+        nxt = map_eliminate(handle, *args, tol, drop=True, faces=faces)
+        if m is not None:
+            m.free()
+        m = nxt
+        per_round.append(dict(m.counts))
+        if m.counts["n_eliminated"] == 0:
+            break
+        args = (m.xy, m.n_points, m.row_index, m.left, m.right, m.n_chains)
+    m.rounds = per_round
+    return m
+
+
+class DeviceEliminatedMap(DeviceChainMap):
+    """A chain map in device memory whose left / right are the targets that rj_map_eliminate gave, with faces
+    (ELIM_FACE_DTYPE rows as a DeviceBuffer, or None), origin (uint32 per chain: its input chain; None without drop) and the
+    counts n_faces, n_slivers, n_eliminated, n_islands, n_mutual, n_negative, n_chains, n_points, n_dropped, n_edges."""
+
+    def __init__(self, xy, row_index, left, right, counts, faces, origin):
+        super().__init__(xy, row_index, left, right, counts)
+        self.faces, self.origin, self.n_faces = faces, origin, int(counts["n_faces"])
+        self.rounds = [dict(counts)]
+
+    def faces_to_host(self):
+        """-> the face records (ELIM_FACE_DTYPE), ascending by unsigned label"""
+        return self.faces.to_host(_capi.ELIM_FACE_DTYPE, self.n_faces)
+
+    def origin_to_host(self):
+        return self.origin.to_host(np.uint32, self.n_chains)
+
+    def free(self):
+        super().free()
+        for b in (self.faces, self.origin):
+            if b is not None:
+                b.free()
+
+
+def _eliminated(handle, m, tol, rounds, faces):
+    """DeviceOutputMap.Eliminate / DeviceChainMap.Eliminate"""
+    args = (m.xy, m.n_points, m.row_index, m.left, m.right, m.n_chains, tol)
+    if int(rounds) <= 1:
+        return map_eliminate(handle, *args, drop=True, faces=faces)
+    return map_eliminate_rounds(handle, *args, max_rounds=rounds, faces=faces)
 
 
 class DevicePolygons:
