@@ -426,8 +426,8 @@ typedef struct {
  * RJ_E_OVERFLOW when a count exceeds its capacity: *counts holds the true counts and nothing beyond any capacity is
  * written; all capacities 0 (arrays may be NULL) is the sizing call.  nc == 0 is valid.  A malformed map (the checks of
  * rj_upload_map_dev, but a chain may have a single point: an output map without RJ_OVM_DROP_DEGENERATE has such
- * chains, they are skipped) and an unknown flag bit are RJ_E_INVALID; RJ_E_INTERNAL when a round budget runs out (33 doubling
- * steps: cannot happen below 2^32 half-chains).  Runs on the handle's stream with one host sync, at the end, to read
+ * chains, they are skipped) and an unknown flag bit are RJ_E_INVALID, with nothing written; RJ_E_INTERNAL when a round budget
+ * runs out (33 doubling steps: cannot happen below 2^32 half-chains).  Runs on the handle's stream with one host sync, at the end, to read
  * the counts; scratch (352 bytes per chain plus the sorts' temporary storage) is allocated per call and freed; no
  * state of the handle (maps, indexes, plans) changes. */
 int rj_map_rings(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev,

@@ -185,90 +185,58 @@ class RayJoinError(RuntimeError):
         self.code = code
 
 
-class MapOverflow(RayJoinError):
+class CountsOverflow(RayJoinError):
+    """RJ_E_OVERFLOW of a call that reports its true counts: the base of the calls' own classes below"""
+
+    def __init__(self, msg, counts):
+        super().__init__(RJ_E_OVERFLOW, msg)
+        self.counts = counts
+
+
+class MapOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_overlay_map: counts = (chains, points, faces), the true counts"""
 
-    def __init__(self, msg, counts):
-        super().__init__(RJ_E_OVERFLOW, msg)
-        self.counts = counts
 
-
-class RingsOverflow(RayJoinError):
+class RingsOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_map_rings: counts = dict(n_rings, n_halves, n_points, n_mixed, n_skipped), the true counts"""
 
-    def __init__(self, msg, counts):
-        super().__init__(RJ_E_OVERFLOW, msg)
-        self.counts = counts
 
-
-class PolygonsOverflow(RayJoinError):
+class PolygonsOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_rings_polygons: counts = dict(n_polygons, n_members, n_holes, n_orphans, n_face0), the true counts"""
 
-    def __init__(self, msg, counts):
-        super().__init__(RJ_E_OVERFLOW, msg)
-        self.counts = counts
 
-
-class RingsMapOverflow(RayJoinError):
+class RingsMapOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_rings_map: counts = dict(n_chains, n_points, n_edges, n_closed, n_zero_edges, n_conflicts, n_dissolved),
     the true counts"""
 
-    def __init__(self, msg, counts):
-        super().__init__(RJ_E_OVERFLOW, msg)
-        self.counts = counts
 
-
-class CrossingsOverflow(RayJoinError):
+class CrossingsOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_map_crossings: counts = dict(n_found, n_proper, n_touch, n_overlap, n_equal, n_edges, n_zero_edges),
     the true counts"""
 
-    def __init__(self, msg, counts):
-        super().__init__(RJ_E_OVERFLOW, msg)
-        self.counts = counts
 
-
-class NodeOverflow(RayJoinError):
+class NodeOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_map_node: counts = dict(n_points, n_edges, n_cuts, n_cut_edges, n_max_cuts, n_used, n_proper, n_equal),
     the true counts"""
 
-    def __init__(self, msg, counts):
-        super().__init__(RJ_E_OVERFLOW, msg)
-        self.counts = counts
 
-
-class SnapOverflow(RayJoinError):
+class SnapOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_map_snap: counts = a dict of SNAP_COUNTS (rj_node_counts' fields, n_exact, n_at_end, n_stale), the
     true counts"""
 
-    def __init__(self, msg, counts):
-        super().__init__(RJ_E_OVERFLOW, msg)
-        self.counts = counts
 
-
-class FacesOverflow(RayJoinError):
+class FacesOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_map_faces: counts = dict(n_faces, n_rings, n_holes, n_outer, n_skipped, n_dangling, n_conflicts), the
     true counts; left / right are written in full"""
 
-    def __init__(self, msg, counts):
-        super().__init__(RJ_E_OVERFLOW, msg)
-        self.counts = counts
 
-
-class SimplifyOverflow(RayJoinError):
+class SimplifyOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_map_simplify: counts = dict(n_points, n_removed, n_rounds, n_closed, n_pinned_extra, n_max_round),
     the true counts"""
 
-    def __init__(self, msg, counts):
-        super().__init__(RJ_E_OVERFLOW, msg)
-        self.counts = counts
 
-
-class EliminateOverflow(RayJoinError):
+class EliminateOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_map_eliminate: counts = a dict of ELIMINATE_COUNTS, the true counts; nothing is written"""
-
-    def __init__(self, msg, counts):
-        super().__init__(RJ_E_OVERFLOW, msg)
-        self.counts = counts
 
 
 class QueueOverflow(RayJoinError):

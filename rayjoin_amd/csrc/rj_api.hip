@@ -282,14 +282,14 @@ struct rj_handle_s {
   // rj_map_crossings: 0 = choose / the default (tests force a shift and lower the budget; tools vary the two factors)
   int debug_cross_shift = 0, debug_cross_pair_budget = 0, debug_cross_extent_factor = 0, debug_cross_reg_factor = 0;
   CrossingsReport cross_report = {};  // what the last rj_map_crossings chose and took (reports only)
-  NodeReport node_report = {{-1, -1, -1, -1, -1, -1}};  // what the stages of the last rj_map_node took (reports only)
-  SnapReport snap_report = {{-1, -1, -1, -1, -1, -1}};  // what the stages of the last rj_map_snap took (reports only)
+  NodeReport node_report;  // what the stages of the last rj_map_node took (reports only)
+  SnapReport snap_report;  // what the stages of the last rj_map_snap took (reports only)
   int debug_simplify_all_points = 0;  // rj_map_simplify: 1 = every round looks at every point, no work list (tests: the same result)
-  SimplifyReport simplify_report = {{-1, -1, -1, -1, -1, -1}};  // what the last rj_map_simplify took (reports only)
+  SimplifyReport simplify_report;  // what the last rj_map_simplify took (reports only)
   int debug_faces_shift = 0;  // rj_map_faces: where the search for the grid's shift starts (0: choose; tests: the same result)
-  FacesReport faces_report = {{-1, -1, -1, -1, -1, -1}, 0, 0, 0, 0};  // what the last rj_map_faces chose and took (reports only)
+  FacesReport faces_report;  // what the last rj_map_faces chose and took (reports only)
   int debug_elim_point_blocks = 0;  // rj_map_eliminate: the grid of the chain sums and of the point scatter (0: by size; tests and sweeps: the same result)
-  EliminateReport eliminate_report = {{-1, -1, -1, -1, -1, -1}};  // what the last rj_map_eliminate took (reports only)
+  EliminateReport eliminate_report;  // what the last rj_map_eliminate took (reports only)
   uint32_t stitch_stats[4] = {0, 0, 0, 0};  // the last run cutting: ranking rounds, incidences on closed loops, rounds of the second ranking, closed chains
   char* strip_scratch = nullptr;  // grow-only temporaries of the column index's build
   size_t strip_scratch_bytes = 0;
@@ -750,6 +750,58 @@ const Report* find_report(const char* name, int* k) {
     if (r.per && tail[0] >= '0' && tail[0] < '0' + r.per && !tail[1]) { *k = tail[0] - '0'; return &r; }
   }
   return nullptr;
+}
+
+// ---- what the entry points over a chain map share (rj_map_rings ... rj_map_eliminate) ----
+// the refusal of entry point `name` for a status of the map check (rings::check_row, rings::check_coordinate; bad != 0)
+int fail_map_check(rj_handle h, const char* name, uint32_t bad) {
+  if (bad == rings::kBadStart) return fail(h, RJ_E_INVALID, "%s: row_index must start at 0", name);
+  if (bad == rings::kBadEnd) return fail(h, RJ_E_INVALID, "%s: row_index must end at np", name);
+  if (bad == rings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "%s: row_index must ascend (a chain has no point)", name);
+  return fail(h, RJ_E_INVALID, "%s: a coordinate lies outside the scaled range [-2^46, 2^46)", name);
+}
+// the output of a call on an empty map: the row's one entry, where the caller has an array
+int write_empty_row(rj_handle h, uint32_t* row_index_dev) {
+  if (row_index_dev) {
+    RJ_HIP(h, hipMemsetAsync(row_index_dev, 0, 4, h->stream));
+    RJ_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return RJ_OK;
+}
+// rj_map_node and rj_map_snap behind their layout checks: `name` the entry point, `drop_last` the name of its one flag
+// (both are node::kDropLast), `device` map_node_device or map_snap_device with its Meta, `report` the handle's member
+template <class Meta, class Device, class Report, class Counts>
+int map_cuts_call(rj_handle h, const char* name, const char* drop_last, Device device, Report rj_handle_s::*report, const int64_t* xy_dev, uint64_t np,
+                  const uint32_t* row_index_dev, uint64_t nc, const rj_crossing* cross_dev, uint64_t n_cross, uint32_t flags, uint64_t point_capacity,
+                  int64_t* out_xy_dev, uint32_t* out_row_index_dev, uint32_t* edge_origin_dev, Counts* counts) {
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "%s: counts is null", name);
+  memset(counts, 0, sizeof(*counts));
+  if (flags & ~node::kDropLast) return fail(h, RJ_E_INVALID, "%s: unknown flags 0x%x", name, flags);
+  if ((np && !xy_dev) || (nc && !row_index_dev) || (n_cross && !cross_dev)) return fail(h, RJ_E_INVALID, "%s: null input array", name);
+  if (np >= (1ull << 32) || nc > np || np - nc >= 0xFFFFFFFFull) return fail(h, RJ_E_INVALID, "%s: nc <= np < 2^32 and np - nc < 2^32 - 1", name);
+  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "%s: points without chains", name);
+  if (n_cross >= (1ull << 31)) return fail(h, RJ_E_INVALID, "%s: n_cross < 2^31", name);
+  if (nc == 0 && n_cross) return fail(h, RJ_E_INVALID, "%s: a record names an edge that the map does not have", name);
+  if (point_capacity && (!out_xy_dev || !out_row_index_dev)) return fail(h, RJ_E_INVALID, "%s: null output", name);
+  if (int r = set_device(h)) return r;
+  h->*report = Report{};
+  if (nc == 0) return write_empty_row(h, out_row_index_dev);  // no chains
+  Meta m;
+  RJ_HIP(h, device(h->stream, xy_dev, np, row_index_dev, nc, cross_dev, n_cross, flags, point_capacity, out_xy_dev, out_row_index_dev, edge_origin_dev, &m,
+                   &(h->*report)));
+  if (m.bad && m.bad <= rings::kBadStart) return fail_map_check(h, name, m.bad);
+  if (m.bad == node::kBadOpenChain)
+    return fail(h, RJ_E_INVALID, "%s: %s needs chains of two points or more whose first point equals the last", name, drop_last);
+  if (m.bad == node::kBadRecord) return fail(h, RJ_E_INVALID, "%s: a record needs eid[0] < eid[1] < ne and a kind in 1..4", name);
+  if (m.bad == node::kBadZeroEdge) return fail(h, RJ_E_INVALID, "%s: a record names an edge of zero length", name);
+  if (m.bad) return fail(h, RJ_E_INVALID, "%s: the records must strictly ascend by (eid[0], eid[1])", name);
+  memcpy(counts, &m.counts, sizeof(*counts));
+  if (np + counts->n_cuts >= (1ull << 32))
+    return fail(h, RJ_E_INVALID, "%s: %llu points and %llu cuts: np + n_cuts < 2^32", name, (unsigned long long) np, (unsigned long long) counts->n_cuts);
+  if (counts->n_points > point_capacity)
+    return fail(h, RJ_E_OVERFLOW, "%s: %llu points; capacity %llu", name, (unsigned long long) counts->n_points, (unsigned long long) point_capacity);
+  return RJ_OK;
 }
 
 }  // namespace
@@ -2812,10 +2864,7 @@ int rj_map_rings(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t
                        ring_capacity, half_capacity, point_capacity};
   rings::Meta m;
   RJ_HIP(h, map_rings_device(h->stream, xy_dev, np, row_index_dev, left_dev, right_dev, nc, flags, out, &m));
-  if (m.bad_map == rings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_rings: row_index must start at 0");
-  if (m.bad_map == rings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_rings: row_index must end at np");
-  if (m.bad_map == rings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_rings: row_index must ascend (a chain has no point)");
-  if (m.bad_map) return fail(h, RJ_E_INVALID, "rj_map_rings: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  if (m.bad_map) return fail_map_check(h, "rj_map_rings", m.bad_map);
   if (m.unfinished) return fail(h, RJ_E_INTERNAL, "rj_map_rings: a ring was not closed within %d doubling steps", rings::kMaxRounds);
   memcpy(counts, &m.counts, sizeof(*counts));
   if (counts->n_rings > ring_capacity || counts->n_halves > half_capacity || (points && counts->n_points > point_capacity))
@@ -2872,13 +2921,7 @@ int rj_rings_map(rj_handle h, const uint32_t* ring_row_dev, const int64_t* ring_
   if ((chain_capacity && (!row_index_dev || !left_dev || !right_dev)) || (point_capacity && !xy_dev))
     return fail(h, RJ_E_INVALID, "rj_rings_map: null output");
   if (int r = set_device(h)) return r;
-  if (n_rings == 0) {  // no rings: the row's one entry, where the caller has an array
-    if (row_index_dev) {
-      RJ_HIP(h, hipMemsetAsync(row_index_dev, 0, 4, h->stream));
-      RJ_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return RJ_OK;
-  }
+  if (n_rings == 0) return write_empty_row(h, row_index_dev);  // no rings
   const ringmap::Out out{xy_dev, row_index_dev, left_dev, right_dev, chain_capacity, point_capacity};
   ringmap::Meta m;
   RJ_HIP(h, rings_map_device(h->stream, ring_row_dev, ring_xy_dev, n_points, ring_face_dev, face_stride, n_rings, flags, out, &m));
@@ -2916,10 +2959,7 @@ int rj_map_crossings(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint
                                h->debug_cross_reg_factor ? (uint64_t) h->debug_cross_reg_factor : crossings::kRegFactor};
   crossings::Meta m;
   RJ_HIP(h, map_crossings_device(h->stream, xy_dev, np, row_index_dev, nc, capacity, out_dev, tuning, &m, &h->cross_report));
-  if (m.bad == crossings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_crossings: row_index must start at 0");
-  if (m.bad == crossings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_crossings: row_index must end at np");
-  if (m.bad == crossings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_crossings: row_index must ascend (a chain has no point)");
-  if (m.bad) return fail(h, RJ_E_INVALID, "rj_map_crossings: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  if (m.bad) return fail_map_check(h, "rj_map_crossings", m.bad);
   memcpy(counts, &m.counts, sizeof(*counts));
   const CrossingsReport& rep = h->cross_report;
   if (rep.over_budget && !rep.pair_tests)
@@ -2940,43 +2980,8 @@ int rj_map_node(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t*
                 rj_node_counts* counts) {
   static_assert(sizeof(rj_crossing) == sizeof(node::Record) && sizeof(rj_node_counts) == sizeof(node::Counts) && RJ_NODE_DROP_LAST == node::kDropLast,
                 "layouts");
-  RJ_CHECK_H(h);
-  if (!counts) return fail(h, RJ_E_INVALID, "rj_map_node: counts is null");
-  memset(counts, 0, sizeof(*counts));
-  if (flags & ~(uint32_t) RJ_NODE_DROP_LAST) return fail(h, RJ_E_INVALID, "rj_map_node: unknown flags 0x%x", flags);
-  if ((np && !xy_dev) || (nc && !row_index_dev) || (n_cross && !cross_dev)) return fail(h, RJ_E_INVALID, "rj_map_node: null input array");
-  if (np >= (1ull << 32) || nc > np || np - nc >= 0xFFFFFFFFull) return fail(h, RJ_E_INVALID, "rj_map_node: nc <= np < 2^32 and np - nc < 2^32 - 1");
-  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_node: points without chains");
-  if (n_cross >= (1ull << 31)) return fail(h, RJ_E_INVALID, "rj_map_node: n_cross < 2^31");
-  if (nc == 0 && n_cross) return fail(h, RJ_E_INVALID, "rj_map_node: a record names an edge that the map does not have");
-  if (point_capacity && (!out_xy_dev || !out_row_index_dev)) return fail(h, RJ_E_INVALID, "rj_map_node: null output");
-  if (int r = set_device(h)) return r;
-  h->node_report = NodeReport{{-1, -1, -1, -1, -1, -1}};
-  if (nc == 0) {  // no chains: the row's one entry, where the caller has an array
-    if (out_row_index_dev) {
-      RJ_HIP(h, hipMemsetAsync(out_row_index_dev, 0, 4, h->stream));
-      RJ_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return RJ_OK;
-  }
-  node::Meta m;
-  RJ_HIP(h, map_node_device(h->stream, xy_dev, np, row_index_dev, nc, cross_dev, n_cross, flags, point_capacity, out_xy_dev, out_row_index_dev,
-                            edge_origin_dev, &m, &h->node_report));
-  if (m.bad == crossings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_node: row_index must start at 0");
-  if (m.bad == crossings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_node: row_index must end at np");
-  if (m.bad == crossings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_node: row_index must ascend (a chain has no point)");
-  if (m.bad == crossings::kBadCoordinate) return fail(h, RJ_E_INVALID, "rj_map_node: a coordinate lies outside the scaled range [-2^46, 2^46)");
-  if (m.bad == node::kBadOpenChain)
-    return fail(h, RJ_E_INVALID, "rj_map_node: RJ_NODE_DROP_LAST needs chains of two points or more whose first point equals the last");
-  if (m.bad == node::kBadRecord) return fail(h, RJ_E_INVALID, "rj_map_node: a record needs eid[0] < eid[1] < ne and a kind in 1..4");
-  if (m.bad == node::kBadZeroEdge) return fail(h, RJ_E_INVALID, "rj_map_node: a record names an edge of zero length");
-  if (m.bad) return fail(h, RJ_E_INVALID, "rj_map_node: the records must strictly ascend by (eid[0], eid[1])");
-  memcpy(counts, &m.counts, sizeof(*counts));
-  if (np + counts->n_cuts >= (1ull << 32))
-    return fail(h, RJ_E_INVALID, "rj_map_node: %llu points and %llu cuts: np + n_cuts < 2^32", (unsigned long long) np, (unsigned long long) counts->n_cuts);
-  if (counts->n_points > point_capacity)
-    return fail(h, RJ_E_OVERFLOW, "rj_map_node: %llu points; capacity %llu", (unsigned long long) counts->n_points, (unsigned long long) point_capacity);
-  return RJ_OK;
+  return map_cuts_call<node::Meta>(h, "rj_map_node", "RJ_NODE_DROP_LAST", map_node_device, &rj_handle_s::node_report, xy_dev, np, row_index_dev, nc,
+                                   cross_dev, n_cross, flags, point_capacity, out_xy_dev, out_row_index_dev, edge_origin_dev, counts);
 }
 
 int rj_map_snap(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc, const rj_crossing* cross_dev, uint64_t n_cross,
@@ -2984,43 +2989,8 @@ int rj_map_snap(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t*
                 rj_snap_counts* counts) {
   static_assert(sizeof(rj_crossing) == sizeof(node::Record) && sizeof(rj_snap_counts) == sizeof(snap::Counts) && RJ_SNAP_DROP_LAST == snap::kDropLast,
                 "layouts");
-  RJ_CHECK_H(h);
-  if (!counts) return fail(h, RJ_E_INVALID, "rj_map_snap: counts is null");
-  memset(counts, 0, sizeof(*counts));
-  if (flags & ~(uint32_t) RJ_SNAP_DROP_LAST) return fail(h, RJ_E_INVALID, "rj_map_snap: unknown flags 0x%x", flags);
-  if ((np && !xy_dev) || (nc && !row_index_dev) || (n_cross && !cross_dev)) return fail(h, RJ_E_INVALID, "rj_map_snap: null input array");
-  if (np >= (1ull << 32) || nc > np || np - nc >= 0xFFFFFFFFull) return fail(h, RJ_E_INVALID, "rj_map_snap: nc <= np < 2^32 and np - nc < 2^32 - 1");
-  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_snap: points without chains");
-  if (n_cross >= (1ull << 31)) return fail(h, RJ_E_INVALID, "rj_map_snap: n_cross < 2^31");
-  if (nc == 0 && n_cross) return fail(h, RJ_E_INVALID, "rj_map_snap: a record names an edge that the map does not have");
-  if (point_capacity && (!out_xy_dev || !out_row_index_dev)) return fail(h, RJ_E_INVALID, "rj_map_snap: null output");
-  if (int r = set_device(h)) return r;
-  h->snap_report = SnapReport{{-1, -1, -1, -1, -1, -1}};
-  if (nc == 0) {  // no chains: the row's one entry, where the caller has an array
-    if (out_row_index_dev) {
-      RJ_HIP(h, hipMemsetAsync(out_row_index_dev, 0, 4, h->stream));
-      RJ_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return RJ_OK;
-  }
-  snap::Meta m;
-  RJ_HIP(h, map_snap_device(h->stream, xy_dev, np, row_index_dev, nc, cross_dev, n_cross, flags, point_capacity, out_xy_dev, out_row_index_dev,
-                            edge_origin_dev, &m, &h->snap_report));
-  if (m.bad == crossings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_snap: row_index must start at 0");
-  if (m.bad == crossings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_snap: row_index must end at np");
-  if (m.bad == crossings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_snap: row_index must ascend (a chain has no point)");
-  if (m.bad == crossings::kBadCoordinate) return fail(h, RJ_E_INVALID, "rj_map_snap: a coordinate lies outside the scaled range [-2^46, 2^46)");
-  if (m.bad == node::kBadOpenChain)
-    return fail(h, RJ_E_INVALID, "rj_map_snap: RJ_SNAP_DROP_LAST needs chains of two points or more whose first point equals the last");
-  if (m.bad == node::kBadRecord) return fail(h, RJ_E_INVALID, "rj_map_snap: a record needs eid[0] < eid[1] < ne and a kind in 1..4");
-  if (m.bad == node::kBadZeroEdge) return fail(h, RJ_E_INVALID, "rj_map_snap: a record names an edge of zero length");
-  if (m.bad) return fail(h, RJ_E_INVALID, "rj_map_snap: the records must strictly ascend by (eid[0], eid[1])");
-  memcpy(counts, &m.counts, sizeof(*counts));
-  if (np + counts->n_cuts >= (1ull << 32))
-    return fail(h, RJ_E_INVALID, "rj_map_snap: %llu points and %llu cuts: np + n_cuts < 2^32", (unsigned long long) np, (unsigned long long) counts->n_cuts);
-  if (counts->n_points > point_capacity)
-    return fail(h, RJ_E_OVERFLOW, "rj_map_snap: %llu points; capacity %llu", (unsigned long long) counts->n_points, (unsigned long long) point_capacity);
-  return RJ_OK;
+  return map_cuts_call<snap::Meta>(h, "rj_map_snap", "RJ_SNAP_DROP_LAST", map_snap_device, &rj_handle_s::snap_report, xy_dev, np, row_index_dev, nc,
+                                   cross_dev, n_cross, flags, point_capacity, out_xy_dev, out_row_index_dev, edge_origin_dev, counts);
 }
 
 int rj_map_simplify(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, uint64_t nc, uint64_t tol_lo, uint64_t tol_hi,
@@ -3036,21 +3006,12 @@ int rj_map_simplify(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint3
   if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_simplify: points without chains");
   if (point_capacity && (!out_xy_dev || !out_row_index_dev)) return fail(h, RJ_E_INVALID, "rj_map_simplify: null output");
   if (int r = set_device(h)) return r;
-  h->simplify_report = SimplifyReport{{-1, -1, -1, -1, -1, -1}};
-  if (nc == 0) {  // no chains: the row's one entry, where the caller has an array
-    if (out_row_index_dev) {
-      RJ_HIP(h, hipMemsetAsync(out_row_index_dev, 0, 4, h->stream));
-      RJ_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return RJ_OK;
-  }
+  h->simplify_report = SimplifyReport{};
+  if (nc == 0) return write_empty_row(h, out_row_index_dev);  // no chains
   simplify::Meta m;
   RJ_HIP(h, map_simplify_device(h->stream, xy_dev, np, row_index_dev, nc, tol_lo, tol_hi, h->debug_simplify_all_points != 0, point_capacity, out_xy_dev,
                                 out_row_index_dev, origin_dev, &m, &h->simplify_report));
-  if (m.bad == crossings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_simplify: row_index must start at 0");
-  if (m.bad == crossings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_simplify: row_index must end at np");
-  if (m.bad == crossings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_simplify: row_index must ascend (a chain has no point)");
-  if (m.bad) return fail(h, RJ_E_INVALID, "rj_map_simplify: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  if (m.bad) return fail_map_check(h, "rj_map_simplify", m.bad);
   memcpy(counts, &m.counts, sizeof(*counts));
   if (counts->n_points > point_capacity)
     return fail(h, RJ_E_OVERFLOW, "rj_map_simplify: %llu points; capacity %llu", (unsigned long long) counts->n_points, (unsigned long long) point_capacity);
@@ -3072,17 +3033,14 @@ int rj_map_faces(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t
   if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_faces: points without chains");
   if (nc && (!left_dev || !right_dev)) return fail(h, RJ_E_INVALID, "rj_map_faces: null output");
   if (int r = set_device(h)) return r;
-  h->faces_report = FacesReport{{-1, -1, -1, -1, -1, -1}, 0, 0, 0, 0};
+  h->faces_report = FacesReport{};
   if (nc == 0) return RJ_OK;
   rings::Meta rm;
   polygons::Meta pm;
   faces::Meta m;
   RJ_HIP(h, map_faces_device(h->stream, xy_dev, np, row_index_dev, nc, in_left_dev, in_right_dev, h->debug_faces_shift, face_capacity, left_dev,
                              right_dev, reinterpret_cast<faces::Face*>(faces_dev), &rm, &pm, &m, &h->faces_report));
-  if (rm.bad_map == rings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_faces: row_index must start at 0");
-  if (rm.bad_map == rings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_faces: row_index must end at np");
-  if (rm.bad_map == rings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_faces: row_index must ascend (a chain has no point)");
-  if (rm.bad_map) return fail(h, RJ_E_INVALID, "rj_map_faces: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  if (rm.bad_map) return fail_map_check(h, "rj_map_faces", rm.bad_map);
   if (rm.unfinished) return fail(h, RJ_E_INTERNAL, "rj_map_faces: a ring was not closed within %d doubling steps", rings::kMaxRounds);
   if (pm.unfinished) return fail(h, RJ_E_INTERNAL, "rj_map_faces: a hole did not reach its shell within %d jumping steps", faces::kMaxRounds);
   memcpy(counts, &m.counts, sizeof(*counts));
@@ -3113,22 +3071,13 @@ int rj_map_eliminate(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint
   if ((chain_capacity && (!out_left_dev || !out_right_dev || (drop && !out_row_index_dev))) || (point_capacity && !out_xy_dev))
     return fail(h, RJ_E_INVALID, "rj_map_eliminate: null output");
   if (int r = set_device(h)) return r;
-  h->eliminate_report = EliminateReport{{-1, -1, -1, -1, -1, -1}};
-  if (nc == 0) {  // no chains: under RJ_ELIM_DROP the row's one entry, where the caller has an array
-    if (drop && out_row_index_dev) {
-      RJ_HIP(h, hipMemsetAsync(out_row_index_dev, 0, 4, h->stream));
-      RJ_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return RJ_OK;
-  }
+  h->eliminate_report = EliminateReport{};
+  if (nc == 0) return write_empty_row(h, drop ? out_row_index_dev : nullptr);  // no chains: a row under RJ_ELIM_DROP only
   eliminate::Meta m;
   RJ_HIP(h, map_eliminate_device(h->stream, xy_dev, np, row_index_dev, left_dev, right_dev, nc, tol_lo, tol_hi, flags, face_capacity, chain_capacity,
                                  point_capacity, reinterpret_cast<eliminate::Face*>(faces_dev), out_left_dev, out_right_dev, out_xy_dev, out_row_index_dev,
                                  chain_origin_dev, h->debug_elim_point_blocks, &m, &h->eliminate_report));
-  if (m.bad == rings::kBadStart) return fail(h, RJ_E_INVALID, "rj_map_eliminate: row_index must start at 0");
-  if (m.bad == rings::kBadEnd) return fail(h, RJ_E_INVALID, "rj_map_eliminate: row_index must end at np");
-  if (m.bad == rings::kBadEmptyChain) return fail(h, RJ_E_INVALID, "rj_map_eliminate: row_index must ascend (a chain has no point)");
-  if (m.bad) return fail(h, RJ_E_INVALID, "rj_map_eliminate: a coordinate lies outside the scaled range [-2^46, 2^46)");
+  if (m.bad) return fail_map_check(h, "rj_map_eliminate", m.bad);
   if (m.unfinished) return fail(h, RJ_E_INTERNAL, "rj_map_eliminate: a face did not reach its target within %d jumping steps", eliminate::kMaxRounds);
   memcpy(counts, &m.counts, sizeof(*counts));
   if (!m.emit)

@@ -93,15 +93,14 @@ struct Meta {
 RJ_RHD uint64_t clamp_add(uint64_t a, uint64_t b) { return a + b < kClamp ? a + b : kClamp; }  // (a, b <= kClamp)
 
 // ---- 0. the input check ------------------------------------------------------------------------------
-// The largest code met is the input's status, 0: fine.  c in [0, nc]; every coordinate.
-constexpr uint32_t kBadStart = 4, kBadEnd = 3, kBadEmptyChain = 2, kBadCoordinate = 1;
-RJ_RHD uint32_t check_row(uint64_t c, const uint32_t* row, uint64_t nc, uint64_t np) {
-  const uint32_t b = row[c];
-  if (c == 0 && b != 0) return kBadStart;
-  if (c == nc) return (uint64_t) b != np ? kBadEnd : 0;
-  return row[c + 1] <= b ? kBadEmptyChain : 0;
-}
-RJ_RHD uint32_t check_coordinate(int64_t v) { return v < -kHalfRange || v >= kHalfRange ? kBadCoordinate : 0; }
+// The map check of rj_rings.h, one definition: the largest code met is the input's status, 0: fine.  c in [0, nc]; every
+// coordinate.
+using rings::check_coordinate;
+using rings::check_row;
+using rings::kBadCoordinate;
+using rings::kBadEmptyChain;
+using rings::kBadEnd;
+using rings::kBadStart;
 
 // ---- 1. edges ------------------------------------------------------------------------------------------
 // the chain of edge e: the last c with row[c] - c <= e (chains of one point have no edge and share that number with
@@ -241,7 +240,10 @@ struct CrossingsReport {
   int shift;
   uint64_t registrations, largest_run, largest_cell, pair_tests, n_items;
   bool over_budget;
-  float ms[6];  // edges and sums; registrations and their sort; runs and items; the pair pass; the sort of the hits; all
+  // edges and sums; registrations and their sort; runs and items; the pair pass; the sort of the hits; all.  StageMs'
+  // entries, but not its first state: 0 until a call reaches the device (a map without chains included), -1 from there
+  // on for what was not reached
+  float ms[6];
 };
 // rj_map_crossings behind its argument checks, on stream st: *result = the device's Meta (counts, the input check's
 // status).  Allocates and frees its scratch; synchronises the stream four times (the sums behind the grid's size; the

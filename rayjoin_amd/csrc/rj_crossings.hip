@@ -25,7 +25,6 @@ using namespace crossings;
 
 namespace {
 
-typedef unsigned long long ull;
 constexpr int kSums = kShifts + 2;  // the registrations per shift, then the two halves of the extent
 static_assert(offsetof(Meta, extent_hi) == offsetof(Meta, regs) + 8 * (kSums - 1), "the sums are one run of words");
 static_assert(offsetof(Meta, counts) + 8 == offsetof(Meta, counts.n_proper) && offsetof(Meta, counts.n_equal) == offsetof(Meta, counts.n_proper) + 24,
@@ -178,21 +177,6 @@ __global__ __launch_bounds__(kThreads) void k_cx_emit(uint64_t n, const uint64_t
   RJ_GRID_STRIDE(r, n) out[r] = make_uint4((uint32_t) (hit[r] >> 32), (uint32_t) hit[r], hit_kind[r], 0u);
 }
 
-struct Events {
-  hipEvent_t ev[7] = {};
-  int n = 0;
-  ~Events() {
-    for (hipEvent_t e : ev)
-      if (e) (void) hipEventDestroy(e);
-  }
-  hipError_t create() {
-    for (hipEvent_t& e : ev)
-      if (hipError_t r = hipEventCreate(&e)) return r;
-    return hipSuccess;
-  }
-  hipError_t mark(int k, hipStream_t st) { return hipEventRecord(ev[k], st); }
-};
-
 }  // namespace
 
 hipError_t warm_crossings_kernels(hipStream_t st) {
@@ -207,7 +191,7 @@ hipError_t map_crossings_device(hipStream_t st, const int64_t* xy, uint64_t np, 
   for (float& m : report->ms) m = -1.0f;
   const uint64_t ne = np - nc;
   result->counts.n_edges = ne;
-  Events ev;
+  StageEvents ev;
   hipError_t e = ev.create();
   if (e != hipSuccess) return e;
   char *blockA = nullptr, *blockB = nullptr, *blockC = nullptr;
@@ -364,10 +348,7 @@ hipError_t map_crossings_device(hipStream_t st, const int64_t* xy, uint64_t np, 
     e = hipStreamSynchronize(st);  // sync 4: nothing of this call runs when its scratch goes
   } while (0);
   if (e != hipSuccess) (void) hipStreamSynchronize(st);
-  if (e == hipSuccess) {
-    for (int k = 1; k <= marks; k++) (void) hipEventElapsedTime(&report->ms[k - 1], ev.ev[k - 1], ev.ev[k]);
-    if (marks) (void) hipEventElapsedTime(&report->ms[5], ev.ev[0], ev.ev[marks]);
-  }
+  if (e == hipSuccess) ev.times(marks, report->ms);
   hipError_t fe = hipFree(blockA);
   const hipError_t fb = hipFree(blockB), fc = hipFree(blockC);
   if (fe == hipSuccess) fe = fb != hipSuccess ? fb : fc;

@@ -224,9 +224,7 @@ RJ_RHD bool fits(const Counts& c, bool records, bool drop, uint64_t face_cap, ui
 
 #if defined(__HIPCC__)
 // what a call reports besides its counts
-struct EliminateReport {
-  float ms[6];  // the check and the chain sums; the faces; the pairs and the choice; the pointers; the new labels and the scatter; all
-};
+struct EliminateReport : StageMs {};  // the check and the chain sums; the faces; the pairs and the choice; the pointers; the new labels and the scatter; all
 // rj_map_eliminate behind its argument checks, on stream st: *result = the device's Meta.  point_blocks: the grid of the
 // two passes over the points (0: by size; any grid gives the same result).  Allocates and frees its scratch;
 // synchronises the stream once, at the end.

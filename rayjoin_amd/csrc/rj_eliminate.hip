@@ -32,8 +32,6 @@ using namespace eliminate;
 
 namespace {
 
-typedef unsigned long long ull;
-
 struct SumOp {
   __host__ __device__ U128 operator()(const U128& a, const U128& b) const { return rings::add(a, b); }
 };
@@ -43,12 +41,6 @@ struct BestOp {
 struct SameFrom {
   __host__ __device__ bool operator()(const uint64_t& a, const uint64_t& b) const { return from_of(a) == from_of(b); }
 };
-
-__device__ __forceinline__ void count_to(uint64_t* counter, uint32_t mine) {
-  const uint32_t sum = block_sum(mine);
-  if (threadIdx.x == 0 && sum) atomicAdd((ull*) counter, (ull) sum);
-  __syncthreads();  // (block_sum's partial sums are free again)
-}
 
 __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
   return ((uint64_t) __builtin_amdgcn_readfirstlane((uint32_t) (v >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t) v);
@@ -302,20 +294,6 @@ __global__ __launch_bounds__(kThreads) void k_el_emit(const int64_t* __restrict_
   }
 }
 
-struct Events {
-  hipEvent_t ev[6] = {};
-  ~Events() {
-    for (hipEvent_t e : ev)
-      if (e) (void) hipEventDestroy(e);
-  }
-  hipError_t create() {
-    for (hipEvent_t& e : ev)
-      if (hipError_t r = hipEventCreate(&e)) return r;
-    return hipSuccess;
-  }
-  hipError_t mark(int k, hipStream_t st) { return hipEventRecord(ev[k], st); }
-};
-
 }  // namespace
 
 hipError_t map_eliminate_device(hipStream_t st, const int64_t* xy, uint64_t np, const uint32_t* row, const int32_t* left, const int32_t* right, uint64_t nc,
@@ -323,8 +301,8 @@ hipError_t map_eliminate_device(hipStream_t st, const int64_t* xy, uint64_t np, 
                                 int32_t* out_left, int32_t* out_right, int64_t* out_xy, uint32_t* out_row, uint32_t* origin, int point_blocks,
                                 Meta* result, EliminateReport* report) {
   memset(result, 0, sizeof(Meta));
-  for (float& m : report->ms) m = -1.0f;
-  Events ev;
+  *report = EliminateReport{};
+  StageEvents ev;
   hipError_t e = ev.create();
   if (e != hipSuccess) return e;
   const bool drop = (flags & kDrop) != 0;
@@ -450,10 +428,7 @@ hipError_t map_eliminate_device(hipStream_t st, const int64_t* xy, uint64_t np, 
     done = e == hipSuccess;
   } while (0);
   if (e != hipSuccess) (void) hipStreamSynchronize(st);
-  if (done) {
-    for (int k = 0; k < 5; k++) (void) hipEventElapsedTime(&report->ms[k], ev.ev[k], ev.ev[k + 1]);
-    (void) hipEventElapsedTime(&report->ms[5], ev.ev[0], ev.ev[5]);
-  }
+  if (done) ev.times(5, report->ms);
   const hipError_t fe = hipFree(block);
   return e != hipSuccess ? e : fe;
 }

@@ -340,8 +340,7 @@ RJ_RHD uint32_t half_face(uint32_t h, const uint32_t* ring_of_half, const Jump* 
 
 #if defined(__HIPCC__)
 // what a call reports besides its counts
-struct FacesReport {
-  float ms[6];  // the ring stages; tops and kinds; the grid; the rays; parents and faces; all (-1: not reached)
+struct FacesReport : StageMs {  // the ring stages; tops and kinds; the grid; the rays; parents and faces; all
   int shift;
   uint64_t registrations, ray_tests, cells;
 };

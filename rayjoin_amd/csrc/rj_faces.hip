@@ -251,7 +251,7 @@ hipError_t map_faces_device(hipStream_t st, const int64_t* xy, uint64_t np, cons
   memset(rmeta_out, 0, sizeof(rings::Meta));
   memset(pmeta_out, 0, sizeof(polygons::Meta));
   memset(result, 0, sizeof(Meta));
-  *report = FacesReport{{-1, -1, -1, -1, -1, -1}, 0, 0, 0, 0};
+  *report = FacesReport{};
   const uint32_t nc = (uint32_t) nc64, ni = 2 * nc;
   const uint64_t n1 = (uint64_t) ni + 1, ne = np - nc64, cap = reg_cap(ne), np1 = np + 1;
   int rounds = 1;  // walks of up to 2^(rounds - 1) steps

@@ -25,7 +25,7 @@
 //         kDropLast every chain must have at least 2 points with the first equal to the last, and is written without
 //         its last point: point slot k is then exactly output edge k.
 //
-// Every step is one function per element that rj_node.hip runs as a grid-stride kernel and
+// Every step is one function per element that rj_node.hip / rj_cut_pipeline.h run as a grid-stride kernel and
 // tests/hosttwin/node_twin.cc runs as a plain loop (a test-only twin, never a fallback):
 //
 //   check_row / check_coordinate (rj_crossings.h) / check_chain / check_record   the input check: the largest code met
@@ -169,9 +169,7 @@ RJ_RHD void totals(uint64_t np, uint64_t nc, uint64_t n_cuts, uint32_t flags, ui
 
 #if defined(__HIPCC__)
 // what a call reports besides its counts
-struct NodeReport {
-  float ms[6];  // the check; the candidates; the sort and the kept cuts; the cuts per edge and their scan; the two scatters; all
-};
+struct NodeReport : StageMs {};  // the check; the candidates; the sort and the kept cuts; the cuts per edge and their scan; the two scatters; all
 // rj_map_node behind its argument checks, on stream st: *result = the device's Meta (counts, the input check's status,
 // whether the output was written).  Allocates and frees its scratch; synchronises the stream once, at the end.
 hipError_t map_node_device(hipStream_t st, const int64_t* xy, uint64_t np, const uint32_t* row, uint64_t nc, const void* rec, uint64_t n_rec,

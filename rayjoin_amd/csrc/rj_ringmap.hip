@@ -36,11 +36,6 @@ struct SlotsSum {
   __host__ __device__ Slots operator()(const Slots& a, const Slots& b) const { return Slots{a.halves + b.halves, a.points + b.points}; }
 };
 
-__device__ __forceinline__ void count_to(uint64_t* counter, uint32_t mine) {
-  const uint32_t sum = block_sum(mine);
-  if (threadIdx.x == 0 && sum) atomicAdd((unsigned long long*) counter, (unsigned long long) sum);
-}
-
 __global__ __launch_bounds__(kThreads) void k_rm_check(const uint32_t* __restrict__ row, uint64_t nr, const int64_t* __restrict__ xy, uint64_t np,
                                                        Meta* meta) {
   uint32_t bad = 0;
@@ -86,7 +81,6 @@ __global__ __launch_bounds__(kThreads) void k_rm_keep(uint64_t n, const int32_t*
     dissolved += (what >> 1) & 1;
   }
   count_to(&meta->counts.n_conflicts, conflicts);
-  __syncthreads();  // (block_sum's partial sums are read before they are written again)
   count_to(&meta->counts.n_dissolved, dissolved);
 }
 __global__ __launch_bounds__(kThreads) void k_rm_edges(uint64_t n, const uint32_t* __restrict__ sv, const Seg* __restrict__ seg,

@@ -60,6 +60,7 @@
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#include "rj_pipeline.h"  // (StageMs: what the reports of the map pipelines, in the headers that include this one, derive from)
 #define RJ_RHD __host__ __device__ __forceinline__
 #else
 #define RJ_RHD inline

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void k_rg_place(uint32_t ni, const int64_
 }
 __global__ __launch_bounds__(kThreads) void k_rg_emit(uint32_t ni, const uint64_t* __restrict__ skeys, const Slots* __restrict__ base,
                                                       const U128* __restrict__ xbase, const uint32_t* __restrict__ mixed, Out o, Meta* meta) {
-  if (meta->unfinished) return;
+  if (meta->bad_map || meta->unfinished) return;  // (a refused map writes nothing, not even the CSRs' one entry of no rings)
   const uint64_t n_rings = meta->counts.n_rings;  // (<= ni: base and xbase have ni + 1 entries)
   uint32_t mine = 0;
   RJ_GRID_STRIDE(r, n_rings + 1) mine += ring_emit((uint32_t) r, skeys, base, xbase, mixed, o, meta) ? 1u : 0u;

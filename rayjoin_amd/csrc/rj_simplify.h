@@ -160,10 +160,9 @@ RJ_RHD void totals(uint64_t np, uint64_t total, uint64_t capacity, Counts* count
 
 #if defined(__HIPCC__)
 // what a call reports besides its counts
-struct SimplifyReport {
+struct SimplifyReport : StageMs {  // the check; the links and the pins; the first round; the later rounds; the scan and the scatter; all
   static constexpr int kRounds = 10;
-  float ms[6];  // the check; the links and the pins; the first round; the later rounds; the scan and the scatter; all
-  uint64_t n_syncs;                  // host syncs of the call
+  uint64_t n_syncs;                 // host syncs of the call
   uint64_t list_sum, list_max;       // the work lists of the rounds behind the first: their sizes summed, the largest
   uint64_t round_list[kRounds];      // round k: the points it looked at (np in the first round) ...
   float round_ms[kRounds], late_ms;  // ... and the host's time from its first launch to its sync; the rounds from kRounds on, summed

@@ -27,14 +27,6 @@ using namespace simplify;
 
 namespace {
 
-typedef unsigned long long ull;
-
-__device__ __forceinline__ void count_to(uint64_t* counter, uint32_t mine) {
-  const uint32_t sum = block_sum(mine);
-  if (threadIdx.x == 0 && sum) atomicAdd((ull*) counter, (ull) sum);
-  __syncthreads();  // (block_sum's partial sums are free again)
-}
-
 // the best of the wave's 64 pairs, in every lane (`better` orders distinct points strictly: all lanes agree)
 __device__ __forceinline__ Best wave_best(Best mine) {
   for (int d = 32; d >= 1; d >>= 1) {
@@ -204,20 +196,6 @@ __global__ __launch_bounds__(kThreads) void k_sp_scatter(const int64_t* __restri
   }
 }
 
-struct Events {
-  hipEvent_t ev[6] = {};
-  ~Events() {
-    for (hipEvent_t e : ev)
-      if (e) (void) hipEventDestroy(e);
-  }
-  hipError_t create() {
-    for (hipEvent_t& e : ev)
-      if (hipError_t r = hipEventCreate(&e)) return r;
-    return hipSuccess;
-  }
-  hipError_t mark(int k, hipStream_t st) { return hipEventRecord(ev[k], st); }
-};
-
 }  // namespace
 
 hipError_t map_simplify_device(hipStream_t st, const int64_t* xy, uint64_t np, const uint32_t* row, uint64_t nc, uint64_t tol_lo, uint64_t tol_hi,
@@ -225,8 +203,7 @@ hipError_t map_simplify_device(hipStream_t st, const int64_t* xy, uint64_t np, c
                                SimplifyReport* report) {
   memset(result, 0, sizeof(Meta));
   *report = SimplifyReport{};
-  for (float& m : report->ms) m = -1.0f;
-  Events ev;
+  StageEvents ev;
   hipError_t e = ev.create();
   if (e != hipSuccess) return e;
   char* block = nullptr;
@@ -332,8 +309,7 @@ hipError_t map_simplify_device(hipStream_t st, const int64_t* xy, uint64_t np, c
   if (done) {
     result->counts.n_rounds = n_rounds;
     result->counts.n_max_round = n_max_round;
-    for (int k = 0; k < 5; k++) (void) hipEventElapsedTime(&report->ms[k], ev.ev[k], ev.ev[k + 1]);
-    (void) hipEventElapsedTime(&report->ms[5], ev.ev[0], ev.ev[5]);
+    ev.times(5, report->ms);
   }
   const hipError_t fe = hipFree(block);
   return e != hipSuccess ? e : fe;

@@ -38,7 +38,7 @@
 //         n_stale.  On records without a kProper kind the output arrays and the eight shared counts equal rj_map_node's
 //         bit for bit.
 //
-// Every step is one function per element that rj_snap.hip runs as a grid-stride kernel and
+// Every step is one function per element that rj_snap.hip / rj_cut_pipeline.h run as a grid-stride kernel and
 // tests/hosttwin/snap_twin.cc runs as a plain loop (a test-only twin, never a fallback):
 //
 //   node::check_chain / node::check_record and the map check of rj_crossings.h   the input check, as rj_map_node's
@@ -184,9 +184,7 @@ RJ_RHD void totals(uint64_t np, uint64_t nc, uint64_t n_cuts, uint32_t flags, ui
 
 #if defined(__HIPCC__)
 // what a call reports besides its counts
-struct SnapReport {
-  float ms[6];  // the check; the candidates; the sort and the kept cuts; the cuts per edge and their scan; the two scatters; all
-};
+struct SnapReport : StageMs {};  // the check; the candidates; the sort and the kept cuts; the cuts per edge and their scan; the two scatters; all
 // rj_map_snap behind its argument checks, on stream st: *result = the device's Meta (counts, the input check's status,
 // whether the output was written).  Allocates and frees its scratch; synchronises the stream once, at the end.
 hipError_t map_snap_device(hipStream_t st, const int64_t* xy, uint64_t np, const uint32_t* row, uint64_t nc, const void* rec, uint64_t n_rec,

@@ -535,6 +535,39 @@ def _simplified_chain_map(handle, m, tol, check, capacity):
         raise
 
 
+def _records_on_device(handle, xy, n_points, row_index, n_chains, records):
+    """The records that map_node / map_snap take -> (a DeviceBuffer that the caller frees, or None; their number).  records:
+    the host CROSSING_DTYPE array, uploaded; None: rj_map_crossings runs here and its records stay on the device"""
+    if records is None:
+        rec, c = _crossings_on_device(handle, xy, n_points, row_index, n_chains)
+        return rec, c["n_found"]
+    records = np.ascontiguousarray(records, dtype=_capi.CROSSING_DTYPE)
+    n_rec = len(records)
+    return (handle.alloc(_capi.CROSSING_DTYPE.itemsize * n_rec).from_host(records) if n_rec else None), n_rec
+
+
+def _cuts_call(call, overflow, handle, xy, n_points, row_index, n_chains, rec, n_rec, flags, edge_origin, capacity):
+    """handle.map_node or handle.map_snap (call, with its overflow class) with the records in device memory (rec may be None
+    with n_rec == 0) -> DeviceNodedMap.  capacity None: a sizing call finds it.  The three buffers are freed on an error"""
+    bufs = []
+    try:
+        args = (xy, n_points, row_index, n_chains, rec, n_rec, flags)
+        if capacity is None:
+            try:
+                capacity = call(*args, 0, None, None)["n_points"]
+            except overflow as e:
+                capacity = e.counts["n_points"]
+        capacity = int(capacity)
+        bufs = [handle.alloc(16 * max(1, capacity)), handle.alloc(4 * (int(n_chains) + 1)), handle.alloc(4 * max(1, capacity)) if edge_origin else None]
+        counts = call(*args, capacity, *bufs)
+    except _capi.RayJoinError:
+        for b in bufs:
+            if b is not None:
+                b.free()
+        raise
+    return DeviceNodedMap(*bufs, counts, n_chains, bool(flags & _capi.RJ_NODE_DROP_LAST))  # (RJ_SNAP_DROP_LAST is the same bit)
+
+
 def map_node(handle, xy, n_points, row_index, n_chains, records=None, drop_last=False, edge_origin=False, capacity=None):
     """A chain map in device memory with every edge cut at the vertices that lie inside it (rj_map_node) as a
     DeviceNodedMap: the exact repair of T-junctions and half-shared borders, the RJ_CROSS_TOUCH and RJ_CROSS_OVERLAP
@@ -544,55 +577,18 @@ def map_node(handle, xy, n_points, row_index, n_chains, records=None, drop_last=
     point == last) and writes each without its last point, the ring layout that rings_map takes.  edge_origin: also the
     input edge of every output edge.  counts["n_proper"]: the crossings that noding cannot repair.  capacity (points):
     NodeOverflow with the true counts when it is too small; left open, a sizing call finds it."""
-    flags = _capi.RJ_NODE_DROP_LAST if drop_last else 0
-    if records is None:
-        rec, c = _crossings_on_device(handle, xy, n_points, row_index, n_chains)
-        n_rec = c["n_found"]
-    else:
-        records = np.ascontiguousarray(records, dtype=_capi.CROSSING_DTYPE)
-        n_rec = len(records)
-        rec = handle.alloc(_capi.CROSSING_DTYPE.itemsize * n_rec).from_host(records) if n_rec else None
-    bufs = []
+    rec, n_rec = _records_on_device(handle, xy, n_points, row_index, n_chains, records)
     try:
-        args = (xy, n_points, row_index, n_chains, rec, n_rec, flags)
-        if capacity is None:
-            try:
-                capacity = handle.map_node(*args, 0, None, None)["n_points"]
-            except _capi.NodeOverflow as e:
-                capacity = e.counts["n_points"]
-        capacity = int(capacity)
-        bufs = [handle.alloc(16 * max(1, capacity)), handle.alloc(4 * (int(n_chains) + 1)), handle.alloc(4 * max(1, capacity)) if edge_origin else None]
-        counts = handle.map_node(*args, capacity, *bufs)
-    except _capi.RayJoinError:
-        for b in bufs:
-            if b is not None:
-                b.free()
-        raise
+        return _cuts_call(handle.map_node, _capi.NodeOverflow, handle, xy, n_points, row_index, n_chains, rec, n_rec,
+                          _capi.RJ_NODE_DROP_LAST if drop_last else 0, edge_origin, capacity)
     finally:
         if rec is not None:
             rec.free()
-    return DeviceNodedMap(*bufs, counts, n_chains, drop_last)
 
 
 def _snap_call(handle, xy, n_points, row_index, n_chains, rec, n_rec, flags, edge_origin, capacity):
     """rj_map_snap with the records in device memory (rec may be None with n_rec == 0) -> DeviceNodedMap"""
-    bufs = []
-    try:
-        args = (xy, n_points, row_index, n_chains, rec, n_rec, flags)
-        if capacity is None:
-            try:
-                capacity = handle.map_snap(*args, 0, None, None)["n_points"]
-            except _capi.SnapOverflow as e:
-                capacity = e.counts["n_points"]
-        capacity = int(capacity)
-        bufs = [handle.alloc(16 * max(1, capacity)), handle.alloc(4 * (int(n_chains) + 1)), handle.alloc(4 * max(1, capacity)) if edge_origin else None]
-        counts = handle.map_snap(*args, capacity, *bufs)
-    except _capi.RayJoinError:
-        for b in bufs:
-            if b is not None:
-                b.free()
-        raise
-    return DeviceNodedMap(*bufs, counts, n_chains, bool(flags & _capi.RJ_SNAP_DROP_LAST))
+    return _cuts_call(handle.map_snap, _capi.SnapOverflow, handle, xy, n_points, row_index, n_chains, rec, n_rec, flags, edge_origin, capacity)
 
 
 def map_snap(handle, xy, n_points, row_index, n_chains, records=None, drop_last=False, edge_origin=False, capacity=None):
@@ -600,16 +596,9 @@ def map_snap(handle, xy, n_points, row_index, n_chains, records=None, drop_last=
     every RJ_CROSS_PROPER record cuts both of its edges at the crossing point rounded to integers (halves toward
     +infinity), the other kinds cut as in map_node.  One call: the rounding can make new crossings -- map_snap_rounds
     repeats it.  records, drop_last, edge_origin, capacity: as map_node (SnapOverflow past the capacity)."""
-    flags = _capi.RJ_SNAP_DROP_LAST if drop_last else 0
-    if records is None:
-        rec, c = _crossings_on_device(handle, xy, n_points, row_index, n_chains)
-        n_rec = c["n_found"]
-    else:
-        records = np.ascontiguousarray(records, dtype=_capi.CROSSING_DTYPE)
-        n_rec = len(records)
-        rec = handle.alloc(_capi.CROSSING_DTYPE.itemsize * n_rec).from_host(records) if n_rec else None
+    rec, n_rec = _records_on_device(handle, xy, n_points, row_index, n_chains, records)
     try:
-        return _snap_call(handle, xy, n_points, row_index, n_chains, rec, n_rec, flags, edge_origin, capacity)
+        return _snap_call(handle, xy, n_points, row_index, n_chains, rec, n_rec, _capi.RJ_SNAP_DROP_LAST if drop_last else 0, edge_origin, capacity)
     finally:
         if rec is not None:
             rec.free()
