@@ -813,7 +813,7 @@ typedef struct { uint64_t n_faces, n_slivers, n_eliminated, n_islands, n_mutual,
  * chains are written in input order with their points into out_xy_dev[2 point_capacity] and
  * out_row_index_dev[chain_capacity + 1], their labels into out_left_dev / out_right_dev[chain_capacity], and
  * chain_origin_dev[k] (may be NULL) is the input chain of output chain k.  Chains are NOT re-joined at vertices that
- * drop to degree 2: that is rj_map_rings followed by rj_rings_map, as for every other map.
+ * drop to degree 2: that is rj_map_dissolve with RJ_DISS_KEEP_EQUAL, as for every other map.
  * All capacities 0 (arrays may be NULL) is the sizing call.  RJ_E_OVERFLOW when a count exceeds its capacity: *counts
  * holds the true counts and nothing is written.  nc == 0 is valid.  RJ_E_INVALID, with nothing written: the map checks
  * of rj_map_rings and an unknown flag bit.  RJ_E_INTERNAL when the budget of 33 jumping rounds runs out (the order on
@@ -831,6 +831,59 @@ int rj_map_eliminate(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint
                      rj_elim_face* faces_dev /* may be NULL */, int32_t* out_left_dev, int32_t* out_right_dev,
                      int64_t* out_xy_dev, uint32_t* out_row_index_dev, uint32_t* chain_origin_dev /* may be NULL */,
                      rj_eliminate_counts* counts);
+
+/* ---- dissolve: faces that share a class become one face; chains that meet two by two become one chain ---- */
+#define RJ_DISS_KEEP_EQUAL 1u   /* keep chains whose two classes are equal: join only, nothing dissolves */
+typedef struct { int32_t label; uint32_t n_sides; uint64_t area2_lo; int64_t area2_hi; } rj_diss_class; /* 24 bytes */
+typedef struct { uint64_t n_kept, n_dropped, n_skipped, n_chains, n_points, n_closed, n_classes, n_unmapped; } rj_dissolve_counts;
+
+/* extends: what GIS users know as Dissolve, and the re-joining of chains that rj_map_eliminate and the overlay
+ * operations leave behind, in one chain-level call on the device: it sorts the 2 nc chain ends, never an edge.
+ * (The reference has no counterpart.)
+ * Input: xy_dev[2 np], row_index_dev[nc + 1], left_dev[nc], right_dev[nc] with the contract, the checks and the size limits
+ * of rj_map_eliminate (a chain may have a single point); labels are any int32.
+ * The definition, in full in rayjoin_amd/csrc/rj_dissolve.h:
+ *   class(0) = 0; with class_dev NULL class(f) = f, otherwise class(f) = class_dev[f] for 0 < f < n_labels.  A nonzero
+ *   label outside that range is counted in n_unmapped: the call is RJ_E_INVALID then, nothing is written and *counts
+ *   holds n_unmapped.  A nonzero label may map to 0, which erases the face into the outside.
+ *   A chain whose points are all equal is skipped (n_skipped).  Of the others a chain is kept (n_kept) unless
+ *   class(left) == class(right) and RJ_DISS_KEEP_EQUAL is not set (n_dropped): bridges and dangles go with the borders
+ *   unless the flag keeps them.
+ *   Half-chain h = 2 c walks chain c first -> last with classes (L, R), h = 2 c + 1 last -> first with (R, L).  h arrives
+ *   at the start point of h ^ 1; when exactly two kept half-chains start there (h ^ 1 and one other, g) and
+ *   classes(g) == classes(h), next(h) = g; otherwise h ends there (a junction, a dead end, a change of classes).  A closed
+ *   chain alone at its vertex has next(h) = h.  Walks are the maximal sequences under next, open or closed; the leader
+ *   of an open walk is its first half-chain, of a closed walk its smallest, and the walk is read from there.  Of a walk
+ *   and its twin (the twins in reverse order) the one with the smaller leader is an output chain.
+ * Output, caller-owned device memory: the chains ascend by leader into out_xy_dev[2 point_capacity],
+ * out_row_index_dev[chain_capacity + 1], out_left_dev / out_right_dev[chain_capacity] (the classes of the leader).  The
+ * points of a chain are every half-chain's points in its direction without its last point, then the last point of the last
+ * half-chain, copied verbatim; a closed chain repeats its first point; every chain has at least 2 points: a map that
+ * rj_upload_map_dev takes.  chain_origin_dev[chain_capacity] (may be NULL): the leader's input chain.
+ * chain_out_dev[nc] (may be NULL): (k << 1) | reversed for a kept input chain that output chain k holds, 0xFFFFFFFF for
+ * a dropped or skipped one.  classes_dev[class_capacity] (may be NULL: no records, class_capacity is ignored): one
+ * record per nonzero class value on a kept chain, ascending by (uint32_t) label -- area2 the sum of S(c) over the kept
+ * chains with the class on the left minus the sum over those with it on the right (S as in rj_map_eliminate, a
+ * two's-complement int128), n_sides the kept chain sides that carry it.  n_points = the edges of the kept chains +
+ * n_chains; n_closed: the output chains that are closed walks.
+ * All capacities 0 (arrays may be NULL) is the sizing call.  RJ_E_OVERFLOW when a count exceeds its capacity: *counts
+ * holds the true counts and nothing is written.  nc == 0 is valid and writes out_row_index_dev[0] = 0 where that pointer is
+ * given.  RJ_E_INVALID, with nothing written: the map checks, an unknown flag bit, null arrays, class_dev with
+ * n_labels == 0, unmapped labels.  RJ_E_INTERNAL when the budget of 33 doubling rounds runs out (cannot happen).
+ * Integers only, exact, fully determined.  Runs on the handle's stream with one host sync, at the end; scratch
+ * (rj_dissolve.h: 388 bytes per chain, none per point) is allocated per call and freed; no map, index or option of the
+ * handle changes.  For tests and sweeps, through rj_set_debug_option: "dissolve_point_blocks" (0: by size) is the grid of
+ * the point scatter; any grid gives the same result.  rj_get_option: "dissolve_last_us0" .. "dissolve_last_us5"
+ * (HIP-event microseconds of the stages: check, classes and keep; ends sorted and next; walks; class records; totals
+ * and scatter; all; -1: not reached). */
+int rj_map_dissolve(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev,
+                    const int32_t* left_dev, const int32_t* right_dev, uint64_t nc,
+                    const int32_t* class_dev /* may be NULL */, uint64_t n_labels, uint32_t flags,
+                    uint64_t class_capacity, uint64_t chain_capacity, uint64_t point_capacity,
+                    rj_diss_class* classes_dev /* may be NULL */, int32_t* out_left_dev, int32_t* out_right_dev,
+                    int64_t* out_xy_dev, uint32_t* out_row_index_dev,
+                    uint32_t* chain_origin_dev /* may be NULL */, uint32_t* chain_out_dev /* may be NULL */,
+                    rj_dissolve_counts* counts);
 
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {

@@ -60,6 +60,10 @@ RJ_ELIM_DROP = 1  # rj_map_eliminate flags
 RJ_ELIM_SLIVER, RJ_ELIM_ELIMINATED, RJ_ELIM_ISLAND, RJ_ELIM_NEGATIVE = 1, 2, 4, 8  # rj_elim_face flags
 # rj_elim_face: one face (a label) of rj_map_eliminate -- the face it joins, the neighbour it chose, RJ_ELIM_*, twice its own area
 ELIM_FACE_DTYPE = np.dtype([("label", "<i4"), ("target", "<i4"), ("best", "<i4"), ("flags", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
+RJ_DISS_KEEP_EQUAL = 1  # rj_map_dissolve flags
+# rj_diss_class: one class of rj_map_dissolve -- its label, the kept chain sides that carry it, twice its area
+DISS_CLASS_DTYPE = np.dtype([("label", "<i4"), ("n_sides", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
+DISSOLVE_COUNTS = ("n_kept", "n_dropped", "n_skipped", "n_chains", "n_points", "n_closed", "n_classes", "n_unmapped")
 ELIMINATE_COUNTS = ("n_faces", "n_slivers", "n_eliminated", "n_islands", "n_mutual", "n_negative", "n_chains", "n_points", "n_dropped")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
@@ -118,6 +122,7 @@ SYMBOLS = {
     "rj_map_simplify": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _u64, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
     "rj_map_faces": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
     "rj_map_eliminate": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _u64, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rj_map_dissolve": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -237,6 +242,18 @@ class SimplifyOverflow(CountsOverflow):
 
 class EliminateOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_map_eliminate: counts = a dict of ELIMINATE_COUNTS, the true counts; nothing is written"""
+
+
+class DissolveOverflow(CountsOverflow):
+    """RJ_E_OVERFLOW of rj_map_dissolve: counts = a dict of DISSOLVE_COUNTS, the true counts; nothing is written"""
+
+
+class DissolveUnmapped(RayJoinError):
+    """RJ_E_INVALID of rj_map_dissolve for labels outside the class table: n_unmapped chain sides carry one; nothing is written"""
+
+    def __init__(self, msg, n_unmapped):
+        super().__init__(RJ_E_INVALID, msg)
+        self.n_unmapped = n_unmapped
 
 
 class QueueOverflow(RayJoinError):
@@ -712,6 +729,27 @@ class Handle:
         named = dict(zip(ELIMINATE_COUNTS, (int(v) for v in counts)))
         if rc == RJ_E_OVERFLOW:
             raise EliminateOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        self._check(rc)
+        return named
+
+    def map_dissolve(self, xy_dev, n_points, row_index_dev, left_dev, right_dev, n_chains, class_dev, n_labels, capacities, out_left_dev, out_right_dev,
+                     out_xy_dev, out_row_index_dev, chain_origin_dev=None, chain_out_dev=None, classes_dev=None, flags=0):
+        """rj_map_dissolve of a labelled chain map in device memory: the faces merged by class (class_dev: an int32 table of
+        n_labels entries, or None for the labels themselves), the chains re-joined, into out_xy_dev / out_row_index_dev /
+        out_left_dev / out_right_dev and (or None) chain_origin_dev, chain_out_dev [n_chains] and the rj_diss_class records
+        classes_dev.  capacities = (classes, chains, points); (0, 0, 0) with arrays None is the sizing call.  Returns the counts
+        as a dict (DISSOLVE_COUNTS); DissolveOverflow (with the true counts) past a capacity, DissolveUnmapped (with
+        n_unmapped) for nonzero labels outside the table."""
+        kc, cc, pc = (int(v) for v in capacities)
+        counts = (_u64 * len(DISSOLVE_COUNTS))()
+        rc = self.L.rj_map_dissolve(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev), int(n_chains), _ptr(class_dev),
+                                    int(n_labels), int(flags), kc, cc, pc, _ptr(classes_dev), _ptr(out_left_dev), _ptr(out_right_dev), _ptr(out_xy_dev),
+                                    _ptr(out_row_index_dev), _ptr(chain_origin_dev), _ptr(chain_out_dev), counts)
+        named = dict(zip(DISSOLVE_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise DissolveOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        if rc == RJ_E_INVALID and named["n_unmapped"]:
+            raise DissolveUnmapped(self.L.rj_last_error_string(self.h).decode(), named["n_unmapped"])
         self._check(rc)
         return named
 

@@ -15,6 +15,7 @@
 
 #include "../../include/rayjoin_amd.h"
 #include "rj_crossings.h"
+#include "rj_dissolve.h"
 #include "rj_eliminate.h"
 #include "rj_faces.h"
 #include "rj_node.h"
@@ -290,6 +291,8 @@ struct rj_handle_s {
   FacesReport faces_report;  // what the last rj_map_faces chose and took (reports only)
   int debug_elim_point_blocks = 0;  // rj_map_eliminate: the grid of the chain sums and of the point scatter (0: by size; tests and sweeps: the same result)
   EliminateReport eliminate_report;  // what the last rj_map_eliminate took (reports only)
+  int debug_dissolve_point_blocks = 0;  // rj_map_dissolve: the grid of the point scatter (0: by size; tests and sweeps: the same result)
+  DissolveReport dissolve_report;  // what the last rj_map_dissolve took (reports only)
   uint32_t stitch_stats[4] = {0, 0, 0, 0};  // the last run cutting: ranking rounds, incidences on closed loops, rounds of the second ranking, closed chains
   char* strip_scratch = nullptr;  // grow-only temporaries of the column index's build
   size_t strip_scratch_bytes = 0;
@@ -644,6 +647,7 @@ const Option kOptions[] = {
     {"simplify_all_points", true, &rj_handle_s::debug_simplify_all_points, 0, 1},  // rj_map_simplify: every round over all points (0: the work list)
     {"faces_shift", true, &rj_handle_s::debug_faces_shift, 15, 47, "faces_shift: 0 (choose) or 15..47", nullptr, nullptr, 1, {0}},  // rj_map_faces: the grid's shift
     {"elim_point_blocks", true, &rj_handle_s::debug_elim_point_blocks, 0, 1 << 20},  // rj_map_eliminate: blocks of its two passes over the points (0: by size)
+    {"dissolve_point_blocks", true, &rj_handle_s::debug_dissolve_point_blocks, 0, 1 << 20},  // rj_map_dissolve: blocks of its point scatter (0: by size)
 };
 
 const Option* find_option(const char* name, bool debug) {
@@ -735,6 +739,7 @@ const Report kReports[] = {
     {"faces_last_cells", 0, RJ_READ(h->faces_report.cells)},
     {"faces_last_us", 6, RJ_READ(h->faces_report.ms[k] < 0 ? -1 : (int64_t) (h->faces_report.ms[k] * 1000.0f))},  // rings, tops and kinds, grid, rays, parents and faces, all
     {"elim_last_us", 6, RJ_READ(h->eliminate_report.ms[k] < 0 ? -1 : (int64_t) (h->eliminate_report.ms[k] * 1000.0f))},  // the last rj_map_eliminate: check and chain sums, faces, pairs and choice, pointers, labels and scatter, all
+    {"dissolve_last_us", 6, RJ_READ(h->dissolve_report.ms[k] < 0 ? -1 : (int64_t) (h->dissolve_report.ms[k] * 1000.0f))},  // the last rj_map_dissolve: check, classes and keep; ends and next; walks; class records; totals and scatter; all
     {"comm_ranks", 0, read_comm_ranks},
     {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
     {"pip_share_blocks", 0, RJ_READ(h->last_pip_share ? h->last_pip_share : h->pip_share_blocks())},
@@ -3083,6 +3088,47 @@ int rj_map_eliminate(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint
   if (!m.emit)
     return fail(h, RJ_E_OVERFLOW, "rj_map_eliminate: %llu faces, %llu chains, %llu points; capacities %llu, %llu, %llu", (unsigned long long) counts->n_faces,
                 (unsigned long long) counts->n_chains, (unsigned long long) counts->n_points, (unsigned long long) face_capacity,
+                (unsigned long long) chain_capacity, (unsigned long long) point_capacity);
+  return RJ_OK;
+}
+
+int rj_map_dissolve(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, const int32_t* left_dev, const int32_t* right_dev,
+                    uint64_t nc, const int32_t* class_dev, uint64_t n_labels, uint32_t flags, uint64_t class_capacity, uint64_t chain_capacity,
+                    uint64_t point_capacity, rj_diss_class* classes_dev, int32_t* out_left_dev, int32_t* out_right_dev, int64_t* out_xy_dev,
+                    uint32_t* out_row_index_dev, uint32_t* chain_origin_dev, uint32_t* chain_out_dev, rj_dissolve_counts* counts) {
+  static_assert(sizeof(rj_diss_class) == 24 && sizeof(dissolve::ClassRec) == 24 && sizeof(rj_dissolve_counts) == sizeof(dissolve::Counts), "layouts");
+  static_assert(RJ_DISS_KEEP_EQUAL == dissolve::kKeepEqual, "flags");
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_map_dissolve: counts is null");
+  memset(counts, 0, sizeof(*counts));
+  h->dissolve_report = DissolveReport{};
+  if (flags & ~(uint32_t) RJ_DISS_KEEP_EQUAL) return fail(h, RJ_E_INVALID, "rj_map_dissolve: unknown flags 0x%x", flags);
+  if (!classes_dev) class_capacity = 0;
+  if ((np && !xy_dev) || (nc && (!row_index_dev || !left_dev || !right_dev))) return fail(h, RJ_E_INVALID, "rj_map_dissolve: null input array");
+  if (class_dev && n_labels == 0) return fail(h, RJ_E_INVALID, "rj_map_dissolve: a class table without labels");
+  if (nc >= (1ull << 31) || np >= (1ull << 32) || nc > np || 2 * (np - nc) >= (1ull << 32))
+    return fail(h, RJ_E_INVALID, "rj_map_dissolve: nc < 2^31, nc <= np < 2^32 and 2 (np - nc) < 2^32");
+  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_dissolve: points without chains");
+  if ((chain_capacity && (!out_left_dev || !out_right_dev || !out_row_index_dev)) || (point_capacity && !out_xy_dev))
+    return fail(h, RJ_E_INVALID, "rj_map_dissolve: null output");
+  if (int r = set_device(h)) return r;
+  if (nc == 0) return write_empty_row(h, out_row_index_dev);  // no chains
+  const dissolve::Out out{reinterpret_cast<dissolve::ClassRec*>(classes_dev), out_left_dev, out_right_dev, out_xy_dev, out_row_index_dev, chain_origin_dev,
+                          chain_out_dev, class_capacity, chain_capacity, point_capacity};
+  dissolve::Meta m;
+  RJ_HIP(h, map_dissolve_device(h->stream, xy_dev, np, row_index_dev, left_dev, right_dev, nc, class_dev, n_labels, flags, out,
+                                h->debug_dissolve_point_blocks, &m, &h->dissolve_report));
+  if (m.bad) return fail_map_check(h, "rj_map_dissolve", m.bad);
+  if (m.counts.n_unmapped) {
+    counts->n_unmapped = m.counts.n_unmapped;
+    return fail(h, RJ_E_INVALID, "rj_map_dissolve: %llu chain sides carry a nonzero label outside the class table of %llu labels",
+                (unsigned long long) m.counts.n_unmapped, (unsigned long long) n_labels);
+  }
+  if (m.unfinished) return fail(h, RJ_E_INTERNAL, "rj_map_dissolve: a walk was not ranked within %d doubling steps", dissolve::kMaxRounds);
+  memcpy(counts, &m.counts, sizeof(*counts));
+  if (!m.emit)
+    return fail(h, RJ_E_OVERFLOW, "rj_map_dissolve: %llu classes, %llu chains, %llu points; capacities %llu, %llu, %llu", (unsigned long long) counts->n_classes,
+                (unsigned long long) counts->n_chains, (unsigned long long) counts->n_points, (unsigned long long) class_capacity,
                 (unsigned long long) chain_capacity, (unsigned long long) point_capacity);
   return RJ_OK;
 }

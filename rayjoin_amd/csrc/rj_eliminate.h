@@ -31,7 +31,7 @@
 //         best, flags, its own area2.  Under kDrop a chain is dropped exactly when its input labels differ and its output
 //         labels are equal (bridges and dangles that came with left == right stay); the kept chains are written in input
 //         order with their points, origin[k] = the input chain of output chain k.  Chains are NOT re-joined at vertices
-//         that drop to degree 2: that is rj_map_rings followed by rj_rings_map.
+//         that drop to degree 2: that is rj_map_dissolve with RJ_DISS_KEEP_EQUAL (rj_dissolve.h).
 //
 // Every step is one function per element that rj_eliminate.hip runs as a kernel and tests/hosttwin/eliminate_twin.cc runs
 // as a plain loop (a test-only twin, never a fallback):

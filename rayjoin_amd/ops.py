@@ -46,6 +46,10 @@
       -- the label side (rj_map_faces): the faces of a chain map computed from its geometry alone, a face number on each
          side of every chain, the face records with exact areas; check=True tells whether a map's own labels describe the
          partition its geometry has (counts["n_conflicts"])
+  map_dissolve(handle, ...) / DeviceOutputMap.Dissolve(handle, classes) / DeviceChainMap.Dissolve(handle, classes) /
+      .Join(handle) -> DeviceDissolvedMap
+      -- Dissolve (rj_map_dissolve): faces that share a class become one face, the borders between them go, and the
+      chains that meet two by two with the same classes become one chain; Join keeps every chain and only re-joins
   map_eliminate(handle, ...) / map_eliminate_rounds(handle, ...) / DeviceOutputMap.Eliminate(handle, tol) /
       DeviceChainMap.Eliminate(handle, tol) -> DeviceEliminatedMap
       -- what removes slivers (rj_map_eliminate): every face of at most tol joins the neighbour it shares the longest
@@ -429,6 +433,16 @@ class DeviceOutputMap:
         into the neighbour with the longest shared border, the chains between merged faces dropped.  rounds > 1: repeated
         (map_eliminate_rounds) until a round eliminates nothing or `rounds` have run; .rounds holds the counts of each"""
         return _eliminated(handle, self, tol, rounds, faces)
+
+    def Dissolve(self, handle, classes=None, **kw):
+        """map_dissolve of this map, on the device, as a DeviceDissolvedMap of its own: the faces merged by class (classes: an
+        int32 table indexed by label, on the device or as a numpy array; None: the labels themselves), the borders between
+        faces of one class dropped, the chains that meet two by two with equal classes joined"""
+        return map_dissolve(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, classes=classes, **kw)
+
+    def Join(self, handle, **kw):
+        """Dissolve with identity classes and keep_equal: no chain goes, the chains that meet two by two are joined"""
+        return self.Dissolve(handle, None, keep_equal=True, **kw)
 
     def free(self):
         for b in (self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin):
@@ -890,6 +904,16 @@ class DeviceChainMap:
         (map_eliminate_rounds) until a round eliminates nothing or `rounds` have run; .rounds holds the counts of each"""
         return _eliminated(handle, self, tol, rounds, faces)
 
+    def Dissolve(self, handle, classes=None, **kw):
+        """map_dissolve of this map, on the device, as a DeviceDissolvedMap of its own: the faces merged by class (classes: an
+        int32 table indexed by label, on the device or as a numpy array; None: the labels themselves), the borders between
+        faces of one class dropped, the chains that meet two by two with equal classes joined"""
+        return map_dissolve(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, classes=classes, **kw)
+
+    def Join(self, handle, **kw):
+        """Dissolve with identity classes and keep_equal: no chain goes, the chains that meet two by two are joined"""
+        return self.Dissolve(handle, None, keep_equal=True, **kw)
+
     def Faces(self, handle, check=False):
         """map_faces of this map, on the device: its faces computed from the geometry alone, as a DeviceFacedMap of its own.
         check: this map's own left / right go in as the labels to check -- counts["n_conflicts"] == 0 tells that they and
@@ -1053,6 +1077,85 @@ def _eliminated(handle, m, tol, rounds, faces):
     if int(rounds) <= 1:
         return map_eliminate(handle, *args, drop=True, faces=faces)
     return map_eliminate_rounds(handle, *args, max_rounds=rounds, faces=faces)
+
+
+def map_dissolve(handle, xy, n_points, row_index, left, right, n_chains, classes=None, keep_equal=False, records=False, origin=False):
+    """A labelled chain map in device memory with its faces merged by class and its chains re-joined (rj_map_dissolve) as a
+    DeviceDissolvedMap.  classes: an int32 table indexed by label (class of label f = classes[f], label 0 stays 0, a nonzero
+    class may be 0: the face joins the outside), a DeviceBuffer (all of it), (device array, n_labels) or a numpy array;
+    None: the labels themselves.  A chain whose two classes are equal is dropped unless keep_equal (RJ_DISS_KEEP_EQUAL:
+    join only, nothing dissolves); the kept chains that meet two by two with the same classes become one chain, loops
+    close.  left / right of the result are classes.  records: also the class records (.classes, DISS_CLASS_DTYPE rows
+    ascending by unsigned label: label, n_sides, area2).  origin: also .origin (the leader's input chain of every output
+    chain) and .chain_out ((k << 1) | reversed per input chain, 0xFFFFFFFF for a chain that went).  A sizing call finds
+    the capacities.  counts: DISSOLVE_COUNTS with n_edges."""
+    n_points, n_chains = int(n_points), int(n_chains)
+    flags = _capi.RJ_DISS_KEEP_EQUAL if keep_equal else 0
+    table, n_labels, own_table = None, 0, None
+    if isinstance(classes, tuple):
+        table, n_labels = classes[0], int(classes[1])
+    elif isinstance(classes, _capi.DeviceBuffer):
+        table, n_labels = classes, classes.nbytes // 4
+    elif classes is not None:
+        host = np.ascontiguousarray(classes, np.int32)
+        if host.ndim != 1 or len(host) == 0:
+            raise ValueError("classes must be a one-dimensional table with an entry for label 0")
+        table = own_table = handle.alloc(4 * len(host)).from_host(host)
+        n_labels = len(host)
+    bufs, recs, org, cout, done = [], None, None, None, False
+    try:
+        args = (xy, n_points, row_index, left, right, n_chains, table, n_labels)
+        try:
+            c = handle.map_dissolve(*args, (0, 0, 0), None, None, None, None, flags=flags)
+        except _capi.DissolveOverflow as e:
+            c = e.counts
+        kc, cc, pc = c["n_classes"] if records else 0, c["n_chains"], c["n_points"]
+        bufs.append(handle.alloc(16 * max(1, pc)))
+        bufs.append(handle.alloc(4 * (cc + 1)))
+        bufs.append(handle.alloc(4 * max(1, cc)))
+        bufs.append(handle.alloc(4 * max(1, cc)))
+        if origin:
+            org, cout = handle.alloc(4 * max(1, cc)), handle.alloc(4 * max(1, n_chains))
+        if records:
+            recs = handle.alloc(_capi.DISS_CLASS_DTYPE.itemsize * max(1, kc))
+        counts = handle.map_dissolve(*args, (kc, cc, pc), bufs[2], bufs[3], bufs[0], bufs[1], org, cout, recs, flags=flags)
+        done = True
+    finally:
+        if own_table is not None:
+            own_table.free()
+        if not done:
+            for b in bufs + [recs, org, cout]:
+                if b is not None:
+                    b.free()
+    return DeviceDissolvedMap(*bufs, dict(counts, n_edges=counts["n_points"] - counts["n_chains"]), recs, org, cout, n_chains)
+
+
+class DeviceDissolvedMap(DeviceChainMap):
+    """A chain map in device memory whose left / right are the classes that rj_map_dissolve gave, with classes
+    (DISS_CLASS_DTYPE rows as a DeviceBuffer, or None), origin (uint32 per chain: its leader's input chain, or None),
+    chain_out (uint32 per INPUT chain, or None) and the counts n_kept, n_dropped, n_skipped, n_chains, n_points, n_closed,
+    n_classes, n_unmapped, n_edges."""
+
+    def __init__(self, xy, row_index, left, right, counts, classes, origin, chain_out, n_input_chains):
+        super().__init__(xy, row_index, left, right, counts)
+        self.classes, self.origin, self.chain_out = classes, origin, chain_out
+        self.n_classes, self.n_input_chains = int(counts["n_classes"]), int(n_input_chains)
+
+    def classes_to_host(self):
+        """-> the class records (DISS_CLASS_DTYPE), ascending by unsigned label"""
+        return self.classes.to_host(_capi.DISS_CLASS_DTYPE, self.n_classes)
+
+    def origin_to_host(self):
+        return self.origin.to_host(np.uint32, self.n_chains)
+
+    def chain_out_to_host(self):
+        return self.chain_out.to_host(np.uint32, self.n_input_chains)
+
+    def free(self):
+        super().free()
+        for b in (self.classes, self.origin, self.chain_out):
+            if b is not None:
+                b.free()
 
 
 class DevicePolygons:
