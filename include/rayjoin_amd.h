@@ -885,6 +885,59 @@ int rj_map_dissolve(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint3
                     uint32_t* chain_origin_dev /* may be NULL */, uint32_t* chain_out_dev /* may be NULL */,
                     rj_dissolve_counts* counts);
 
+/* ---- neighbours: which faces touch which, along how much border and at how many nodes ---- */
+#define RJ_NB_VERTEX 1u   /* also the nodes: n_nodes of every pair, and the pairs that meet only at a vertex */
+typedef struct { int32_t label; uint32_t n_sides, n_edge_nbrs, n_vertex_nbrs; uint64_t area2_lo; int64_t area2_hi;
+                 uint64_t perimeter_lo, perimeter_hi, outer_lo, outer_hi; } rj_nb_face; /* 64 bytes */
+typedef struct { int32_t label; uint32_t face, n_chains, n_nodes; uint64_t w_lo, w_hi; } rj_nb_entry; /* 32 bytes */
+typedef struct { uint64_t n_faces, n_entries, n_edge_pairs, n_vertex_pairs, n_nodes, n_node_pairs_raw,
+                 max_labels_at_node; } rj_neighbours_counts;
+
+/* extends: the face adjacency table of a labelled chain map in device memory -- what GIS users know as Polygon
+ * Neighbors, and the input of rook and queen contiguity weights, of region growing and of any merge rule other than
+ * rj_map_eliminate's longest border.  rj_map_eliminate computes the shared borders for its one rule and throws them
+ * away; this call returns them.  (The reference has no counterpart.)
+ * Input: xy_dev[2 np], row_index_dev[nc + 1], left_dev[nc], right_dev[nc] with the contract, the checks and the size
+ * limits of rj_map_eliminate (a chain may have a single point); labels are any int32.  Under RJ_NB_VERTEX also nc < 2^30.
+ * xy_dev is 16-byte aligned (device allocations are): the points are read with 16-byte loads.
+ * The definition, in full in rayjoin_amd/csrc/rj_neighbours.h:
+ *   faces, their numbering by ascending (uint32_t) label, S(c), L(c) and area2(f) are rj_map_eliminate's; n_sides(f) = the
+ *   chain sides that carry f.  Faces f != g, both not 0, are edge neighbours when some chain has {left, right} = {f, g};
+ *   w(f, g) = the sum of L(c) over those chains, n_chains(f, g) their number; a pair with w = 0 is still a pair; chains
+ *   with left == right add nothing to any length.  perimeter(f) = the sum of L(c) over the chains with left != right and
+ *   one side f (the other may be 0), outer(f) the part whose other side is 0: perimeter = outer + the sum of w.
+ *   Under RJ_NB_VERTEX a node is a chain end: a distinct point that is the first or the last point of some chain; points
+ *   inside a chain are not looked at, so the call is meant for noded maps whose shared vertices are chain ends
+ *   (rj_rings_map, rj_map_node, rj_map_snap, rj_map_dissolve); a pseudo-node of degree 2 counts, so rj_map_dissolve with
+ *   RJ_DISS_KEEP_EQUAL first for canonical node counts.  F(P) = the nonzero labels on either side of any chain that ends
+ *   at P; f != g meet at P when both are in F(P); n_nodes(f, g) = the distinct nodes where they meet; a pair with
+ *   n_nodes > 0 and n_chains = 0 is a vertex-only neighbour.  Without the flag no node is looked at: every n_nodes and
+ *   n_vertex_nbrs and the counts n_vertex_pairs, n_nodes, n_node_pairs_raw and max_labels_at_node are 0.
+ * Output, caller-owned device memory, CSR over the faces: faces_dev[face_capacity] (may be NULL: no records), record k of
+ * the k-th face -- label, n_sides, n_edge_nbrs, n_vertex_nbrs (vertex-only neighbours), area2 (a two's-complement
+ * int128), perimeter and outer (unsigned 128-bit); offsets_dev[face_capacity + 1]: entry k is where the entries of face k
+ * start, entry n_faces is n_entries; entries_dev[entry_capacity]: the neighbour's label and face number, n_chains,
+ * n_nodes, w -- ascending by the neighbour's (uint32_t) label within a face, every pair in both directions with equal
+ * values.  Counts: the pair counts are unordered; n_node_pairs_raw = the sum over nodes of m (m - 1), m = |F(P)|, which
+ * is what the call has to sort; max_labels_at_node the largest m.
+ * All capacities 0 (arrays may be NULL) is the sizing call.  RJ_E_OVERFLOW when n_faces > face_capacity or n_entries >
+ * entry_capacity: *counts holds the true counts and nothing is written.  nc == 0 is valid and writes offsets_dev[0] = 0
+ * where that pointer is given.  RJ_E_INVALID, with nothing written: the map checks, an unknown flag bit, null input
+ * arrays or a null counts, a capacity without its array, and n_node_pairs_raw >= 2^32 (*counts holds that count; it
+ * saturates at 2^64 - 1; below that limit memory is the practical one, 56 bytes of scratch per raw node pair, and a call
+ * that does not get it fails with RJ_E_HIP).  Integers only, exact, fully determined.  Runs on the handle's stream;
+ * rook only with one host sync, at the end; with RJ_NB_VERTEX one more, behind the node stage, to read n_node_pairs_raw and size the scratch of
+ * the node pairs.  Scratch (rj_neighbours.h has the bytes per chain and per raw node pair) is allocated per call and
+ * freed; no map, index or option of the handle changes.  For tests and sweeps, through rj_set_debug_option:
+ * "neighbours_point_blocks" (0: by size) is the grid of the pass over the points; any grid gives the same result.
+ * rj_get_option: "neighbours_last_us0" .. "neighbours_last_us5" (HIP-event microseconds of the stages: check and chain
+ * sums, faces, edge pairs, nodes, the table, all; -1: no call yet, or the last call was refused). */
+int rj_map_neighbours(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev,
+                      const int32_t* left_dev, const int32_t* right_dev, uint64_t nc, uint32_t flags,
+                      uint64_t face_capacity, uint64_t entry_capacity,
+                      rj_nb_face* faces_dev /* may be NULL */, uint64_t* offsets_dev, rj_nb_entry* entries_dev,
+                      rj_neighbours_counts* counts);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

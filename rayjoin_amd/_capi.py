@@ -64,6 +64,14 @@ RJ_DISS_KEEP_EQUAL = 1  # rj_map_dissolve flags
 # rj_diss_class: one class of rj_map_dissolve -- its label, the kept chain sides that carry it, twice its area
 DISS_CLASS_DTYPE = np.dtype([("label", "<i4"), ("n_sides", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
 DISSOLVE_COUNTS = ("n_kept", "n_dropped", "n_skipped", "n_chains", "n_points", "n_closed", "n_classes", "n_unmapped")
+RJ_NB_VERTEX = 1  # rj_map_neighbours flags
+# rj_nb_face: one face of rj_map_neighbours -- its label, the chain sides that carry it, its edge and vertex-only neighbours, twice
+# its area, its perimeter and the part of it that borders label 0 (unsigned 128-bit integer lengths)
+NB_FACE_DTYPE = np.dtype([("label", "<i4"), ("n_sides", "<u4"), ("n_edge_nbrs", "<u4"), ("n_vertex_nbrs", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8"),
+                          ("perimeter_lo", "<u8"), ("perimeter_hi", "<u8"), ("outer_lo", "<u8"), ("outer_hi", "<u8")])
+# rj_nb_entry: one neighbour of a face -- its label and face number, the chains and nodes the two share, the length of their border
+NB_ENTRY_DTYPE = np.dtype([("label", "<i4"), ("face", "<u4"), ("n_chains", "<u4"), ("n_nodes", "<u4"), ("w_lo", "<u8"), ("w_hi", "<u8")])
+NEIGHBOURS_COUNTS = ("n_faces", "n_entries", "n_edge_pairs", "n_vertex_pairs", "n_nodes", "n_node_pairs_raw", "max_labels_at_node")
 ELIMINATE_COUNTS = ("n_faces", "n_slivers", "n_eliminated", "n_islands", "n_mutual", "n_negative", "n_chains", "n_points", "n_dropped")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
@@ -123,6 +131,7 @@ SYMBOLS = {
     "rj_map_faces": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, C.c_uint32, _u64, _vp, _vp, _vp, _vp]),
     "rj_map_eliminate": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _u64, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rj_map_dissolve": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rj_map_neighbours": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -246,6 +255,19 @@ class EliminateOverflow(CountsOverflow):
 
 class DissolveOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_map_dissolve: counts = a dict of DISSOLVE_COUNTS, the true counts; nothing is written"""
+
+
+class NeighboursOverflow(CountsOverflow):
+    """RJ_E_OVERFLOW of rj_map_neighbours: counts = a dict of NEIGHBOURS_COUNTS, the true counts; nothing is written"""
+
+
+class NeighboursNodePairs(RayJoinError):
+    """RJ_E_INVALID of rj_map_neighbours under RJ_NB_VERTEX for n_node_pairs_raw >= 2^32: the count (it saturates at
+    2^64 - 1); nothing is written"""
+
+    def __init__(self, msg, n_node_pairs_raw):
+        super().__init__(RJ_E_INVALID, msg)
+        self.n_node_pairs_raw = n_node_pairs_raw
 
 
 class DissolveUnmapped(RayJoinError):
@@ -750,6 +772,25 @@ class Handle:
             raise DissolveOverflow(self.L.rj_last_error_string(self.h).decode(), named)
         if rc == RJ_E_INVALID and named["n_unmapped"]:
             raise DissolveUnmapped(self.L.rj_last_error_string(self.h).decode(), named["n_unmapped"])
+        self._check(rc)
+        return named
+
+    def map_neighbours(self, xy_dev, n_points, row_index_dev, left_dev, right_dev, n_chains, capacities, faces_dev=None, offsets_dev=None, entries_dev=None,
+                       flags=0):
+        """rj_map_neighbours of a labelled chain map in device memory: the face adjacency table in CSR form -- the rj_nb_face
+        records into faces_dev (or None), uint64 offsets_dev [faces + 1] and the rj_nb_entry rows entries_dev.  capacities =
+        (faces, entries); (0, 0) with arrays None is the sizing call.  flags: RJ_NB_VERTEX for the nodes and the vertex-only
+        neighbours.  Returns the counts as a dict (NEIGHBOURS_COUNTS); NeighboursOverflow (with the true counts) past a capacity,
+        NeighboursNodePairs (with the count) where the nodes give 2^32 directed pairs or more."""
+        fc, ec = (int(v) for v in capacities)
+        counts = (_u64 * len(NEIGHBOURS_COUNTS))()
+        rc = self.L.rj_map_neighbours(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev), int(n_chains), int(flags), fc,
+                                      ec, _ptr(faces_dev), _ptr(offsets_dev), _ptr(entries_dev), counts)
+        named = dict(zip(NEIGHBOURS_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise NeighboursOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        if rc == RJ_E_INVALID and named["n_node_pairs_raw"]:
+            raise NeighboursNodePairs(self.L.rj_last_error_string(self.h).decode(), named["n_node_pairs_raw"])
         self._check(rc)
         return named
 

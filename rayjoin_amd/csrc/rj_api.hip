@@ -20,6 +20,7 @@
 #include "rj_faces.h"
 #include "rj_node.h"
 #include "rj_kernels.h"
+#include "rj_neighbours.h"
 #include "rj_overlay_dev.h"
 #include "rj_overlay_ops.h"
 #include "rj_pipeline.h"
@@ -293,6 +294,8 @@ struct rj_handle_s {
   EliminateReport eliminate_report;  // what the last rj_map_eliminate took (reports only)
   int debug_dissolve_point_blocks = 0;  // rj_map_dissolve: the grid of the point scatter (0: by size; tests and sweeps: the same result)
   DissolveReport dissolve_report;  // what the last rj_map_dissolve took (reports only)
+  int debug_neighbours_point_blocks = 0;  // rj_map_neighbours: the grid of the pass over the points (0: by size; tests and sweeps: the same result)
+  NeighboursReport neighbours_report;  // what the last rj_map_neighbours took (reports only)
   uint32_t stitch_stats[4] = {0, 0, 0, 0};  // the last run cutting: ranking rounds, incidences on closed loops, rounds of the second ranking, closed chains
   char* strip_scratch = nullptr;  // grow-only temporaries of the column index's build
   size_t strip_scratch_bytes = 0;
@@ -648,6 +651,7 @@ const Option kOptions[] = {
     {"faces_shift", true, &rj_handle_s::debug_faces_shift, 15, 47, "faces_shift: 0 (choose) or 15..47", nullptr, nullptr, 1, {0}},  // rj_map_faces: the grid's shift
     {"elim_point_blocks", true, &rj_handle_s::debug_elim_point_blocks, 0, 1 << 20},  // rj_map_eliminate: blocks of its two passes over the points (0: by size)
     {"dissolve_point_blocks", true, &rj_handle_s::debug_dissolve_point_blocks, 0, 1 << 20},  // rj_map_dissolve: blocks of its point scatter (0: by size)
+    {"neighbours_point_blocks", true, &rj_handle_s::debug_neighbours_point_blocks, 0, 1 << 20},  // rj_map_neighbours: blocks of its pass over the points (0: by size)
 };
 
 const Option* find_option(const char* name, bool debug) {
@@ -740,6 +744,7 @@ const Report kReports[] = {
     {"faces_last_us", 6, RJ_READ(h->faces_report.ms[k] < 0 ? -1 : (int64_t) (h->faces_report.ms[k] * 1000.0f))},  // rings, tops and kinds, grid, rays, parents and faces, all
     {"elim_last_us", 6, RJ_READ(h->eliminate_report.ms[k] < 0 ? -1 : (int64_t) (h->eliminate_report.ms[k] * 1000.0f))},  // the last rj_map_eliminate: check and chain sums, faces, pairs and choice, pointers, labels and scatter, all
     {"dissolve_last_us", 6, RJ_READ(h->dissolve_report.ms[k] < 0 ? -1 : (int64_t) (h->dissolve_report.ms[k] * 1000.0f))},  // the last rj_map_dissolve: check, classes and keep; ends and next; walks; class records; totals and scatter; all
+    {"neighbours_last_us", 6, RJ_READ(h->neighbours_report.ms[k] < 0 ? -1 : (int64_t) (h->neighbours_report.ms[k] * 1000.0f))},  // the last rj_map_neighbours: check and chain sums, faces, edge pairs, nodes, the table, all
     {"comm_ranks", 0, read_comm_ranks},
     {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
     {"pip_share_blocks", 0, RJ_READ(h->last_pip_share ? h->last_pip_share : h->pip_share_blocks())},
@@ -3130,6 +3135,49 @@ int rj_map_dissolve(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint3
     return fail(h, RJ_E_OVERFLOW, "rj_map_dissolve: %llu classes, %llu chains, %llu points; capacities %llu, %llu, %llu", (unsigned long long) counts->n_classes,
                 (unsigned long long) counts->n_chains, (unsigned long long) counts->n_points, (unsigned long long) class_capacity,
                 (unsigned long long) chain_capacity, (unsigned long long) point_capacity);
+  return RJ_OK;
+}
+
+int rj_map_neighbours(rj_handle h, const int64_t* xy_dev, uint64_t np, const uint32_t* row_index_dev, const int32_t* left_dev, const int32_t* right_dev,
+                      uint64_t nc, uint32_t flags, uint64_t face_capacity, uint64_t entry_capacity, rj_nb_face* faces_dev, uint64_t* offsets_dev,
+                      rj_nb_entry* entries_dev, rj_neighbours_counts* counts) {
+  static_assert(sizeof(rj_nb_face) == 64 && sizeof(neighbours::Face) == 64 && sizeof(rj_nb_entry) == 32 && sizeof(neighbours::Entry) == 32 &&
+                    sizeof(rj_neighbours_counts) == sizeof(neighbours::Counts),
+                "layouts");
+  static_assert(RJ_NB_VERTEX == neighbours::kVertex, "flags");
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_map_neighbours: counts is null");
+  memset(counts, 0, sizeof(*counts));
+  h->neighbours_report = NeighboursReport{};
+  if (flags & ~(uint32_t) RJ_NB_VERTEX) return fail(h, RJ_E_INVALID, "rj_map_neighbours: unknown flags 0x%x", flags);
+  if ((np && !xy_dev) || (nc && (!row_index_dev || !left_dev || !right_dev))) return fail(h, RJ_E_INVALID, "rj_map_neighbours: null input array");
+  if (nc >= (1ull << 31) || np >= (1ull << 32) || nc > np || 2 * (np - nc) >= (1ull << 32))
+    return fail(h, RJ_E_INVALID, "rj_map_neighbours: nc < 2^31, nc <= np < 2^32 and 2 (np - nc) < 2^32");
+  if ((flags & RJ_NB_VERTEX) && nc >= (1ull << 30)) return fail(h, RJ_E_INVALID, "rj_map_neighbours: nc < 2^30 under RJ_NB_VERTEX");
+  if (nc == 0 && np != 0) return fail(h, RJ_E_INVALID, "rj_map_neighbours: points without chains");
+  if (((face_capacity || entry_capacity) && !offsets_dev) || (entry_capacity && !entries_dev)) return fail(h, RJ_E_INVALID, "rj_map_neighbours: null output");
+  if (int r = set_device(h)) return r;
+  if (nc == 0) {  // no chains: no faces, the offsets' one entry
+    if (offsets_dev) {
+      RJ_HIP(h, hipMemsetAsync(offsets_dev, 0, 8, h->stream));
+      RJ_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return RJ_OK;
+  }
+  neighbours::Meta m;
+  RJ_HIP(h, map_neighbours_device(h->stream, xy_dev, np, row_index_dev, left_dev, right_dev, nc, flags, face_capacity, entry_capacity,
+                                  reinterpret_cast<neighbours::Face*>(faces_dev), offsets_dev, reinterpret_cast<neighbours::Entry*>(entries_dev),
+                                  h->debug_neighbours_point_blocks, &m, &h->neighbours_report));
+  if (m.bad) return fail_map_check(h, "rj_map_neighbours", m.bad);
+  if (m.counts.n_node_pairs_raw >= neighbours::kMaxRawPairs) {
+    counts->n_node_pairs_raw = m.counts.n_node_pairs_raw;
+    return fail(h, RJ_E_INVALID, "rj_map_neighbours: %llu directed pairs of faces at the nodes: n_node_pairs_raw < 2^32",
+                (unsigned long long) m.counts.n_node_pairs_raw);
+  }
+  memcpy(counts, &m.counts, sizeof(*counts));
+  if (!m.emit)
+    return fail(h, RJ_E_OVERFLOW, "rj_map_neighbours: %llu faces, %llu entries; capacities %llu, %llu", (unsigned long long) counts->n_faces,
+                (unsigned long long) counts->n_entries, (unsigned long long) face_capacity, (unsigned long long) entry_capacity);
   return RJ_OK;
 }
 

@@ -1,6 +1,6 @@
 // rj_pipeline.h -- what the multi-stage device pipelines share (rj_stitch.hip, rj_strip.hip, rj_overlay.hip,
 // rj_overlay_map.hip, rj_rings.hip, rj_grid.hip, rj_polygons.hip, rj_ringmap.hip, rj_crossings.hip, rj_simplify.hip,
-// rj_faces.hip, rj_eliminate.hip, rj_dissolve.hip, rj_node.hip and rj_snap.hip through rj_cut_pipeline.h, and their callers in
+// rj_faces.hip, rj_eliminate.hip, rj_dissolve.hip, rj_neighbours.hip, rj_node.hip and rj_snap.hip through rj_cut_pipeline.h, and their callers in
 // rj_api.hip): the launch width, the grid-stride loop, the carving of one scratch block, the grow-only block itself,
 // the block-wide sum and the counter update behind it, the largest of rocPRIM's temporary sizes, and the stage times
 // of a call with the events that measure them.  No state, no .hip file of its own.  HIP only.

@@ -54,6 +54,11 @@
       DeviceChainMap.Eliminate(handle, tol) -> DeviceEliminatedMap
       -- what removes slivers (rj_map_eliminate): every face of at most tol joins the neighbour it shares the longest
          border with, exactly, on the device; the chains between merged faces are dropped, rounds repeat the call
+  map_neighbours(handle, ...) / DeviceOutputMap.Neighbours(handle, vertex=) / DeviceChainMap.Neighbours(handle, vertex=)
+      -> DeviceNeighbours
+      -- the face adjacency table (rj_map_neighbours): which faces touch which, the integer length of the shared border,
+         the chains that make it, with vertex=True the nodes where two faces meet and the faces that meet only at a
+         vertex; CSR over the faces, to_csr() for a sparse matrix
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -443,6 +448,11 @@ class DeviceOutputMap:
     def Join(self, handle, **kw):
         """Dissolve with identity classes and keep_equal: no chain goes, the chains that meet two by two are joined"""
         return self.Dissolve(handle, None, keep_equal=True, **kw)
+
+    def Neighbours(self, handle, vertex=False, **kw):
+        """map_neighbours of this map, on the device, as a DeviceNeighbours: which faces touch which, along how much border
+        and (vertex=True) at how many nodes, with the faces that meet only at a vertex"""
+        return map_neighbours(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, vertex=vertex, **kw)
 
     def free(self):
         for b in (self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin):
@@ -914,6 +924,11 @@ class DeviceChainMap:
         """Dissolve with identity classes and keep_equal: no chain goes, the chains that meet two by two are joined"""
         return self.Dissolve(handle, None, keep_equal=True, **kw)
 
+    def Neighbours(self, handle, vertex=False, **kw):
+        """map_neighbours of this map, on the device, as a DeviceNeighbours: which faces touch which, along how much border
+        and (vertex=True) at how many nodes, with the faces that meet only at a vertex"""
+        return map_neighbours(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, vertex=vertex, **kw)
+
     def Faces(self, handle, check=False):
         """map_faces of this map, on the device: its faces computed from the geometry alone, as a DeviceFacedMap of its own.
         check: this map's own left / right go in as the labels to check -- counts["n_conflicts"] == 0 tells that they and
@@ -1154,6 +1169,69 @@ class DeviceDissolvedMap(DeviceChainMap):
     def free(self):
         super().free()
         for b in (self.classes, self.origin, self.chain_out):
+            if b is not None:
+                b.free()
+
+
+def map_neighbours(handle, xy, n_points, row_index, left, right, n_chains, vertex=False, records=True):
+    """The face adjacency table of a labelled chain map in device memory (rj_map_neighbours) as a DeviceNeighbours, in CSR
+    form over the faces (the nonzero labels, ascending as unsigned numbers): per face its neighbours with the integer
+    length w of the shared border, the chains n_chains that make it and, with vertex (RJ_NB_VERTEX), the nodes n_nodes
+    where the two meet -- a node is a chain end, so the map should be noded, and joined (Join) where pseudo-nodes matter;
+    neighbours with n_chains == 0 meet only at a vertex.  records: also the face records (.faces, NB_FACE_DTYPE rows:
+    label, n_sides, n_edge_nbrs, n_vertex_nbrs, area2, perimeter, outer).  A sizing call finds the capacities."""
+    n_points, n_chains = int(n_points), int(n_chains)
+    flags = _capi.RJ_NB_VERTEX if vertex else 0
+    args = (xy, n_points, row_index, left, right, n_chains)
+    try:
+        c = handle.map_neighbours(*args, (0, 0), flags=flags)
+    except _capi.NeighboursOverflow as e:
+        c = e.counts
+    fc, ec = c["n_faces"], c["n_entries"]
+    faces, offsets, entries, done = None, None, None, False
+    try:
+        if records:
+            faces = handle.alloc(_capi.NB_FACE_DTYPE.itemsize * max(1, fc))
+        offsets = handle.alloc(8 * (fc + 1))
+        entries = handle.alloc(_capi.NB_ENTRY_DTYPE.itemsize * max(1, ec))
+        counts = handle.map_neighbours(*args, (fc, ec), faces, offsets, entries, flags=flags)
+        done = True
+    finally:
+        if not done:
+            for b in (faces, offsets, entries):
+                if b is not None:
+                    b.free()
+    return DeviceNeighbours(faces, offsets, entries, counts)
+
+
+class DeviceNeighbours:
+    """The face adjacency table of a chain map in device memory (rj_map_neighbours): faces (NB_FACE_DTYPE rows as a
+    DeviceBuffer, or None), offsets (uint64 [n_faces + 1]), entries (NB_ENTRY_DTYPE rows) and the counts n_faces, n_entries,
+    n_edge_pairs, n_vertex_pairs, n_nodes, n_node_pairs_raw, max_labels_at_node."""
+
+    def __init__(self, faces, offsets, entries, counts):
+        self.faces, self.offsets, self.entries = faces, offsets, entries
+        self.counts = dict(counts)
+        self.n_faces, self.n_entries = int(counts["n_faces"]), int(counts["n_entries"])
+
+    def faces_to_host(self):
+        """-> the face records (NB_FACE_DTYPE), ascending by unsigned label; ValueError for a table made with records=False"""
+        if self.faces is None:
+            raise ValueError("this table was made with records=False: it has no face records")
+        return self.faces.to_host(_capi.NB_FACE_DTYPE, self.n_faces)
+
+    def to_host(self):
+        """-> (offsets uint64 [n_faces + 1], entries NB_ENTRY_DTYPE [n_entries])"""
+        return self.offsets.to_host(np.uint64, self.n_faces + 1), self.entries.to_host(_capi.NB_ENTRY_DTYPE, self.n_entries)
+
+    def to_csr(self):
+        """-> (indptr int64 [n_faces + 1], indices int64 [n_entries]: the neighbours' face numbers, the entries themselves):
+        what scipy.sparse.csr_matrix((weights, indices, indptr)) takes, with any column of the entries as the weights"""
+        offsets, entries = self.to_host()
+        return offsets.astype(np.int64), entries["face"].astype(np.int64), entries
+
+    def free(self):
+        for b in (self.faces, self.offsets, self.entries):
             if b is not None:
                 b.free()
 
