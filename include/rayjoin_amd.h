@@ -938,6 +938,59 @@ int rj_map_neighbours(rj_handle h, const int64_t* xy_dev, uint64_t np, const uin
                       rj_nb_face* faces_dev /* may be NULL */, uint64_t* offsets_dev, rj_nb_entry* entries_dev,
                       rj_neighbours_counts* counts);
 
+/* ---- face points: per face the count, the sum, min, max and the members of located points ---- */
+#define RJ_FP_MEMBERS 1u  /* also the CSR of the points of every face */
+typedef struct { int32_t label; uint32_t first; uint64_t n_points; uint64_t sum_lo; int64_t sum_hi;
+                 int64_t min, max; } rj_fp_face; /* 48 bytes */
+typedef struct { uint64_t n_faces, n_members, n_outside, n_unmatched, n_runs; } rj_face_points_counts;
+
+/* extends: the other half of a spatial join -- what GIS users know as Summarize Within, Points in Polygon count, or a
+ * spatial join with aggregation.  rj_pip_query stops at one int32 per point; this call turns that array into one row
+ * per face: how many points, the exact sum, the min and the max of an int64 attribute, and which points.  Its rows are
+ * numbered as rj_map_neighbours numbers its faces, so "points per face" and "neighbours of a face" are columns of one
+ * table.  (The reference has no counterpart.)
+ * Input: label_dev[n], the label of point i < n -- what rj_pip_query wrote to face_id_dev, but any int32 is accepted;
+ * n < 2^32.  value_dev (may be NULL: no values): the value of point i is value_dev[i * value_stride], value_stride >= 1
+ * in int64 elements; the scaled point array with stride 2, and then that array + 1, give the sums of x and of y (the mean
+ * centre per face).  face_label_dev[n_face_labels] (may be NULL), the universe: face k is face_label_dev[k]; the array
+ * must ascend strictly in (uint32_t) order of its labels and must not contain 0 -- exactly the label column of
+ * rj_map_neighbours' records; it is checked on the device.  Faces without a point appear with n_points = 0.  Without a
+ * universe the faces are the distinct nonzero labels among the points, in the same order.
+ * The definition, in full in rayjoin_amd/csrc/rj_face_points.h:
+ *   per face n_points; sum, a two's-complement int128 (sum_lo, sum_hi), exact; min and max, INT64_MAX / INT64_MIN where the
+ *   face has no point or there are no values (every sum is 0 then); first = the smallest point number in the face,
+ *   0xFFFFFFFF where there is none.  Counts: n_members = the points whose label is a face, n_outside = the points with
+ *   label 0, n_unmatched = the points with a nonzero label that is not in the universe (0 without one):
+ *   n_members + n_outside + n_unmatched == n.  n_runs = the number of i with i == 0 || label[i] != label[i - 1]: the
+ *   coherence of the point order, which decides the cost of the call.
+ * Output, caller-owned device memory: faces_dev[face_capacity] (may be NULL: no records).  Under RJ_FP_MEMBERS
+ * offsets_dev[face_capacity + 1] and members_dev[member_capacity]: the point numbers of face k lie at [offsets[k],
+ * offsets[k + 1]), ascending, and offsets[n_faces] == n_members.  Without the flag neither array is touched and
+ * member_capacity must be 0.
+ * All capacities 0 (arrays may be NULL) is the sizing call.  RJ_E_OVERFLOW when n_faces > face_capacity or, under the
+ * flag, n_members > member_capacity: *counts holds the true counts and nothing is written.  n == 0 is valid: no faces
+ * without a universe, every record empty with one.  RJ_E_INVALID, with nothing written: an unknown flag bit, a null
+ * label_dev with n > 0, a null counts, a capacity without its array (face_capacity needs faces_dev, or offsets_dev under
+ * the flag; under the flag a face_capacity also needs offsets_dev), member_capacity without the flag, value_stride == 0
+ * with values, a universe array that is NULL with n_face_labels > 0, n >= 2^32, n_face_labels >= 2^32 and a bad universe.
+ * Integers only, exact, fully determined: the accumulators are integer atomics, which commute, so no grid, wave layout or
+ * arrival order changes a result.  Runs on the handle's stream; with a universe one host sync, at the end; without one
+ * one more, behind the compaction of the run heads, to size their sort (only the heads are sorted, never all n labels).
+ * Scratch (rj_face_points.h has the bytes per face, per run head and per point) is allocated per call and freed; no map,
+ * index or option of the handle changes.  For tests and sweeps, through rj_set_debug_option: "face_points_blocks" (0: by
+ * size) is the grid of the table pass; any grid gives the same result.  rj_get_option: "face_points_last_us0" ..
+ * "face_points_last_us4" (HIP-event microseconds of the stages: universe, table, records, members, all; -1: no call yet,
+ * or the last call was refused). */
+int rj_face_points(rj_handle h, const int32_t* label_dev, uint64_t n,
+                   const int64_t* value_dev /* may be NULL */, uint64_t value_stride,
+                   const int32_t* face_label_dev /* may be NULL */, uint64_t n_face_labels,
+                   uint32_t flags, uint64_t face_capacity, uint64_t member_capacity,
+                   rj_fp_face* faces_dev /* may be NULL */, uint64_t* offsets_dev, uint32_t* members_dev,
+                   rj_face_points_counts* counts);
+/* label_dev[k] = faces_dev[k].label for k < n_faces: the label column of rj_map_neighbours' records as an array of its
+ * own, on the device -- what rj_face_points takes as its universe.  Synchronous, like the memory helpers below. */
+int rj_neighbours_labels(rj_handle h, const rj_nb_face* faces_dev, uint64_t n_faces, int32_t* label_dev);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

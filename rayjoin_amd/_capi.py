@@ -72,6 +72,11 @@ NB_FACE_DTYPE = np.dtype([("label", "<i4"), ("n_sides", "<u4"), ("n_edge_nbrs", 
 # rj_nb_entry: one neighbour of a face -- its label and face number, the chains and nodes the two share, the length of their border
 NB_ENTRY_DTYPE = np.dtype([("label", "<i4"), ("face", "<u4"), ("n_chains", "<u4"), ("n_nodes", "<u4"), ("w_lo", "<u8"), ("w_hi", "<u8")])
 NEIGHBOURS_COUNTS = ("n_faces", "n_entries", "n_edge_pairs", "n_vertex_pairs", "n_nodes", "n_node_pairs_raw", "max_labels_at_node")
+RJ_FP_MEMBERS = 1  # rj_face_points flags
+# rj_fp_face: one face of rj_face_points -- its label, its smallest point number (0xFFFFFFFF: none), its points, the exact sum of their
+# values (a two's-complement int128), their min and max (INT64_MAX / INT64_MIN: no point, or no values)
+FP_FACE_DTYPE = np.dtype([("label", "<i4"), ("first", "<u4"), ("n_points", "<u8"), ("sum_lo", "<u8"), ("sum_hi", "<i8"), ("min", "<i8"), ("max", "<i8")])
+FACE_POINTS_COUNTS = ("n_faces", "n_members", "n_outside", "n_unmatched", "n_runs")
 ELIMINATE_COUNTS = ("n_faces", "n_slivers", "n_eliminated", "n_islands", "n_mutual", "n_negative", "n_chains", "n_points", "n_dropped")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
@@ -132,6 +137,8 @@ SYMBOLS = {
     "rj_map_eliminate": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _u64, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rj_map_dissolve": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rj_map_neighbours": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "rj_face_points": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "rj_neighbours_labels": (_int, [_vp, _vp, _u64, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -259,6 +266,10 @@ class DissolveOverflow(CountsOverflow):
 
 class NeighboursOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_map_neighbours: counts = a dict of NEIGHBOURS_COUNTS, the true counts; nothing is written"""
+
+
+class FacePointsOverflow(CountsOverflow):
+    """RJ_E_OVERFLOW of rj_face_points: counts = a dict of FACE_POINTS_COUNTS, the true counts; nothing is written"""
 
 
 class NeighboursNodePairs(RayJoinError):
@@ -793,6 +804,29 @@ class Handle:
             raise NeighboursNodePairs(self.L.rj_last_error_string(self.h).decode(), named["n_node_pairs_raw"])
         self._check(rc)
         return named
+
+    def face_points(self, label_dev, n, capacities, value_dev=None, value_stride=1, face_label_dev=None, n_face_labels=0, faces_dev=None, offsets_dev=None,
+                    members_dev=None, flags=0):
+        """rj_face_points of n located points in device memory (label_dev: int32, what rj_pip_query wrote): per face the count,
+        the exact int128 sum, min and max of value_dev[i * value_stride] (int64; None: no values) and the smallest point number
+        as rj_fp_face records into faces_dev (or None); under RJ_FP_MEMBERS the uint64 offsets_dev [faces + 1] and the uint32
+        point numbers members_dev of every face.  face_label_dev [n_face_labels] (int32, or None): the faces, strictly ascending
+        as unsigned numbers, without 0 -- the label column of rj_map_neighbours' records; None: the distinct nonzero labels of
+        the points.  capacities = (faces, members); (0, 0) with arrays None is the sizing call.  Returns the counts as a dict
+        (FACE_POINTS_COUNTS); FacePointsOverflow (with the true counts) past a capacity."""
+        fc, mc = (int(v) for v in capacities)
+        counts = (_u64 * len(FACE_POINTS_COUNTS))()
+        rc = self.L.rj_face_points(self.h, _ptr(label_dev), int(n), _ptr(value_dev), int(value_stride), _ptr(face_label_dev), int(n_face_labels), int(flags),
+                                   fc, mc, _ptr(faces_dev), _ptr(offsets_dev), _ptr(members_dev), counts)
+        named = dict(zip(FACE_POINTS_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise FacePointsOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        self._check(rc)
+        return named
+
+    def neighbours_labels(self, faces_dev, n_faces, label_dev):
+        """label_dev[k] = the label of record k of rj_map_neighbours' faces_dev, on the device (rj_neighbours_labels)"""
+        self._check(self.L.rj_neighbours_labels(self.h, _ptr(faces_dev), int(n_faces), _ptr(label_dev)))
 
     def sort_pairs(self, pairs_dev, n):
         self._check(self.L.rj_sort_pairs(self.h, _ptr(pairs_dev), n))

@@ -20,6 +20,7 @@
 #include "rj_faces.h"
 #include "rj_node.h"
 #include "rj_kernels.h"
+#include "rj_face_points.h"
 #include "rj_neighbours.h"
 #include "rj_overlay_dev.h"
 #include "rj_overlay_ops.h"
@@ -296,6 +297,8 @@ struct rj_handle_s {
   DissolveReport dissolve_report;  // what the last rj_map_dissolve took (reports only)
   int debug_neighbours_point_blocks = 0;  // rj_map_neighbours: the grid of the pass over the points (0: by size; tests and sweeps: the same result)
   NeighboursReport neighbours_report;  // what the last rj_map_neighbours took (reports only)
+  int debug_face_points_blocks = 0;  // rj_face_points: the grid of the table pass (0: by size; tests and sweeps: the same result)
+  FacePointsReport face_points_report;  // what the last rj_face_points took (reports only)
   uint32_t stitch_stats[4] = {0, 0, 0, 0};  // the last run cutting: ranking rounds, incidences on closed loops, rounds of the second ranking, closed chains
   char* strip_scratch = nullptr;  // grow-only temporaries of the column index's build
   size_t strip_scratch_bytes = 0;
@@ -652,6 +655,7 @@ const Option kOptions[] = {
     {"elim_point_blocks", true, &rj_handle_s::debug_elim_point_blocks, 0, 1 << 20},  // rj_map_eliminate: blocks of its two passes over the points (0: by size)
     {"dissolve_point_blocks", true, &rj_handle_s::debug_dissolve_point_blocks, 0, 1 << 20},  // rj_map_dissolve: blocks of its point scatter (0: by size)
     {"neighbours_point_blocks", true, &rj_handle_s::debug_neighbours_point_blocks, 0, 1 << 20},  // rj_map_neighbours: blocks of its pass over the points (0: by size)
+    {"face_points_blocks", true, &rj_handle_s::debug_face_points_blocks, 0, 1 << 20},  // rj_face_points: blocks of its table pass (0: by size)
 };
 
 const Option* find_option(const char* name, bool debug) {
@@ -745,6 +749,7 @@ const Report kReports[] = {
     {"elim_last_us", 6, RJ_READ(h->eliminate_report.ms[k] < 0 ? -1 : (int64_t) (h->eliminate_report.ms[k] * 1000.0f))},  // the last rj_map_eliminate: check and chain sums, faces, pairs and choice, pointers, labels and scatter, all
     {"dissolve_last_us", 6, RJ_READ(h->dissolve_report.ms[k] < 0 ? -1 : (int64_t) (h->dissolve_report.ms[k] * 1000.0f))},  // the last rj_map_dissolve: check, classes and keep; ends and next; walks; class records; totals and scatter; all
     {"neighbours_last_us", 6, RJ_READ(h->neighbours_report.ms[k] < 0 ? -1 : (int64_t) (h->neighbours_report.ms[k] * 1000.0f))},  // the last rj_map_neighbours: check and chain sums, faces, edge pairs, nodes, the table, all
+    {"face_points_last_us", 5, RJ_READ(h->face_points_report.ms[k == 4 ? 5 : k] < 0 ? -1 : (int64_t) (h->face_points_report.ms[k == 4 ? 5 : k] * 1000.0f))},  // the last rj_face_points: universe, table, records, members, all
     {"comm_ranks", 0, read_comm_ranks},
     {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
     {"pip_share_blocks", 0, RJ_READ(h->last_pip_share ? h->last_pip_share : h->pip_share_blocks())},
@@ -3178,6 +3183,47 @@ int rj_map_neighbours(rj_handle h, const int64_t* xy_dev, uint64_t np, const uin
   if (!m.emit)
     return fail(h, RJ_E_OVERFLOW, "rj_map_neighbours: %llu faces, %llu entries; capacities %llu, %llu", (unsigned long long) counts->n_faces,
                 (unsigned long long) counts->n_entries, (unsigned long long) face_capacity, (unsigned long long) entry_capacity);
+  return RJ_OK;
+}
+
+int rj_face_points(rj_handle h, const int32_t* label_dev, uint64_t n, const int64_t* value_dev, uint64_t value_stride, const int32_t* face_label_dev,
+                   uint64_t n_face_labels, uint32_t flags, uint64_t face_capacity, uint64_t member_capacity, rj_fp_face* faces_dev, uint64_t* offsets_dev,
+                   uint32_t* members_dev, rj_face_points_counts* counts) {
+  static_assert(sizeof(rj_fp_face) == 48 && sizeof(face_points::Face) == 48 && sizeof(face_points::Acc) == 48 &&
+                    sizeof(rj_face_points_counts) == sizeof(face_points::Counts),
+                "layouts");
+  static_assert(RJ_FP_MEMBERS == face_points::kMembers, "flags");
+  RJ_CHECK_H(h);
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_face_points: counts is null");
+  memset(counts, 0, sizeof(*counts));
+  h->face_points_report = FacePointsReport{};
+  if (flags & ~(uint32_t) RJ_FP_MEMBERS) return fail(h, RJ_E_INVALID, "rj_face_points: unknown flags 0x%x", flags);
+  const bool members = (flags & RJ_FP_MEMBERS) != 0;
+  if (n && !label_dev) return fail(h, RJ_E_INVALID, "rj_face_points: null label array");
+  if (n >= face_points::kMaxPoints || n_face_labels >= face_points::kMaxPoints) return fail(h, RJ_E_INVALID, "rj_face_points: n < 2^32 and n_face_labels < 2^32");
+  if (value_dev && value_stride == 0) return fail(h, RJ_E_INVALID, "rj_face_points: value_stride >= 1");
+  if (n_face_labels && !face_label_dev) return fail(h, RJ_E_INVALID, "rj_face_points: n_face_labels without face_label_dev");
+  if (!members && member_capacity) return fail(h, RJ_E_INVALID, "rj_face_points: member_capacity without RJ_FP_MEMBERS");
+  if ((face_capacity && (members ? !offsets_dev : !faces_dev)) || (member_capacity && !members_dev)) return fail(h, RJ_E_INVALID, "rj_face_points: null output");
+  if (int r = set_device(h)) return r;
+  face_points::Meta m;
+  RJ_HIP(h, face_points_device(h->stream, label_dev, n, value_dev, value_stride, face_label_dev, n_face_labels, flags, face_capacity, member_capacity,
+                               reinterpret_cast<face_points::Face*>(faces_dev), members ? offsets_dev : nullptr, members ? members_dev : nullptr,
+                               h->debug_face_points_blocks, &m, &h->face_points_report));
+  if (m.bad) return fail(h, RJ_E_INVALID, "rj_face_points: face_label_dev must ascend strictly by (uint32_t) label and must not contain 0");
+  memcpy(counts, &m.counts, sizeof(*counts));
+  if (!m.emit)
+    return fail(h, RJ_E_OVERFLOW, "rj_face_points: %llu faces, %llu members; capacities %llu, %llu", (unsigned long long) counts->n_faces,
+                (unsigned long long) counts->n_members, (unsigned long long) face_capacity, (unsigned long long) member_capacity);
+  return RJ_OK;
+}
+
+int rj_neighbours_labels(rj_handle h, const rj_nb_face* faces_dev, uint64_t n_faces, int32_t* label_dev) {
+  RJ_CHECK_H(h);
+  if (n_faces && (!faces_dev || !label_dev)) return fail(h, RJ_E_INVALID, "rj_neighbours_labels: null array");
+  if (int r = set_device(h)) return r;
+  if (n_faces) RJ_HIP(h, neighbours_labels_device(h->stream, faces_dev, n_faces, label_dev));
+  RJ_HIP(h, hipStreamSynchronize(h->stream));
   return RJ_OK;
 }
 

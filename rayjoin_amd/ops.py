@@ -59,6 +59,8 @@
       -- the face adjacency table (rj_map_neighbours): which faces touch which, the integer length of the shared border,
          the chains that make it, with vertex=True the nodes where two faces meet and the faces that meet only at a
          vertex; CSR over the faces, to_csr() for a sparse matrix
+  face_points(handle, labels, n, values=, faces=, members=) / PIPLBVH.Summarize(values=, faces=, members=) -> DeviceFacePoints
+      -- per face the count, the exact sum, min, max and the members of located points (rj_face_points), rows as DeviceNeighbours' faces
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -235,6 +237,14 @@ class PIPLBVH:
 
     def get_face_ids(self):
         return self.faces.to_host(np.int32, self.n)
+
+    def Summarize(self, values=None, value_stride=1, faces=None, members=False, **kw):
+        """face_points over the face ids of the last Query, on the device, as a DeviceFacePoints: per face of the base map
+        how many of the queried points it holds, the exact sum, min and max of values[i * value_stride] (int64 in device
+        memory) and, with members, which points.  faces: the labels of the faces as a device int32 array or a
+        (device array, count) pair -- DeviceNeighbours.labels(handle) of the base map, so that the rows here are the
+        rows of its adjacency table."""
+        return face_points(self.h, self.faces, self.n, values=values, value_stride=value_stride, faces=faces, members=members, **kw)
 
 
 class LSIGrid(LSILBVH):
@@ -1230,8 +1240,94 @@ class DeviceNeighbours:
         offsets, entries = self.to_host()
         return offsets.astype(np.int64), entries["face"].astype(np.int64), entries
 
+    def labels(self, handle):
+        """-> the labels of the face records as a device int32 array (a DeviceBuffer with .count = n_faces), copied out of the
+        records on the device: what face_points and PIPLBVH.Summarize take as faces=.  The caller frees it."""
+        if self.faces is None:
+            raise ValueError("this table was made with records=False: it has no face records")
+        out = handle.alloc(4 * max(1, self.n_faces))
+        out.count = self.n_faces
+        handle.neighbours_labels(self.faces, self.n_faces, out)
+        return out
+
     def free(self):
         for b in (self.faces, self.offsets, self.entries):
+            if b is not None:
+                b.free()
+
+
+def face_points(handle, labels, n, values=None, value_stride=1, faces=None, members=False, records=True):
+    """Per-face counts, sums and members of n located points in device memory (rj_face_points) as a DeviceFacePoints.
+    labels: int32 per point, what a PIP query wrote (PIPLBVH.faces).  values: int64 in device memory, the value of point i
+    at values[i * value_stride]; None: counts only.  faces: the universe -- a device int32 array with a .count, or a
+    (device array, count) pair, strictly ascending as unsigned numbers and without 0 (DeviceNeighbours.labels); None: the
+    distinct nonzero labels of the points.  members (RJ_FP_MEMBERS): also the CSR of the points of every face.  records:
+    the face records (.faces, FP_FACE_DTYPE rows: label, first, n_points, sum, min, max).  A sizing call finds the capacities."""
+    n = int(n)
+    flags = _capi.RJ_FP_MEMBERS if members else 0
+    universe, n_universe = (None, 0) if faces is None else (tuple(faces) if isinstance(faces, (tuple, list)) else (faces, faces.count))
+    kw = dict(value_dev=values, value_stride=value_stride, face_label_dev=universe, n_face_labels=n_universe, flags=flags)
+    try:
+        c = handle.face_points(labels, n, (0, 0), **kw)
+    except _capi.FacePointsOverflow as e:
+        c = e.counts
+    fc, mc = c["n_faces"], c["n_members"] if members else 0
+    recs, offsets, mem, done = None, None, None, False
+    try:
+        if records:
+            recs = handle.alloc(_capi.FP_FACE_DTYPE.itemsize * max(1, fc))
+        if members:
+            offsets = handle.alloc(8 * (fc + 1))
+            mem = handle.alloc(4 * max(1, mc))
+        counts = handle.face_points(labels, n, (fc if records or members else 0, mc), faces_dev=recs, offsets_dev=offsets, members_dev=mem, **kw)
+        done = True
+    except _capi.FacePointsOverflow as e:
+        if records or members:
+            raise
+        counts, done = e.counts, True  # (neither records nor members: the counts are all there is)
+    finally:
+        if not done:
+            for b in (recs, offsets, mem):
+                if b is not None:
+                    b.free()
+    return DeviceFacePoints(recs, offsets, mem, counts)
+
+
+class DeviceFacePoints:
+    """Per-face counts, sums and members of located points in device memory (rj_face_points): faces (FP_FACE_DTYPE rows as a
+    DeviceBuffer, or None), under members offsets (uint64 [n_faces + 1]) and members (uint32 point numbers, ascending
+    inside every face), else None, and the counts n_faces, n_members, n_outside, n_unmatched, n_runs."""
+
+    def __init__(self, faces, offsets, members, counts):
+        self.faces, self.offsets, self.members = faces, offsets, members
+        self.counts = dict(counts)
+        self.n_faces, self.n_members = int(counts["n_faces"]), int(counts["n_members"])
+
+    def faces_to_host(self):
+        """-> the face records (FP_FACE_DTYPE), ascending by unsigned label; ValueError for a table made with records=False"""
+        if self.faces is None:
+            raise ValueError("this table was made with records=False: it has no face records")
+        return self.faces.to_host(_capi.FP_FACE_DTYPE, self.n_faces)
+
+    def to_host(self):
+        """-> (offsets uint64 [n_faces + 1], members uint32 [n_members]); ValueError for a table made without members"""
+        if self.offsets is None:
+            raise ValueError("this table was made with members=False: it has no member lists")
+        return self.offsets.to_host(np.uint64, self.n_faces + 1), self.members.to_host(np.uint32, self.n_members)
+
+    def to_csr(self):
+        """-> (indptr int64 [n_faces + 1], indices int64 [n_members]: the point numbers): the faces x points incidence matrix
+        as scipy.sparse.csr_matrix((ones, indices, indptr)) takes it"""
+        offsets, members = self.to_host()
+        return offsets.astype(np.int64), members.astype(np.int64)
+
+    def sums(self):
+        """-> the exact int128 sums of the faces as a list of Python ints"""
+        f = self.faces_to_host()
+        return [(int(hi) << 64) + int(lo) for lo, hi in zip(f["sum_lo"], f["sum_hi"])]
+
+    def free(self):
+        for b in (self.faces, self.offsets, self.members):
             if b is not None:
                 b.free()
 
