@@ -991,6 +991,45 @@ int rj_face_points(rj_handle h, const int32_t* label_dev, uint64_t n,
  * own, on the device -- what rj_face_points takes as its universe.  Synchronous, like the memory helpers below. */
 int rj_neighbours_labels(rj_handle h, const rj_nb_face* faces_dev, uint64_t n_faces, int32_t* label_dev);
 
+/* ---- nearest: the nearest edge of the base map for every point, and how far it is ---- */
+typedef struct { uint32_t eid; uint32_t where; uint64_t num_lo; int64_t num_hi; uint64_t den_lo, den_hi; } rj_near; /* 40 bytes */
+
+/* extends: the third query over the index of rj_build_lbvh, beside "which edge lies above a point" (rj_pip_query) and
+ * "which edges cross" (rj_lsi_query): which edge of the base map is nearest to each point, and how far it is -- what GIS
+ * users know as Near, sjoin_nearest or a join within a distance.  (The reference has no counterpart.)
+ * Points: exactly as rj_pip_query.  pts_dev NULL: the vertices [pt_begin, pt_begin + n) of the query map; otherwise n
+ * scaled points of the caller's (pt_begin is ignored), taken in the cached Morton order that rj_pip_query keeps for such
+ * arrays where that pays.  The order decides speed only.  n < 2^32.
+ * The definition, in full in rayjoin_amd/csrc/rj_nearest.h, in integers only: for the point P and the edge (A, B),
+ * l = |B - A|^2 and dot = (P - A) . (B - A);
+ *   dot <= 0      where = 1, the first end (also A == B):  d^2 = |P - A|^2
+ *   dot >= l      where = 2, the second end:               d^2 = |P - B|^2
+ *   otherwise     where = 0, the interior:                 d^2 = c^2 / l with c = (B - A) x (P - A)
+ * The nearest edge has the smallest d^2, compared exactly as rationals (up to 285 bits); ties -- the common case: every
+ * point nearest to an interior vertex of a chain -- go to the smaller eid.
+ * max_dist: negative = unlimited; otherwise an edge qualifies iff d^2 <= max_dist^2, exactly, equality included (the join
+ * within a distance); at most 2^48.
+ * Output, caller-owned device memory: eid_dev[n], the eid of the nearest qualifying edge, RJ_MISS_EID where there is none.
+ * rec_dev[n] (may be NULL): where = 0: (num_lo, num_hi) is the SIGNED cross product c as a two's-complement int128 and
+ * (den_lo, den_hi) = l, so d^2 = num^2 / den, and the sign of num tells the side of the edge (positive: left of A -> B);
+ * where = 1, 2: num = d^2 and den = 1; a miss: eid = RJ_MISS_EID and everything else 0.  Nothing is divided on the device.
+ * dist_dev[n] (may be NULL): sqrt(d^2) in double, within 2^-50 relative of the true value (separate conversions, one
+ * multiply, one divide, one square root), +inf on a miss: a convenience, no result depends on it.
+ * RJ_E_INVALID, with nothing written: map ids that are not {0, 1} and different, no index on the base map, a null eid_dev
+ * with n > 0, a point range outside the query map, n >= 2^32, max_dist > 2^48.  n == 0 is valid and writes nothing.
+ * Runs on the handle's stream and is synchronised when it returns.  The result does not depend on the grid, the order
+ * of the points, "leaf_order" or any other option.  No map, index or option of the handle changes; the cached point
+ * orders are those of rj_pip_query.  rj_get_option: "nearest_last_us0" .. "nearest_last_us2" (HIP-event microseconds of
+ * the stages: ordering, traversal, all; -1: no call yet, or the last call was refused or had n == 0).  Under "stats" 1
+ * rj_last_stats gives [0] leaf blocks visited, summed over the points (a point visits a block that its bound admits), [1]
+ * (point, edge) pairs evaluated exactly, [2] nodes expanded and [3] leaf blocks loaded, both per wave of 64 points.  For tests
+ * and sweeps, through rj_set_debug_option: "nearest_blocks" (0: by size) is the grid; any grid gives the same result;
+ * "nearest_order_nomem" 1 makes the ordering of the points behave as without memory: the call takes them as given, still
+ * returns RJ_OK, and remembers the array (pointer, n) so as not to try again until rj_invalidate or an upload of a map. */
+int rj_nearest_query(rj_handle h, int base_map_id, int query_map_id, const int64_t* pts_dev,
+                     uint64_t pt_begin, uint64_t n, int64_t max_dist,
+                     uint32_t* eid_dev, rj_near* rec_dev /* may be NULL */, double* dist_dev /* may be NULL */);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

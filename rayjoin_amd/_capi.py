@@ -77,6 +77,9 @@ RJ_FP_MEMBERS = 1  # rj_face_points flags
 # values (a two's-complement int128), their min and max (INT64_MAX / INT64_MIN: no point, or no values)
 FP_FACE_DTYPE = np.dtype([("label", "<i4"), ("first", "<u4"), ("n_points", "<u8"), ("sum_lo", "<u8"), ("sum_hi", "<i8"), ("min", "<i8"), ("max", "<i8")])
 FACE_POINTS_COUNTS = ("n_faces", "n_members", "n_outside", "n_unmatched", "n_runs")
+# rj_near: the nearest edge of one point (rj_nearest_query) -- where 0: num = the signed cross product (a two's-complement int128), den = the
+# squared length of the edge, d^2 = num^2 / den; where 1, 2 (first, second end): num = d^2, den = 1; a miss: eid = MISS_EID, the rest 0
+NEAR_DTYPE = np.dtype([("eid", "<u4"), ("where", "<u4"), ("num_lo", "<u8"), ("num_hi", "<i8"), ("den_lo", "<u8"), ("den_hi", "<u8")])
 ELIMINATE_COUNTS = ("n_faces", "n_slivers", "n_eliminated", "n_islands", "n_mutual", "n_negative", "n_chains", "n_points", "n_dropped")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
@@ -139,6 +142,7 @@ SYMBOLS = {
     "rj_map_neighbours": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp]),
     "rj_face_points": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp]),
     "rj_neighbours_labels": (_int, [_vp, _vp, _u64, _vp]),
+    "rj_nearest_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _i64, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -834,6 +838,14 @@ class Handle:
     def pip_query(self, base_map_id, query_map_id, pts_dev, pt_begin, n, closest_dev, face_dev=None, sync=True):
         fn = self.L.rj_pip_query if sync else self.L.rj_pip_query_async
         self._check(fn(self.h, base_map_id, query_map_id, _ptr(pts_dev), pt_begin, n, _ptr(closest_dev), _ptr(face_dev)))
+
+    def nearest_query(self, base_map_id, query_map_id, pts_dev, pt_begin, n, eid_dev, rec_dev=None, dist_dev=None, max_dist=-1):
+        """rj_nearest_query: for n points (pts_dev: int64 pairs in device memory, or None for the vertices [pt_begin, pt_begin + n)
+        of the query map) the eid of the nearest edge of the indexed base map into eid_dev (uint32, MISS_EID where none
+        qualifies), the exact record into rec_dev (NEAR_DTYPE, or None) and sqrt(d^2) into dist_dev (float64, +inf on a
+        miss, or None).  max_dist: negative = unlimited, else only edges with d <= max_dist qualify, exactly.  Synchronous."""
+        self._check(self.L.rj_nearest_query(self.h, base_map_id, query_map_id, _ptr(pts_dev), int(pt_begin), int(n), int(max_dist), _ptr(eid_dev),
+                                            _ptr(rec_dev), _ptr(dist_dev)))
 
     def last_ms(self, which):
         ms = C.c_float()

@@ -21,6 +21,7 @@
 #include "rj_node.h"
 #include "rj_kernels.h"
 #include "rj_face_points.h"
+#include "rj_nearest.h"
 #include "rj_neighbours.h"
 #include "rj_overlay_dev.h"
 #include "rj_overlay_ops.h"
@@ -299,6 +300,15 @@ struct rj_handle_s {
   NeighboursReport neighbours_report;  // what the last rj_map_neighbours took (reports only)
   int debug_face_points_blocks = 0;  // rj_face_points: the grid of the table pass (0: by size; tests and sweeps: the same result)
   FacePointsReport face_points_report;  // what the last rj_face_points took (reports only)
+  int debug_nearest_blocks = 0;  // rj_nearest_query: the grid of the traversal (0: by size; tests and sweeps: the same result)
+  int debug_nearest_order_nomem = 0;  // rj_nearest_query: 1 = the ordering of the points finds no memory (tests of the fallback to the given order)
+  StageMs nearest_report;  // what the last rj_nearest_query took: ordering, traversal, (nothing), (nothing), (nothing), all (reports only)
+  // the point sets (pointer, size) whose ordering found no memory in rj_nearest_query: taken in the given order from then on,
+  // not tried again -- until rj_invalidate or an upload of a map, which forget them (the oldest goes when a fifth fails)
+  struct NearestUnordered { const void* p = nullptr; uint64_t n = 0; bool valid = false; };
+  static constexpr int kNearestUnordered = 4;
+  NearestUnordered nearest_unordered[kNearestUnordered];
+  int nearest_unordered_next = 0;
   uint32_t stitch_stats[4] = {0, 0, 0, 0};  // the last run cutting: ranking rounds, incidences on closed loops, rounds of the second ranking, closed chains
   char* strip_scratch = nullptr;  // grow-only temporaries of the column index's build
   size_t strip_scratch_bytes = 0;
@@ -656,6 +666,8 @@ const Option kOptions[] = {
     {"dissolve_point_blocks", true, &rj_handle_s::debug_dissolve_point_blocks, 0, 1 << 20},  // rj_map_dissolve: blocks of its point scatter (0: by size)
     {"neighbours_point_blocks", true, &rj_handle_s::debug_neighbours_point_blocks, 0, 1 << 20},  // rj_map_neighbours: blocks of its pass over the points (0: by size)
     {"face_points_blocks", true, &rj_handle_s::debug_face_points_blocks, 0, 1 << 20},  // rj_face_points: blocks of its table pass (0: by size)
+    {"nearest_blocks", true, &rj_handle_s::debug_nearest_blocks, 0, 1 << 20},  // rj_nearest_query: blocks of its traversal (0: by size)
+    {"nearest_order_nomem", true, &rj_handle_s::debug_nearest_order_nomem, 0, 1},  // rj_nearest_query: the ordering pass behaves as without memory (the fallback)
 };
 
 const Option* find_option(const char* name, bool debug) {
@@ -750,6 +762,7 @@ const Report kReports[] = {
     {"dissolve_last_us", 6, RJ_READ(h->dissolve_report.ms[k] < 0 ? -1 : (int64_t) (h->dissolve_report.ms[k] * 1000.0f))},  // the last rj_map_dissolve: check, classes and keep; ends and next; walks; class records; totals and scatter; all
     {"neighbours_last_us", 6, RJ_READ(h->neighbours_report.ms[k] < 0 ? -1 : (int64_t) (h->neighbours_report.ms[k] * 1000.0f))},  // the last rj_map_neighbours: check and chain sums, faces, edge pairs, nodes, the table, all
     {"face_points_last_us", 5, RJ_READ(h->face_points_report.ms[k == 4 ? 5 : k] < 0 ? -1 : (int64_t) (h->face_points_report.ms[k == 4 ? 5 : k] * 1000.0f))},  // the last rj_face_points: universe, table, records, members, all
+    {"nearest_last_us", 3, RJ_READ(h->nearest_report.ms[k == 2 ? 5 : k] < 0 ? -1 : (int64_t) (h->nearest_report.ms[k == 2 ? 5 : k] * 1000.0f))},  // the last rj_nearest_query: ordering, traversal, all
     {"comm_ranks", 0, read_comm_ranks},
     {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
     {"pip_share_blocks", 0, RJ_READ(h->last_pip_share ? h->last_pip_share : h->pip_share_blocks())},
@@ -862,7 +875,7 @@ int rj_create(int device_id, rj_handle* out) {
             hipHostMalloc((void**) &h->h_est, 64, hipHostMallocMapped) == hipSuccess &&
             hipHostGetDevicePointer((void**) &h->d_est, h->h_est, 0) == hipSuccess;
   if (ok) {
-    h->h_fault[0] = h->h_fault[1] = 0;
+    h->h_fault[0] = h->h_fault[1] = h->h_fault[kFaultNearestStack] = 0;
     h->h_rest[0] = h->h_rest[1] = ~0ull;  // (no finished two-pass query yet)
     h->h_rest[2] = ~0ull;                 // (... and no records produced yet: k_lsi_points' pair count)
     for (int k = 0; k < rj_handle_s::kCallerSets; k++) h->h_est[k] = 0;
@@ -945,6 +958,7 @@ int rj_invalidate(rj_handle h) {
     h->caller[k].valid = h->caller[k].has_perm = false;
     h->h_est[k] = 0;
   }
+  for (auto& u : h->nearest_unordered) u.valid = false;
   return RJ_OK;
 }
 
@@ -1079,6 +1093,7 @@ static int install_map(rj_handle h, int map_id, uint64_t np, uint64_t nc, const 
   free_grid(h->grid[map_id]);
   h->coh[0][map_id].valid = h->coh[1][map_id].valid = false;
   h->ordc[0][map_id].valid = h->ordc[1][map_id].valid = false;
+  for (auto& u : h->nearest_unordered) u.valid = false;
   m.np = np; m.nc = nc; m.ne = np - nc;
   int rc = RJ_OK;
   if (!rc) rc = dev_alloc(h, &m.pts, 2 * np + 2);
@@ -2273,6 +2288,85 @@ int rj_pip_query(rj_handle h, int base_map_id, int query_map_id, const int64_t* 
   RJ_HIP(h, join_aux(h));
   if (h->stats_on) for (int i = 0; i < 16; i++) h->last_stats[i] = h->h_pinned[1 + i];
   return check_fault(h);
+}
+
+// ---- the nearest edge of the base map for every point (rj_nearest.h, rj_nearest.hip) ----------------------------------------
+int rj_nearest_query(rj_handle h, int base_map_id, int query_map_id, const int64_t* pts_dev, uint64_t pt_begin, uint64_t n, int64_t max_dist,
+                     uint32_t* eid_dev, rj_near* rec_dev, double* dist_dev) {
+  static_assert(sizeof(rj_near) == 40 && sizeof(nearest::Near) == 40, "layouts");
+  static_assert(RJ_MISS_EID == nearest::kMissEid, "the miss value");
+  RJ_CHECK_H(h);
+  h->nearest_report = StageMs{};
+  if (base_map_id < 0 || base_map_id > 1 || query_map_id != 1 - base_map_id)
+    return fail(h, RJ_E_INVALID, "rj_nearest_query: base/query map ids must be {0,1} and differ");
+  if (!h->bvh[base_map_id].built) return fail(h, RJ_E_INVALID, "rj_nearest_query: call rj_build_lbvh(base map) first");
+  if (n && !eid_dev) return fail(h, RJ_E_INVALID, "rj_nearest_query: null output");
+  if (max_dist > nearest::kMaxDist) return fail(h, RJ_E_INVALID, "rj_nearest_query: max_dist must not exceed 2^48 (negative: unlimited)");
+  const int64_t* pts = pts_dev;
+  uint64_t coh_begin = 0;
+  if (!pts) {
+    coh_begin = pt_begin;
+    const MapState& q = h->map[query_map_id];
+    if (!q.present || pt_begin + n > q.np || pt_begin + n < pt_begin) return fail(h, RJ_E_INVALID, "rj_nearest_query: bad point range of the query map");
+    pts = q.pts + 2 * pt_begin;
+  }
+  if (n >= (1ull << 32)) return fail(h, RJ_E_INVALID, "rj_nearest_query: n < 2^32");
+  if (n == 0) return RJ_OK;
+  if (int r = set_device(h)) return r;
+  StageEvents ev;
+  RJ_HIP(h, ev.create());
+  RJ_HIP(h, ev.mark(0, h->stream));
+  // The order the points are taken in: PIP's, with PIP's caches (the Morton order of a map's vertices, what the handle
+  // knows about a caller's array).  It decides speed only.  An ordering that finds no memory (the sort's scratch, the
+  // cached permutation) leaves the given order, and that point set is not tried again; every other failure is the call's.
+  const uint32_t* order = nullptr;
+  h->lazy_columns_ok = false;
+  bool given_order = false;
+  for (const auto& u : h->nearest_unordered) given_order = given_order || (u.valid && u.p == pts && u.n == n);
+  if (!given_order) {
+    const std::string err_before = h->err;
+    const int r = h->debug_nearest_order_nomem ? RJ_E_NOMEM : maybe_order_queries(h, true, pts, nullptr, 0, n, &order, pts_dev ? -1 : query_map_id, coh_begin);
+    if (r == RJ_E_NOMEM) {
+      (void) hipGetLastError();
+      h->err = err_before;  // (the call goes on and returns RJ_OK: no message of its own)
+      rj_handle_s::NearestUnordered& u = h->nearest_unordered[h->nearest_unordered_next];
+      h->nearest_unordered_next = (h->nearest_unordered_next + 1) % rj_handle_s::kNearestUnordered;
+      u.p = pts; u.n = n; u.valid = true;
+      given_order = true;
+    } else if (r != RJ_OK) {
+      return r;
+    }
+  }
+  if (given_order) {  // (nothing of another query's order may stay behind: the estimate below goes by cur_caller and cur_order)
+    order = nullptr;
+    h->last_ordered = false; h->order_fresh = false; h->cur_caller = -1; h->cur_order = nullptr;
+  }
+  if (h->stats_on) RJ_HIP(h, hipMemsetAsync(h->d_stats, 0, 128, h->stream));
+  NearestArgs a;
+  a.bvh = bvh_view(h->bvh[base_map_id]);
+  a.pts = pts; a.n = n; a.order = order;
+  a.max_dist = max_dist;
+  a.eid = eid_dev; a.rec = reinterpret_cast<nearest::Near*>(rec_dev); a.dist = dist_dev;
+  a.fault = h->d_fault;
+  a.stats = h->stats_on ? h->d_stats : nullptr;
+  a.stack_cap = h->debug_stack_cap;
+  RJ_HIP(h, ev.mark(1, h->stream));
+  RJ_HIP(h, launch_nearest(h->stream, a, h->stats_on != 0, h->debug_nearest_blocks, h->cus));
+  RJ_HIP(h, ev.mark(2, h->stream));
+  // (a caller's array: the estimate that the next query over it goes by, as behind a PIP query)
+  if (h->cur_caller >= 0) {
+    const rj_handle_s::CallerSet& e = h->caller[h->cur_caller];
+    if (e.queries <= 2 || e.queries % 4 == 0) RJ_HIP(h, launch_group_extent_tail(h->stream, pts, h->cur_order, n, h->d_est + h->cur_caller));
+  }
+  if (h->stats_on) RJ_HIP(h, hipMemcpyAsync(h->h_pinned + 1, h->d_stats, 128, hipMemcpyDeviceToHost, h->stream));
+  RJ_HIP(h, hipStreamSynchronize(h->stream));
+  ev.times(2, h->nearest_report.ms);
+  if (h->stats_on) for (int i = 0; i < 16; i++) h->last_stats[i] = h->h_pinned[1 + i];
+  if (h->h_fault[kFaultNearestStack]) {
+    h->h_fault[kFaultNearestStack] = 0;
+    return fail(h, RJ_E_INTERNAL, "traversal stack overflow in k_nearest: results are incomplete");
+  }
+  return RJ_OK;
 }
 
 

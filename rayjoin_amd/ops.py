@@ -61,6 +61,9 @@
          vertex; CSR over the faces, to_csr() for a sparse matrix
   face_points(handle, labels, n, values=, faces=, members=) / PIPLBVH.Summarize(values=, faces=, members=) -> DeviceFacePoints
       -- per face the count, the exact sum, min, max and the members of located points (rj_face_points), rows as DeviceNeighbours' faces
+  NearestLBVH(ctx).Init(n_points); .Query(query_map_id, query_points, max_dist=); .get_eids(); .get_records(); .get_dist()
+      -- the nearest edge of the indexed map for every point and its exact distance (rj_nearest_query): Near, sjoin_nearest,
+         the join within a distance
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -245,6 +248,78 @@ class PIPLBVH:
         (device array, count) pair -- DeviceNeighbours.labels(handle) of the base map, so that the rows here are the
         rows of its adjacency table."""
         return face_points(self.h, self.faces, self.n, values=values, value_stride=value_stride, faces=faces, members=members, **kw)
+
+
+class NearestLBVH:
+    """The nearest edge of the indexed base map for every query point (rj_nearest_query), mirroring PIPLBVH: the eid, the
+    exact record (which end or the interior, and d^2 as a rational) and the distance in double."""
+
+    def __init__(self, dctx):
+        self.ctx_ = dctx
+        self.h = dctx.handle
+        self.eids = self.records = self.dist = None
+        self.n = 0
+        self.has_records = self.has_dist = False
+
+    def Init(self, n_points):
+        self.n_alloc = int(n_points)
+        self.eids = self.h.alloc(4 * max(1, self.n_alloc))
+        self.records = self.h.alloc(_capi.NEAR_DTYPE.itemsize * max(1, self.n_alloc))
+        self.dist = self.h.alloc(8 * max(1, self.n_alloc))
+
+    def Query(self, query_map_id, query_points=None, point_range=None, max_dist=None, records=True, dist=True):
+        """query_points: int64[n,2] scaled host points, or None for the query map's own vertices, optionally a [begin, end)
+        sub-range (a shard).  max_dist (scaled units, None: unlimited): only edges within it qualify, the others' points
+        miss.  records / dist: whether the call fills them.  Returns the number of points."""
+        base = 1 - query_map_id
+        md = -1 if max_dist is None else int(max_dist)
+        rec, dst = (self.records if records else None), (self.dist if dist else None)
+        if query_points is not None:
+            pts = np.ascontiguousarray(query_points, dtype=np.int64).reshape(-1, 2)
+            n = pts.shape[0]
+            assert n <= self.n_alloc
+            buf = self.h.alloc(16 * max(1, n)).from_host(pts)
+            try:
+                self.h.nearest_query(base, query_map_id, buf, 0, n, self.eids, rec, dst, md)
+            finally:
+                buf.free()
+        else:
+            b, e = point_range if point_range is not None else (0, self.ctx_.get_map(query_map_id).n_points)
+            n = e - b
+            assert n <= self.n_alloc
+            self.h.nearest_query(base, query_map_id, None, b, n, self.eids, rec, dst, md)
+        self.n, self.has_records, self.has_dist = n, bool(records), bool(dist)
+        return n
+
+    def get_eids(self):
+        return self.eids.to_host(np.uint32, self.n)
+
+    def get_records(self):
+        """-> NEAR_DTYPE rows; ValueError after a Query with records=False"""
+        if not self.has_records:
+            raise ValueError("the last Query ran with records=False")
+        return self.records.to_host(_capi.NEAR_DTYPE, self.n)
+
+    def get_dist(self):
+        if not self.has_dist:
+            raise ValueError("the last Query ran with dist=False")
+        return self.dist.to_host(np.float64, self.n)
+
+    @staticmethod
+    def exact(records):
+        """NEAR_DTYPE rows -> [(eid, where, num, den)] with num (signed) and den as Python ints: d^2 = num^2 / den where
+        `where` is 0, num / den (den = 1) at an end"""
+        return [(int(r["eid"]), int(r["where"]), (int(r["num_hi"]) << 64) + int(r["num_lo"]), (int(r["den_hi"]) << 64) + int(r["den_lo"])) for r in records]
+
+    def nums(self):
+        """-> the exact num of every record as a list of Python ints"""
+        return [t[2] for t in self.exact(self.get_records())]
+
+    def free(self):
+        for b in (self.eids, self.records, self.dist):
+            if b is not None:
+                b.free()
+        self.eids = self.records = self.dist = None
 
 
 class LSIGrid(LSILBVH):
