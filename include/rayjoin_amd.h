@@ -1030,6 +1030,53 @@ int rj_nearest_query(rj_handle h, int base_map_id, int query_map_id, const int64
                      uint64_t pt_begin, uint64_t n, int64_t max_dist,
                      uint32_t* eid_dev, rj_near* rec_dev /* may be NULL */, double* dist_dev /* may be NULL */);
 
+/* ---- within: every edge of the base map within a distance of each point, as a CSR ---- */
+typedef struct { uint64_t n_pairs, n_points_hit, max_per_point; } rj_within_counts;
+
+/* extends: rj_nearest_query with max_dist says WHETHER an edge lies within the distance of a point; this call says WHICH
+ * edges do, all of them -- what GIS users know as dwithin, "Select by distance" or "Generate Near Table (all)": every road
+ * segment within 100 m of each address, how many shorelines within 1 km of each station.  The fourth query over the index
+ * of rj_build_lbvh and the first whose result is a CSR, the shape that rj_face_points (RJ_FP_MEMBERS) and rj_map_neighbours
+ * hand out.  (The reference has no counterpart.)
+ * Points: exactly as rj_nearest_query.  pts_dev NULL: the vertices [pt_begin, pt_begin + n) of the query map; otherwise n
+ * scaled points of the caller's (pt_begin is ignored), taken in the cached Morton order that rj_pip_query keeps for such
+ * arrays where that pays; an ordering that finds no memory leaves the given order.  The order decides speed only.  n < 2^32.
+ * The definition, in full in rayjoin_amd/csrc/rj_within.h on the functions of rj_nearest.h: edge e belongs to point i iff
+ * d^2 (P_i, e) <= max_dist^2 with d^2 = N / D as in rj_nearest_query, compared exactly (N <= max_dist^2 D), equality
+ * included.  A point on an interior vertex of a chain lists both edges k and k + 1: a pair list, not a nearest.
+ * 0 <= max_dist <= 2^48; a negative value is refused here, "unlimited" would be n x ne pairs.
+ * Output, caller-owned device memory: offsets_dev[n + 1] (may be NULL), eid_dev[pair_capacity]: the eids of point i lie at
+ * eid_dev[offsets[i] .. offsets[i + 1]), ASCENDING in eid, offsets[0] == 0 and offsets[n] == n_pairs.  rec_dev[pair_capacity]
+ * (may be NULL): the rj_near of pair k -- eid, where, num and den mean what they mean in rj_nearest_query, nothing is
+ * divided.  dist_dev[pair_capacity] (may be NULL): sqrt(d^2) in double, within 2^-50 relative.  *counts: n_pairs,
+ * n_points_hit = the points with a list that is not empty, max_per_point = the longest list.
+ * pair_capacity == 0 is the counting call: eid_dev, rec_dev and dist_dev may be NULL and are not touched, offsets_dev (if
+ * given) and *counts are written, RJ_OK -- also the cheap answer to "how many edges within d of each point".
+ * RJ_E_OVERFLOW when pair_capacity > 0 and n_pairs > pair_capacity: *counts holds the true counts and offsets_dev (if
+ * given) the true offsets; eid_dev, rec_dev and dist_dev are untouched.  n == 0 is valid: the counts are zero and
+ * offsets_dev[0] = 0 if given.
+ * RJ_E_INVALID, with nothing written, *counts neither: map ids that are not {0, 1} and different, no index on the base map,
+ * a null counts, pair_capacity > 0 with a null eid_dev, a point range outside the query map (a wrapping end too),
+ * n >= 2^32, pair_capacity >= 2^32, max_dist < 0 or > 2^48.  RJ_E_INTERNAL when the traversal's stack overflowed (cannot
+ * happen on a tree that rj_build_lbvh accepts).
+ * Runs on the handle's stream and is synchronised when it returns; inside it one more host sync, behind the scan of the
+ * counts: the number of pairs sizes the sort.  The result does not depend on the grid, the order of the points,
+ * "leaf_order" or any other option: the pairs are found in any order as 64-bit keys (point << 32 | eid) and sorted.  No
+ * map, index or option of the handle changes; the cached point orders are those of rj_pip_query.
+ * Scratch is allocated per call and freed: 12 bytes per point and 8 bytes per pair of capacity, then 8 bytes per pair found,
+ * plus rocPRIM's temporaries of one scan and one radix sort (rayjoin_amd/csrc/rj_within.h); the counting call takes the
+ * per-point part only.
+ * rj_get_option: "within_last_us0" .. "within_last_us3" (HIP-event microseconds of the stages: ordering, traversal, sort
+ * + outputs, all; -1: no call yet, or the last call was refused or had n == 0).  Under "stats" 1 rj_last_stats gives [0]
+ * .. [3] as after rj_nearest_query and [4] the pairs appended.  For tests and sweeps, through rj_set_debug_option:
+ * "within_blocks" (0: by size) is the grid of the traversal; any grid gives the same result; "nearest_order_nomem" acts
+ * here as in rj_nearest_query. */
+int rj_within_query(rj_handle h, int base_map_id, int query_map_id, const int64_t* pts_dev,
+                    uint64_t pt_begin, uint64_t n, int64_t max_dist, uint64_t pair_capacity,
+                    uint64_t* offsets_dev /* [n + 1], may be NULL */, uint32_t* eid_dev /* [pair_capacity] */,
+                    rj_near* rec_dev /* [pair_capacity], may be NULL */, double* dist_dev /* [pair_capacity], may be NULL */,
+                    rj_within_counts* counts);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

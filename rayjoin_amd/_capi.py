@@ -80,6 +80,7 @@ FACE_POINTS_COUNTS = ("n_faces", "n_members", "n_outside", "n_unmatched", "n_run
 # rj_near: the nearest edge of one point (rj_nearest_query) -- where 0: num = the signed cross product (a two's-complement int128), den = the
 # squared length of the edge, d^2 = num^2 / den; where 1, 2 (first, second end): num = d^2, den = 1; a miss: eid = MISS_EID, the rest 0
 NEAR_DTYPE = np.dtype([("eid", "<u4"), ("where", "<u4"), ("num_lo", "<u8"), ("num_hi", "<i8"), ("den_lo", "<u8"), ("den_hi", "<u8")])
+WITHIN_COUNTS = ("n_pairs", "n_points_hit", "max_per_point")
 ELIMINATE_COUNTS = ("n_faces", "n_slivers", "n_eliminated", "n_islands", "n_mutual", "n_negative", "n_chains", "n_points", "n_dropped")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
@@ -143,6 +144,7 @@ SYMBOLS = {
     "rj_face_points": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp]),
     "rj_neighbours_labels": (_int, [_vp, _vp, _u64, _vp]),
     "rj_nearest_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _i64, _vp, _vp, _vp]),
+    "rj_within_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _i64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -274,6 +276,10 @@ class NeighboursOverflow(CountsOverflow):
 
 class FacePointsOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_face_points: counts = a dict of FACE_POINTS_COUNTS, the true counts; nothing is written"""
+
+
+class WithinOverflow(CountsOverflow):
+    """RJ_E_OVERFLOW of rj_within_query: counts = a dict of WITHIN_COUNTS, the true counts; the offsets are written, the pairs are not"""
 
 
 class NeighboursNodePairs(RayJoinError):
@@ -846,6 +852,23 @@ class Handle:
         miss, or None).  max_dist: negative = unlimited, else only edges with d <= max_dist qualify, exactly.  Synchronous."""
         self._check(self.L.rj_nearest_query(self.h, base_map_id, query_map_id, _ptr(pts_dev), int(pt_begin), int(n), int(max_dist), _ptr(eid_dev),
                                             _ptr(rec_dev), _ptr(dist_dev)))
+
+    def within_query(self, base_map_id, query_map_id, pts_dev, pt_begin, n, max_dist, pair_capacity=0, offsets_dev=None, eid_dev=None, rec_dev=None,
+                     dist_dev=None):
+        """rj_within_query: for n points (pts_dev: int64 pairs in device memory, or None for the vertices [pt_begin, pt_begin + n)
+        of the query map) every edge of the indexed base map with d <= max_dist, exactly, as a CSR: the uint64 offsets_dev
+        [n + 1] (or None) and, ascending per point, the eids into eid_dev (uint32), the exact records into rec_dev (NEAR_DTYPE, or
+        None) and sqrt(d^2) into dist_dev (float64, or None), each of pair_capacity entries.  pair_capacity 0 is the counting
+        call.  Returns the counts as a dict (WITHIN_COUNTS); WithinOverflow (with the true counts) past the capacity.
+        Synchronous."""
+        counts = (_u64 * len(WITHIN_COUNTS))()
+        rc = self.L.rj_within_query(self.h, base_map_id, query_map_id, _ptr(pts_dev), int(pt_begin), int(n), int(max_dist), int(pair_capacity),
+                                    _ptr(offsets_dev), _ptr(eid_dev), _ptr(rec_dev), _ptr(dist_dev), counts)
+        named = dict(zip(WITHIN_COUNTS, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise WithinOverflow(self.L.rj_last_error_string(self.h).decode(), named)
+        self._check(rc)
+        return named
 
     def last_ms(self, which):
         ms = C.c_float()

@@ -22,6 +22,7 @@
 #include "rj_kernels.h"
 #include "rj_face_points.h"
 #include "rj_nearest.h"
+#include "rj_within.h"
 #include "rj_neighbours.h"
 #include "rj_overlay_dev.h"
 #include "rj_overlay_ops.h"
@@ -309,6 +310,8 @@ struct rj_handle_s {
   static constexpr int kNearestUnordered = 4;
   NearestUnordered nearest_unordered[kNearestUnordered];
   int nearest_unordered_next = 0;
+  int debug_within_blocks = 0;  // rj_within_query: the grid of the traversal (0: by size; tests and sweeps: the same result)
+  StageMs within_report;  // what the last rj_within_query took: ordering, traversal, sort + outputs, (nothing), (nothing), all (reports only)
   uint32_t stitch_stats[4] = {0, 0, 0, 0};  // the last run cutting: ranking rounds, incidences on closed loops, rounds of the second ranking, closed chains
   char* strip_scratch = nullptr;  // grow-only temporaries of the column index's build
   size_t strip_scratch_bytes = 0;
@@ -667,7 +670,8 @@ const Option kOptions[] = {
     {"neighbours_point_blocks", true, &rj_handle_s::debug_neighbours_point_blocks, 0, 1 << 20},  // rj_map_neighbours: blocks of its pass over the points (0: by size)
     {"face_points_blocks", true, &rj_handle_s::debug_face_points_blocks, 0, 1 << 20},  // rj_face_points: blocks of its table pass (0: by size)
     {"nearest_blocks", true, &rj_handle_s::debug_nearest_blocks, 0, 1 << 20},  // rj_nearest_query: blocks of its traversal (0: by size)
-    {"nearest_order_nomem", true, &rj_handle_s::debug_nearest_order_nomem, 0, 1},  // rj_nearest_query: the ordering pass behaves as without memory (the fallback)
+    {"nearest_order_nomem", true, &rj_handle_s::debug_nearest_order_nomem, 0, 1},  // rj_nearest_query and rj_within_query: the ordering pass behaves as without memory (the fallback)
+    {"within_blocks", true, &rj_handle_s::debug_within_blocks, 0, 1 << 20},  // rj_within_query: blocks of its traversal (0: by size)
 };
 
 const Option* find_option(const char* name, bool debug) {
@@ -763,6 +767,7 @@ const Report kReports[] = {
     {"neighbours_last_us", 6, RJ_READ(h->neighbours_report.ms[k] < 0 ? -1 : (int64_t) (h->neighbours_report.ms[k] * 1000.0f))},  // the last rj_map_neighbours: check and chain sums, faces, edge pairs, nodes, the table, all
     {"face_points_last_us", 5, RJ_READ(h->face_points_report.ms[k == 4 ? 5 : k] < 0 ? -1 : (int64_t) (h->face_points_report.ms[k == 4 ? 5 : k] * 1000.0f))},  // the last rj_face_points: universe, table, records, members, all
     {"nearest_last_us", 3, RJ_READ(h->nearest_report.ms[k == 2 ? 5 : k] < 0 ? -1 : (int64_t) (h->nearest_report.ms[k == 2 ? 5 : k] * 1000.0f))},  // the last rj_nearest_query: ordering, traversal, all
+    {"within_last_us", 4, RJ_READ(h->within_report.ms[k == 3 ? 5 : k] < 0 ? -1 : (int64_t) (h->within_report.ms[k == 3 ? 5 : k] * 1000.0f))},  // the last rj_within_query: ordering, traversal, sort + outputs, all
     {"comm_ranks", 0, read_comm_ranks},
     {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
     {"pip_share_blocks", 0, RJ_READ(h->last_pip_share ? h->last_pip_share : h->pip_share_blocks())},
@@ -875,7 +880,7 @@ int rj_create(int device_id, rj_handle* out) {
             hipHostMalloc((void**) &h->h_est, 64, hipHostMallocMapped) == hipSuccess &&
             hipHostGetDevicePointer((void**) &h->d_est, h->h_est, 0) == hipSuccess;
   if (ok) {
-    h->h_fault[0] = h->h_fault[1] = h->h_fault[kFaultNearestStack] = 0;
+    h->h_fault[0] = h->h_fault[1] = h->h_fault[kFaultNearestStack] = h->h_fault[kFaultWithinStack] = 0;
     h->h_rest[0] = h->h_rest[1] = ~0ull;  // (no finished two-pass query yet)
     h->h_rest[2] = ~0ull;                 // (... and no records produced yet: k_lsi_points' pair count)
     for (int k = 0; k < rj_handle_s::kCallerSets; k++) h->h_est[k] = 0;
@@ -2290,6 +2295,45 @@ int rj_pip_query(rj_handle h, int base_map_id, int query_map_id, const int64_t* 
   return check_fault(h);
 }
 
+// The order the points of a distance query (rj_nearest_query, rj_within_query) are taken in: PIP's, with PIP's caches (the
+// Morton order of a map's vertices, what the handle knows about a caller's array).  It decides speed only.  An ordering that
+// finds no memory (the sort's scratch, the cached permutation) leaves the given order, and that point set is not tried again;
+// every other failure is the call's.  *order_out: null (the given order) or the permutation.
+static int order_distance_points(rj_handle h, const int64_t* pts, bool callers, int query_map_id, uint64_t coh_begin, uint64_t n, const uint32_t** order_out) {
+  const uint32_t* order = nullptr;
+  h->lazy_columns_ok = false;
+  bool given_order = false;
+  for (const auto& u : h->nearest_unordered) given_order = given_order || (u.valid && u.p == pts && u.n == n);
+  if (!given_order) {
+    const std::string err_before = h->err;
+    const int r = h->debug_nearest_order_nomem ? RJ_E_NOMEM : maybe_order_queries(h, true, pts, nullptr, 0, n, &order, callers ? -1 : query_map_id, coh_begin);
+    if (r == RJ_E_NOMEM) {
+      (void) hipGetLastError();
+      h->err = err_before;  // (the call goes on and returns RJ_OK: no message of its own)
+      rj_handle_s::NearestUnordered& u = h->nearest_unordered[h->nearest_unordered_next];
+      h->nearest_unordered_next = (h->nearest_unordered_next + 1) % rj_handle_s::kNearestUnordered;
+      u.p = pts; u.n = n; u.valid = true;
+      given_order = true;
+    } else if (r != RJ_OK) {
+      return r;
+    }
+  }
+  if (given_order) {  // (nothing of another query's order may stay behind: the estimate below goes by cur_caller and cur_order)
+    order = nullptr;
+    h->last_ordered = false; h->order_fresh = false; h->cur_caller = -1; h->cur_order = nullptr;
+  }
+  *order_out = order;
+  return RJ_OK;
+}
+// (a caller's array: the estimate that the next query over it goes by, as behind a PIP query)
+static int estimate_distance_points(rj_handle h, const int64_t* pts, uint64_t n) {
+  if (h->cur_caller >= 0) {
+    const rj_handle_s::CallerSet& e = h->caller[h->cur_caller];
+    if (e.queries <= 2 || e.queries % 4 == 0) RJ_HIP(h, launch_group_extent_tail(h->stream, pts, h->cur_order, n, h->d_est + h->cur_caller));
+  }
+  return RJ_OK;
+}
+
 // ---- the nearest edge of the base map for every point (rj_nearest.h, rj_nearest.hip) ----------------------------------------
 int rj_nearest_query(rj_handle h, int base_map_id, int query_map_id, const int64_t* pts_dev, uint64_t pt_begin, uint64_t n, int64_t max_dist,
                      uint32_t* eid_dev, rj_near* rec_dev, double* dist_dev) {
@@ -2316,31 +2360,8 @@ int rj_nearest_query(rj_handle h, int base_map_id, int query_map_id, const int64
   StageEvents ev;
   RJ_HIP(h, ev.create());
   RJ_HIP(h, ev.mark(0, h->stream));
-  // The order the points are taken in: PIP's, with PIP's caches (the Morton order of a map's vertices, what the handle
-  // knows about a caller's array).  It decides speed only.  An ordering that finds no memory (the sort's scratch, the
-  // cached permutation) leaves the given order, and that point set is not tried again; every other failure is the call's.
   const uint32_t* order = nullptr;
-  h->lazy_columns_ok = false;
-  bool given_order = false;
-  for (const auto& u : h->nearest_unordered) given_order = given_order || (u.valid && u.p == pts && u.n == n);
-  if (!given_order) {
-    const std::string err_before = h->err;
-    const int r = h->debug_nearest_order_nomem ? RJ_E_NOMEM : maybe_order_queries(h, true, pts, nullptr, 0, n, &order, pts_dev ? -1 : query_map_id, coh_begin);
-    if (r == RJ_E_NOMEM) {
-      (void) hipGetLastError();
-      h->err = err_before;  // (the call goes on and returns RJ_OK: no message of its own)
-      rj_handle_s::NearestUnordered& u = h->nearest_unordered[h->nearest_unordered_next];
-      h->nearest_unordered_next = (h->nearest_unordered_next + 1) % rj_handle_s::kNearestUnordered;
-      u.p = pts; u.n = n; u.valid = true;
-      given_order = true;
-    } else if (r != RJ_OK) {
-      return r;
-    }
-  }
-  if (given_order) {  // (nothing of another query's order may stay behind: the estimate below goes by cur_caller and cur_order)
-    order = nullptr;
-    h->last_ordered = false; h->order_fresh = false; h->cur_caller = -1; h->cur_order = nullptr;
-  }
+  if (int r = order_distance_points(h, pts, pts_dev != nullptr, query_map_id, coh_begin, n, &order)) return r;
   if (h->stats_on) RJ_HIP(h, hipMemsetAsync(h->d_stats, 0, 128, h->stream));
   NearestArgs a;
   a.bvh = bvh_view(h->bvh[base_map_id]);
@@ -2353,11 +2374,7 @@ int rj_nearest_query(rj_handle h, int base_map_id, int query_map_id, const int64
   RJ_HIP(h, ev.mark(1, h->stream));
   RJ_HIP(h, launch_nearest(h->stream, a, h->stats_on != 0, h->debug_nearest_blocks, h->cus));
   RJ_HIP(h, ev.mark(2, h->stream));
-  // (a caller's array: the estimate that the next query over it goes by, as behind a PIP query)
-  if (h->cur_caller >= 0) {
-    const rj_handle_s::CallerSet& e = h->caller[h->cur_caller];
-    if (e.queries <= 2 || e.queries % 4 == 0) RJ_HIP(h, launch_group_extent_tail(h->stream, pts, h->cur_order, n, h->d_est + h->cur_caller));
-  }
+  if (int r = estimate_distance_points(h, pts, n)) return r;
   if (h->stats_on) RJ_HIP(h, hipMemcpyAsync(h->h_pinned + 1, h->d_stats, 128, hipMemcpyDeviceToHost, h->stream));
   RJ_HIP(h, hipStreamSynchronize(h->stream));
   ev.times(2, h->nearest_report.ms);
@@ -2366,6 +2383,73 @@ int rj_nearest_query(rj_handle h, int base_map_id, int query_map_id, const int64
     h->h_fault[kFaultNearestStack] = 0;
     return fail(h, RJ_E_INTERNAL, "traversal stack overflow in k_nearest: results are incomplete");
   }
+  return RJ_OK;
+}
+
+// ---- every edge of the base map within a distance of each point (rj_within.h, rj_within.hip) --------------------------------
+int rj_within_query(rj_handle h, int base_map_id, int query_map_id, const int64_t* pts_dev, uint64_t pt_begin, uint64_t n, int64_t max_dist,
+                    uint64_t pair_capacity, uint64_t* offsets_dev, uint32_t* eid_dev, rj_near* rec_dev, double* dist_dev, rj_within_counts* counts) {
+  static_assert(sizeof(rj_within_counts) == sizeof(within::Counts), "layouts");
+  RJ_CHECK_H(h);
+  h->within_report = StageMs{};
+  if (base_map_id < 0 || base_map_id > 1 || query_map_id != 1 - base_map_id)
+    return fail(h, RJ_E_INVALID, "rj_within_query: base/query map ids must be {0,1} and differ");
+  if (!h->bvh[base_map_id].built) return fail(h, RJ_E_INVALID, "rj_within_query: call rj_build_lbvh(base map) first");
+  if (!counts) return fail(h, RJ_E_INVALID, "rj_within_query: counts is null");
+  if (pair_capacity && !eid_dev) return fail(h, RJ_E_INVALID, "rj_within_query: pair_capacity without eid_dev");
+  if (max_dist < 0 || max_dist > nearest::kMaxDist) return fail(h, RJ_E_INVALID, "rj_within_query: max_dist must lie in [0, 2^48]");
+  const int64_t* pts = pts_dev;
+  uint64_t coh_begin = 0;
+  if (!pts) {
+    coh_begin = pt_begin;
+    const MapState& q = h->map[query_map_id];
+    if (!q.present || pt_begin + n > q.np || pt_begin + n < pt_begin) return fail(h, RJ_E_INVALID, "rj_within_query: bad point range of the query map");
+    pts = q.pts + 2 * pt_begin;
+  }
+  if (n >= within::kMaxPoints || pair_capacity >= within::kMaxPoints) return fail(h, RJ_E_INVALID, "rj_within_query: n < 2^32 and pair_capacity < 2^32");
+  if (int r = set_device(h)) return r;
+  memset(counts, 0, sizeof(*counts));
+  if (n == 0) {
+    if (offsets_dev) {
+      RJ_HIP(h, hipMemsetAsync(offsets_dev, 0, sizeof(uint64_t), h->stream));
+      RJ_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return RJ_OK;
+  }
+  StageEvents ev;
+  RJ_HIP(h, ev.create());
+  RJ_HIP(h, ev.mark(0, h->stream));
+  const uint32_t* order = nullptr;
+  if (int r = order_distance_points(h, pts, pts_dev != nullptr, query_map_id, coh_begin, n, &order)) return r;
+  if (int r = estimate_distance_points(h, pts, n)) return r;
+  if (h->stats_on) RJ_HIP(h, hipMemsetAsync(h->d_stats, 0, 128, h->stream));
+  WithinArgs a;
+  a.bvh = bvh_view(h->bvh[base_map_id]);
+  a.seg = h->map[base_map_id].seg;
+  a.pts = pts; a.n = n; a.order = order;
+  a.max_dist = max_dist;
+  a.capacity = pair_capacity;
+  a.offsets = offsets_dev;
+  a.eid = eid_dev; a.rec = reinterpret_cast<nearest::Near*>(rec_dev); a.dist = dist_dev;
+  a.fault = h->d_fault;
+  a.stats = h->stats_on ? h->d_stats : nullptr;
+  a.stack_cap = h->debug_stack_cap;
+  WithinResult res;
+  RJ_HIP(h, within_device(h->stream, a, h->stats_on != 0, h->debug_within_blocks, h->cus, &ev, &res));
+  if (h->stats_on) {
+    RJ_HIP(h, hipMemcpy(h->h_pinned + 1, h->d_stats, 128, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 16; i++) h->last_stats[i] = h->h_pinned[1 + i];
+  }
+  if (h->h_fault[kFaultWithinStack]) {
+    h->h_fault[kFaultWithinStack] = 0;
+    return fail(h, RJ_E_INTERNAL, "traversal stack overflow in k_within: results are incomplete");
+  }
+  if (res.appended != res.counts.n_pairs)
+    return fail(h, RJ_E_INTERNAL, "rj_within_query: %llu pairs appended, %llu counted", (unsigned long long) res.appended, (unsigned long long) res.counts.n_pairs);
+  ev.times(3, h->within_report.ms);
+  memcpy(counts, &res.counts, sizeof(*counts));
+  if (pair_capacity && !res.emitted)
+    return fail(h, RJ_E_OVERFLOW, "rj_within_query: %llu pairs; capacity %llu", (unsigned long long) counts->n_pairs, (unsigned long long) pair_capacity);
   return RJ_OK;
 }
 

@@ -64,6 +64,10 @@
   NearestLBVH(ctx).Init(n_points); .Query(query_map_id, query_points, max_dist=); .get_eids(); .get_records(); .get_dist()
       -- the nearest edge of the indexed map for every point and its exact distance (rj_nearest_query): Near, sjoin_nearest,
          the join within a distance
+  WithinLBVH(ctx).Init(n_points, pair_capacity); .Query(query_map_id, query_points, max_dist=, grow=); .Count(...); .get_offsets();
+      .get_eids(); .get_records(); .get_dist(); .to_csr(); .counts()
+      -- every edge of the indexed map within max_dist of each point, as a CSR over the points (rj_within_query): dwithin,
+         Select by distance, Generate Near Table (all)
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -320,6 +324,120 @@ class NearestLBVH:
             if b is not None:
                 b.free()
         self.eids = self.records = self.dist = None
+
+
+class WithinLBVH:
+    """Every edge of the indexed base map within max_dist of each query point (rj_within_query), mirroring NearestLBVH: a
+    CSR over the points -- offsets, and per pair the eid (ascending per point), the exact record and the distance."""
+
+    def __init__(self, dctx):
+        self.ctx_ = dctx
+        self.h = dctx.handle
+        self.offsets = self.eids = self.records = self.dist = None
+        self.n = self.n_pairs = 0
+        self.n_alloc = self.capacity = 0
+        self.has_records = self.has_dist = False
+        self.counts_ = dict.fromkeys(_capi.WITHIN_COUNTS, 0)
+
+    def Init(self, n_points, pair_capacity):
+        self.free()
+        self.n_alloc = int(n_points)
+        self.offsets = self.h.alloc(8 * (self.n_alloc + 1))
+        self._alloc_pairs(int(pair_capacity))
+
+    def _alloc_pairs(self, capacity):
+        for b in (self.eids, self.records, self.dist):
+            if b is not None:
+                b.free()
+        self.capacity = capacity
+        self.eids = self.h.alloc(4 * max(1, capacity))
+        self.records = self.h.alloc(_capi.NEAR_DTYPE.itemsize * max(1, capacity))
+        self.dist = self.h.alloc(8 * max(1, capacity))
+
+    def _call(self, query_map_id, query_points, point_range, max_dist, capacity, rec, dst):
+        base = 1 - query_map_id
+        eids = self.eids if capacity else None
+        if query_points is not None:
+            pts = np.ascontiguousarray(query_points, dtype=np.int64).reshape(-1, 2)
+            n = pts.shape[0]
+            assert n <= self.n_alloc
+            buf = self.h.alloc(16 * max(1, n)).from_host(pts)
+            try:
+                return n, self.h.within_query(base, query_map_id, buf, 0, n, max_dist, capacity, self.offsets, eids, rec, dst)
+            finally:
+                buf.free()
+        b, e = point_range if point_range is not None else (0, self.ctx_.get_map(query_map_id).n_points)
+        n = e - b
+        assert n <= self.n_alloc
+        return n, self.h.within_query(base, query_map_id, None, b, n, max_dist, capacity, self.offsets, eids, rec, dst)
+
+    def Query(self, query_map_id, query_points=None, point_range=None, max_dist=0, records=True, dist=True, grow=True):
+        """query_points: int64[n,2] scaled host points, or None for the query map's own vertices, optionally a [begin, end)
+        sub-range (a shard).  max_dist (scaled units, 0 .. 2^48): every edge with d <= max_dist is listed.  records / dist:
+        whether the call fills them.  grow: on an overflow (or with a capacity of 0) the pair arrays are allocated again at
+        the true count and the call repeats once; otherwise _capi.WithinOverflow with the true counts.  Returns n_pairs."""
+        self.n_pairs = 0
+        self.has_records = self.has_dist = False
+        args = (query_map_id, query_points, point_range, int(max_dist))
+        if self.capacity == 0:  # (a capacity of 0 is the counting call: it sizes the arrays)
+            n, counts = self._call(*args, 0, None, None)
+            if counts["n_pairs"] and not grow:
+                raise _capi.WithinOverflow("rj_within_query: %d pairs; capacity 0" % counts["n_pairs"], counts)
+            if counts["n_pairs"]:
+                self._alloc_pairs(counts["n_pairs"])
+        if self.capacity:
+            try:
+                n, counts = self._call(*args, self.capacity, self.records if records else None, self.dist if dist else None)
+            except _capi.WithinOverflow as e:
+                if not grow:
+                    raise
+                self._alloc_pairs(e.counts["n_pairs"])
+                n, counts = self._call(*args, self.capacity, self.records if records else None, self.dist if dist else None)
+        self.n, self.n_pairs, self.counts_ = n, counts["n_pairs"], counts
+        self.has_records, self.has_dist = bool(records), bool(dist)
+        return self.n_pairs
+
+    def Count(self, query_map_id, query_points=None, point_range=None, max_dist=0):
+        """the counting call: how many edges lie within max_dist of each point -> uint64[n]; nothing but the offsets and the
+        counts is written"""
+        n, counts = self._call(query_map_id, query_points, point_range, int(max_dist), 0, None, None)
+        self.n, self.n_pairs, self.counts_ = n, 0, counts
+        self.has_records = self.has_dist = False
+        return np.diff(self.get_offsets())
+
+    def get_offsets(self):
+        return self.offsets.to_host(np.uint64, self.n + 1)
+
+    def get_eids(self):
+        return self.eids.to_host(np.uint32, self.n_pairs)
+
+    def get_records(self):
+        """-> NEAR_DTYPE rows, one per pair; ValueError after a Query with records=False"""
+        if not self.has_records:
+            raise ValueError("the last Query ran with records=False")
+        return self.records.to_host(_capi.NEAR_DTYPE, self.n_pairs)
+
+    def get_dist(self):
+        if not self.has_dist:
+            raise ValueError("the last Query ran with dist=False")
+        return self.dist.to_host(np.float64, self.n_pairs)
+
+    def to_csr(self):
+        """-> (indptr int64[n + 1], eids uint32[n_pairs]): row i lists the edges within the distance of point i, ascending"""
+        return self.get_offsets().astype(np.int64), self.get_eids()
+
+    def counts(self):
+        """the counts of the last call: n_pairs, n_points_hit, max_per_point"""
+        return dict(self.counts_)
+
+    exact = staticmethod(NearestLBVH.exact)
+
+    def free(self):
+        for b in (self.offsets, self.eids, self.records, self.dist):
+            if b is not None:
+                b.free()
+        self.offsets = self.eids = self.records = self.dist = None
+        self.capacity = 0
 
 
 class LSIGrid(LSILBVH):

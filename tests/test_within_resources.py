@@ -1,0 +1,39 @@
+"""k_within, the traversal of rj_within_query, keeps a point, a candidate -- two 128-bit integers -- and the wide compare's
+limbs in registers: no scratch memory and at most 128 VGPRs, in either instantiation, like k_nearest.  Read from the resource
+report of the build (`make` writes rayjoin_amd/csrc/resource_usage_within.txt: -Rpass-analysis=kernel-resource-usage)."""
+import os
+import re
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPORT = os.path.join(os.path.dirname(HERE), "rayjoin_amd", "csrc", "resource_usage_within.txt")
+
+
+def kernels():
+    assert os.path.exists(REPORT), "no resource report: build the library first (__graft_entry__.build)"
+    out, name = {}, None
+    for line in open(REPORT):
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            out[name] = {}
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
+        if m and name:
+            out[name][m.group(1).strip()] = int(m.group(2))
+    return out
+
+
+def test_the_traversal_kernel_uses_no_scratch():
+    hits = {k: v for k, v in kernels().items() if re.search(r"k_withinILb[01]E", k)}
+    assert len(hits) == 2, sorted(kernels())  # the plain and the instrumented kernel
+    for name, r in hits.items():
+        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0, "%s: %d VGPRs, %s" % (name, r["VGPRs"], r)
+        assert 0 < r["VGPRs"] <= 128, "%s: %d VGPRs (above 128 a SIMD holds fewer than four waves)" % (name, r["VGPRs"])
+        assert r["LDS Size"] <= 32768, "%s: %d VGPRs, %d bytes of LDS" % (name, r["VGPRs"], r["LDS Size"])
+
+
+def test_the_other_kernels_use_no_scratch():
+    rest = {k: v for k, v in kernels().items() if "k_within_" in k}
+    assert len(rest) == 2, sorted(kernels())  # the totals and the outputs
+    for name, r in rest.items():
+        assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0, (name, r)
