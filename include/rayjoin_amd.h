@@ -1183,6 +1183,12 @@ int rj_last_stats(rj_handle h, uint64_t stats[16]);
  * "own_stream"       1                        back to the handle's private stream (see rj_set_stream).
  * A new handle takes the defaults of six from the environment (A/B runs; a value the option refuses keeps the default):
  * RJ_LEAF_ORDER, RJ_LEAF_YSORT, RJ_PIP_COLUMNS, RJ_LSI_SEGMENTS, RJ_WALK_POINTS ("pip_walk_points"), RJ_POINTS_SPLIT ("lsi_points_split").
+ * One more has no option behind it: RJ_WALK_SETS = 2 or 3, the 64-position sets a wave of the two-per-lane walk family
+ * takes where the walk reads the query map's prepared points beside an LSI query in flight ("pip_concurrent", schedules
+ * "shared" and "full grids"; from four 192-position groups per resident wave on).  3: k_pip_walk3_prepared -- 192
+ * positions per traversal, five list slots per point and a stack of 76 in the same registers and LDS; 2: k_pip_walk2's
+ * 128 everywhere; anything else: the handle's own rule -- see "pip_last_walk_sets".  Caller-owned arrays, re-ordered
+ * sets, the instrumented kernel and every query that runs alone take two sets whatever it says.
  *
  * rj_get_option reads any of these, and what the handle did or decided:
  *   "leaf_order_used0/1", "leaf_slots0/1", "leaf_runs0/1", "skyline_used0/1", "closed_chains0/1",
@@ -1192,10 +1198,16 @@ int rj_last_stats(rj_handle h, uint64_t stats[16]);
  *   "pip_schedule" (0 turns, 1 shared, 2 full grids, -1 still trying), "pip_schedule_trials", "pip_schedule_us0/1/2",
  *   "lsi_share_blocks", "pip_share_blocks"                      what "pip_concurrent" 2 measured and settled on
  *   "lsi_last_segments", "pip_last_walk_points", "pip_last_passes", "lsi_points_last_split", "lsi_points_gcd_pairs",
- *   "pip_rest", "pip_rest_aux", "query_last_ordered", "pip_last_columns", "pip_last_prepared"   what the last query ran
+ *   "pip_rest", "pip_rest_aux", "query_last_ordered", "pip_last_columns", "pip_last_prepared",
+ *   "pip_last_walk_sets"                                        what the last query ran
  *     ("pip_last_prepared": what the walk read -- 0 the int64 points, 1 the query map's prepared points with a computed
  *     extent per group, 2 prepared points and prepared extents: a range of the query map's own vertices, in their own
- *     order, through k_pip_walk2; extents where pt_begin is a multiple of 64)
+ *     order, through k_pip_walk2; extents where pt_begin is a multiple of 64.
+ *     "pip_last_walk_sets": 2 or 3, the 64-position sets per wave of the last walk of the k_pip_walk2 family -- see
+ *     RJ_WALK_SETS above; left to itself the handle takes the sets RJ_WALK_SETS' default names and goes back to two for
+ *     the rest of the epoch when a three-set query leaves far more points to the rest list than two sets did, which
+ *     rj_get_plan then says why.  "pip_last_walk_points" is 2 for either, and the plan's first pass names the family,
+ *     k_pip_walk2, with the sets beside it)
  *   "comm_ranks"                                                the ranks RCCL counts in the handle's communicator (0: none) */
 int rj_set_option(rj_handle h, const char* name, int64_t value);
 int rj_get_option(rj_handle h, const char* name, int64_t* value);

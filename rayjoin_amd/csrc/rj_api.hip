@@ -184,6 +184,19 @@ struct rj_handle_s {
   // PIP in two passes (rj_kernels.hip, k_pip_walk): the integer-only walk settles what it can, k_pip takes the rest
   int pip_walk = 1;                        // "pip_walk": 1 auto (default), 0 k_pip alone, 2 always both passes
   int last_walk_points = 1;                // ... and how many points a lane of its walk took
+  // Three 64-position sets per wave (k_pip_walk3_prepared) where the walk shares the chip with an LSI query in flight and
+  // reads the query map's prepared points; two everywhere else.  RJ_WALK_SETS (read at rj_create): 2 never, 3 always where
+  // it applies, anything else auto -- three, until a three-set query leaves far more points to the rest list than the
+  // two-set form of the same query did (five list slots and a 76-entry stack against six and 124): then two for the rest
+  // of the epoch, and rj_get_plan says so.
+  int walk_sets = 0;                       // RJ_WALK_SETS: 0 auto, 2, 3
+  int last_walk_sets = 2;                  // "pip_last_walk_sets": sets per wave of the last many-position walk
+  // (a three-set walk reports its rest count in a host word of its own, h_rest[kRest3Word]: a count arrives some time after
+  //  its query was launched, and in a pipelined loop the word of the two-set queries would otherwise hold either form's)
+  static constexpr int kRest3Word = 5;
+  uint64_t walk_n3 = 0;                    // size of the three-set query that word's count belongs to
+  int rest_sets_aux = 2;                   // sets of the last walk on the second stream: which word "pip_rest_aux" reads
+  uint64_t walk3_off_epoch = ~0ull;        // the epoch that went back to two sets
   int last_prepared = 0;                   // ... and what it read: 0 the int64 points, 1 the query map's prepared points, 2 and its prepared extents
   int last_passes = 0;                     // kernels of the last PIP query (3 or 1)
   int flip_walk[2] = {0, 0};
@@ -369,6 +382,7 @@ struct rj_handle_s {
       LaunchNote first = {"", 0, 0};
       int passes = 0, order = 0, exact_blocks = 0, locate_blocks = 0;
       int prepared = 0;  // "pip_last_prepared" of that query
+      int sets = 0;      // 64-position sets per wave of its many-position walk (0: another first pass)
       const char* why = "";
     } pip;
   } plan;
@@ -721,13 +735,14 @@ const Report kReports[] = {
     {"pip_schedule_us", 3, RJ_READ(h->co_best[k] < 1e29f ? (int64_t) (h->co_best[k] * 1000.0f) : -1)},  // best span seen per schedule, microseconds (-1: not measured)
     {"lsi_last_segments", 0, RJ_READ(h->last_lsi_segments)},
     {"pip_last_walk_points", 0, RJ_READ(h->last_walk_points)},
+    {"pip_last_walk_sets", 0, RJ_READ(h->last_walk_sets)},  // 64-position sets per wave of the last many-position walk: 2, or 3 (k_pip_walk3_prepared)
     {"pip_last_prepared", 0, RJ_READ(h->last_prepared)},
     {"lsi_points_last_split", 0, RJ_READ(h->last_points_split)},
     {"lsi_points_gcd_pairs", 0, read_gcd_pairs},
     {"pip_last_passes", 0, RJ_READ(h->last_passes)},  // how the last PIP query ran: 3 = walk + exact + k_pip, 1 = k_pip alone
     {"pip_last_columns", 0, RJ_READ(h->last_columns)},
     {"pip_rest", 0, RJ_READ(h->h_rest[0])},  // points the last finished two-pass query on the main stream left to k_pip (-1: none yet)
-    {"pip_rest_aux", 0, RJ_READ(h->h_rest[1])},
+    {"pip_rest_aux", 0, RJ_READ(h->h_rest[h->rest_sets_aux == 3 ? rj_handle_s::kRest3Word : 1])},
     {"leaf_order_used", 2, RJ_READ(h->bvh[k].leaf_order)},  // what the index of map k was built with
     {"leaf_slots", 2, RJ_READ(h->bvh[k].n0p)},              // slots of the index of map k (64 per leaf, padding included)
     {"leaf_runs", 2, RJ_READ(h->map[k].runs_cut ? (int64_t) h->map[k].nruns : -1)},  // polyline runs cut for map k (-1: none cut)
@@ -854,6 +869,7 @@ int rj_create(int device_id, rj_handle* out) {
   for (const Option& o : kOptions)  // (A/B runs)
     if (const char* e = o.env ? getenv(o.env) : nullptr)
       if (o.accepts(atoi(e))) h->*o.field = atoi(e);
+  if (const char* e = getenv("RJ_WALK_SETS")) { const int v = atoi(e); h->walk_sets = v == 2 || v == 3 ? v : 0; }
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) h->cus = prop.multiProcessorCount;
@@ -883,6 +899,7 @@ int rj_create(int device_id, rj_handle* out) {
     h->h_fault[0] = h->h_fault[1] = h->h_fault[kFaultNearestStack] = h->h_fault[kFaultWithinStack] = 0;
     h->h_rest[0] = h->h_rest[1] = ~0ull;  // (no finished two-pass query yet)
     h->h_rest[2] = ~0ull;                 // (... and no records produced yet: k_lsi_points' pair count)
+    h->h_rest[rj_handle_s::kRest3Word] = ~0ull;
     for (int k = 0; k < rj_handle_s::kCallerSets; k++) h->h_est[k] = 0;
     ok = hipMemset(h->d_counter, 0, kCounterBytes) == hipSuccess;
     for (size_t blk : {kSchedLsi, kSchedLsi + kSchedBlockWords, kSchedPipMain, kSchedPipMain + kSchedBlockWords, kSchedPipAux,
@@ -1040,10 +1057,10 @@ int rj_get_plan(rj_handle h, char* buf, size_t cap, size_t* need) {
   }
   if (P.pip.ran) {
     add(", \"pip\": {\"epoch\": %llu, \"current\": %s, \"points\": %llu, \"points_from\": \"%s\", \"stream\": \"%s\", \"on_shared_grid\": %s, \"order\": \"%s\", "
-        "\"passes\": %d, \"first_pass\": {\"kernel\": \"%s\", \"blocks\": %d, \"points_per_lane\": %d}, \"prepared_points\": %d",
+        "\"passes\": %d, \"first_pass\": {\"kernel\": \"%s\", \"blocks\": %d, \"points_per_lane\": %d, \"sets\": %d}, \"prepared_points\": %d",
         (unsigned long long) P.pip.epoch, P.pip.epoch == P.epoch ? "true" : "false", (unsigned long long) P.pip.n, P.pip.caller ? "a caller-owned array" : "the query map's vertices",
         P.pip.aux ? "second (beside the LSI query)" : "main", P.pip.shared ? "true" : "false", kOrder[P.pip.order], P.pip.passes, P.pip.first.kernel, P.pip.first.grid,
-        P.pip.first.per_lane, P.pip.prepared);
+        P.pip.first.per_lane, P.pip.sets, P.pip.prepared);
     if (P.pip.passes == 3)
       add(", \"second_pass\": {\"kernel\": \"k_pip_exact\", \"blocks\": %d, \"locate_blocks\": %d}, \"left_over_by_last_query_of_this_size\": %lld", P.pip.exact_blocks,
           P.pip.locate_blocks, P.pip.rest_hint == ~0ull ? -1ll : (long long) P.pip.rest_hint);
@@ -1083,7 +1100,7 @@ static int begin_upload(rj_handle h, int map_id) {
   RJ_HIP(h, join_aux(h));
   co_reset(h);
   h->h_rest[0] = h->h_rest[1] = ~0ull;  // (what the last walk over another map left to k_pip says nothing about this one)
-  h->walk_n[0] = h->walk_n[1] = 0;
+  h->walk_n[0] = h->walk_n[1] = 0; h->h_rest[rj_handle_s::kRest3Word] = ~0ull; h->walk_n3 = 0;
   return RJ_OK;
 }
 
@@ -1643,7 +1660,7 @@ int rj_build_lbvh(rj_handle h, int base_map_id) {
   b.built = true;
   co_reset(h);
   h->h_rest[0] = h->h_rest[1] = ~0ull;  // (a new index: the "auto" decision to drop the walk is taken again)
-  h->walk_n[0] = h->walk_n[1] = 0;
+  h->walk_n[0] = h->walk_n[1] = 0; h->h_rest[rj_handle_s::kRest3Word] = ~0ull; h->walk_n3 = 0;
   return RJ_OK;
 }
 
@@ -2037,7 +2054,7 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
         co_reset(h);
         h->plan.epoch++;
         h->h_rest[0] = h->h_rest[1] = ~0ull;
-        h->walk_n[0] = h->walk_n[1] = 0;
+        h->walk_n[0] = h->walk_n[1] = 0; h->h_rest[rj_handle_s::kRest3Word] = ~0ull; h->walk_n3 = 0;
         h->last_ordered = false; h->order_fresh = false; h->cur_caller = -1; h->cur_order = nullptr;
       } else if (int r = maybe_order_queries(h, true, pts, nullptr, 0, n, &order, pts_dev ? -1 : query_map_id, coh_begin)) {
         return r;  // (no index after all -- a segment too wide, no memory: the permutation, as before)
@@ -2121,12 +2138,25 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
   const int si = aux ? 1 : 0;
   // (instrumented: k_pip alone, unless "pip_walk" 2 asks for the walk's own counters)
   bool walk = h->pip_walk != 0 && (!h->stats_on || h->pip_walk == 2) && n > 0 && n < (1ull << 32);
-  // how many points the last two-pass query of this size left to k_pip (either stream: the count belongs to the query)
+  // how many points the last two-pass query of this size left to k_pip (either stream: the count belongs to the query);
+  // from two-set and one-per-lane walks here, from three-set walks in `seen3`
   uint64_t seen = ~0ull;
   for (int k : {si, 1 - si})
     if (seen == ~0ull && h->walk_n[k] == n && h->h_rest[k] != ~0ull) {
       seen = h->h_rest[k];
     }
+  const uint64_t seen3 = h->walk_n3 == n ? (uint64_t) h->h_rest[rj_handle_s::kRest3Word] : ~0ull;
+  // Three sets left `seen3`: how many of them are the shorter lists' and stack's doing?  Every such point is located from
+  // scratch by the exact kernel's first blocks, one scattered handful per wave, at the very end of the PIP chain.  Measured
+  // on the full-size pairs (profiles/r08_rest_counts.txt, r08_ab_sets_*.txt): USCounty x BlockGroup 15 -> 33 points, the
+  // step 2.8 % shorter; x NestedBlockGroup 5 530 -> 14 496, the walk 1.6 % shorter and the step 0.6 % LONGER; x
+  // CrossingZipcode 1 422 -> 5 954, the walk 1.3 % shorter and the step 3.9 % longer -- 4.5 k more points cost 30 us where
+  // the walk gained 9.  So: more than kWalk3RestSlack points above the two-set count of the same query (the "turns" trial
+  // and every query that runs alone leave one, and it stays while three sets run; none known: above nothing) sends the
+  // epoch back to two sets.  The rule below, which drops the first pass altogether, goes by the two-set count alone.
+  constexpr uint64_t kWalk3RestSlack = 2048;
+  if (seen3 != ~0ull && h->walk_sets == 0 && h->walk3_off_epoch != h->plan.epoch && seen3 > (seen != ~0ull ? seen : 0) + kWalk3RestSlack)
+    h->walk3_off_epoch = h->plan.epoch;
   // "auto" drops the first pass where it does not pay: most points left over, or many overflowed lists in absolute
   // terms -- k_pip locates those one scattered handful per wave (the list is in no useful order), which on the gaussian
   // polygons (25 k of 8 M) costs more than the walk saves
@@ -2162,6 +2192,7 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
   h->last_passes = walk ? 3 : 1;
   h->last_walk_points = 1;
   h->last_prepared = 0;
+  int walk_sets_now = 2;
   tic(h, RJ_T_PIP_KERNEL, st);
   if (n && walk) {
     const int wflip = h->flip_walk[si];
@@ -2211,8 +2242,18 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
         h->last_prepared = 1;
         if (pt_begin % 64 == 0) { w.qext = q.qext + pt_begin / 64; h->last_prepared = 2; }
       }
-      RJ_HIP(h, launch_pip_walk2(st, w, walk_blocks, h->cus, h->stats_on));
+      // three sets per wave: a prepared range in a pair that shares the chip ("shared", or "beside" on full grids), from four
+      // 192-position groups per resident wave on
+      const bool in_pair = aux && h->lsi_inflight && (h->lsi_shared || h->co_mode == 2);
+      const int grid_cap = walk_blocks < h->cus * pip_walk2_blocks_per_cu(w.bvh.top, 3) ? walk_blocks : h->cus * pip_walk2_blocks_per_cu(w.bvh.top, 3);
+      const bool three = h->walk_sets != 2 && w.qpts && in_pair && (h->walk_sets == 3 || h->walk3_off_epoch != h->plan.epoch) &&
+                         n >= (uint64_t) 192 * 4 * 4 * (uint64_t) (grid_cap > 0 ? grid_cap : 1);
+      RJ_HIP(h, launch_pip_walk2(st, w, walk_blocks, h->cus, h->stats_on, three ? 3 : 2));
       h->last_walk_points = 2;
+      h->last_walk_sets = three ? 3 : 2;
+      walk_sets_now = h->last_walk_sets;
+      if (!three && w.qpts && in_pair && h->walk_sets == 0 && h->walk3_off_epoch == h->plan.epoch)
+        why = "two sets per wave: three left far more points to the rest list than two on this pair (five list slots, a stack of 76)";
     } else {
       RJ_HIP(h, launch_pip_walk(st, w, h->stats_on, walk_blocks));
     }
@@ -2224,23 +2265,27 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
     // over the points whose list overflowed; that part's grid follows the last count seen for this query size
     // (the list is appended group by group all over the map: the fewer points it holds, the less a wave's points have
     //  to do with each other -- a handful of overflowed lists are unrelated traversals, one wave each)
-    const uint64_t left = seen != ~0ull ? seen : 8192;
+    // (what a walk like this one left the last time; the first three-set query of a size goes by the two-set count: the
+    //  grid of a schedule's first shared trial must not differ from the settled steps' for want of a count)
+    const uint64_t hint = walk_sets_now == 3 && seen3 != ~0ull ? seen3 : seen;
+    const uint64_t left = hint != ~0ull ? hint : 8192;
     PipRestArgs r;
     r.order = h->rest[li];
     r.n_dev = w.rest_count;
-    r.rest_count = h->d_rest + si;  // (the count goes to the host)
+    r.rest_count = h->d_rest + (walk_sets_now == 3 ? rj_handle_s::kRest3Word : si);  // (the count goes to the host)
     r.work_counter = a.work_counter;
     r.next_work_counter = a.next_work_counter;
     r.group_lanes = left < 8192 ? 1 : (left * 100 < n ? 4 : (left * 10 < n ? 8 : 16));
     r.chunk_groups = 1;
     int rest_blocks = h->cus * 4;
-    if (seen != ~0ull) {
-      const uint64_t want = seen / (r.group_lanes * 4 * 2) + 1;  // about two groups per wave
+    if (hint != ~0ull) {
+      const uint64_t want = hint / (r.group_lanes * 4 * 2) + 1;  // about two groups per wave
       const uint64_t lo = (uint64_t) h->cus / 4, hi = (uint64_t) h->cus * 4;  // (at least a block per four CUs: the count is a hint)
       rest_blocks = (int) (want < lo ? lo : (want > hi ? hi : want));
     }
     r.blocks = (uint32_t) rest_blocks;
-    h->walk_n[si] = n;
+    if (walk_sets_now == 3) h->walk_n3 = n; else h->walk_n[si] = n;
+    if (si) h->rest_sets_aux = walk_sets_now;
     if (own) {
       RJ_HIP(h, hipEventRecord(h->ev_walk_done, st));
       RJ_HIP(h, hipStreamWaitEvent(h->exact_stream, h->ev_walk_done, 0));
@@ -2269,9 +2314,10 @@ int rj_pip_query_async(rj_handle h, int base_map_id, int query_map_id, const int
   {
     rj_handle_s::PlanRec::Pip& pp = h->plan.pip;
     pp.ran = n > 0; pp.epoch = h->plan.epoch; pp.n = n; pp.aux = aux; pp.caller = pts_dev != nullptr;
-    pp.shared = aux && h->lsi_shared; pp.passes = h->last_passes; pp.rest_hint = seen; pp.why = why;
+    pp.shared = aux && h->lsi_shared; pp.passes = h->last_passes; pp.rest_hint = walk_sets_now == 3 && seen3 != ~0ull ? seen3 : seen; pp.why = why;
     pp.order = order ? (h->order_fresh ? 2 : 1) : 0;
     pp.prepared = h->last_prepared;
+    pp.sets = walk && h->last_walk_points == 2 ? h->last_walk_sets : 0;
   }
   toc(h, RJ_T_PIP_KERNEL, own ? h->exact_stream : st);
   // a caller-owned array: the estimate the next query over it will go by, behind this query's kernels on their stream

@@ -72,7 +72,7 @@ struct PipArgs {
   unsigned long long* rest_count;        // (walk) zero when the kernel starts; (k_pip) nullable: where it reports the count it found
   unsigned long long* next_rest_count;   // (walk) the next walk's counter on this stream: cleared by this walk
   const unsigned long long* n_dev;       // (k_pip only) nullable: process min(n, *n_dev) queries
-  // k_pip_walk2 only, both nullable: what the query map's upload prepared (launch_prepare_points), offset to the first
+  // k_pip_walk2 and k_pip_walk3_prepared only, both nullable: what the query map's upload prepared (launch_prepare_points), offset to the first
   // point like `pts`.  qpts: {quant(x), quant(y)} per point -- the walk reads these 8 bytes instead of 16 and quantises
   // nothing.  qext: {min x, max x, min y, 0} of every 64 positions -- a group's extent is two scalar loads instead of a
   // wave reduction (only where the first point is a multiple of 64; requires qpts and order == nullptr)
@@ -183,9 +183,10 @@ hipError_t launch_lsi_points(hipStream_t st, const Seg* seg0, const Seg* seg1, c
                              unsigned long long* count_hint);
 hipError_t launch_pip(hipStream_t st, const PipArgs& a, bool stats, int max_blocks);
 hipError_t launch_pip_walk(hipStream_t st, const PipArgs& a, bool stats, int max_blocks);
-hipError_t launch_pip_walk2(hipStream_t st, const PipArgs& a, int max_blocks, int cus, bool stats = false);
-int pip_walk2_blocks_per_cu(int top);
-int pip_walk2_blocks_beside(int top, int lsi_blocks_per_cu);
+// sets: 64-position sets per wave -- 2, or 3 (k_pip_walk3_prepared: prepared points only; anything it cannot take runs with 2)
+hipError_t launch_pip_walk2(hipStream_t st, const PipArgs& a, int max_blocks, int cus, bool stats = false, int sets = 2);
+int pip_walk2_blocks_per_cu(int top, int sets = 2);
+int pip_walk2_blocks_beside(int top, int lsi_blocks_per_cu, int sets = 2);
 hipError_t launch_pip_exact(hipStream_t st, const PipArgs& a, int blocks, const PipRestArgs& r);
 int pip_walk_list_slots();  // candidates a todo record holds
 uint32_t pip_walk_group_lanes(uint64_t n, int top, int cus);  // points per wave k_pip_walk uses when the caller leaves it open

@@ -2039,24 +2039,47 @@ __global__ __launch_bounds__(256, 8) void k_pip_walk(PipArgs A) {
 // of whose lanes wants a leaf block skips it (wave-uniform).  Same stack, twice the candidate lists; the hand-over
 // (one todo slot per position, one mask per 64 positions, the rest list) is exactly k_pip_walk's, so k_pip_exact
 // cannot tell the two apart.  Requires group_lanes == 64 (a large query set).
-// (the body takes P points per lane; only P = 2 is built -- four per lane measured slower)
-__host__ __device__ __forceinline__ size_t walk2_wave_lds(int top, int P = 2) { return (size_t) 16 * walk_stack_entries(top) + (size_t) kWalkList * 256 * P; }
+// (the body takes P points per lane; P = 2 is built, and P = 3 over prepared points with shorter lists and stack --
+//  four per lane measured slower)
+// (three per lane: k_pip_walk3_prepared, with LIST = kWalk3List slots per point and a stack of at most kWalk3Stack entries,
+//  which is exactly the LDS of two per lane -- 3 x 5 x 256 + 16 x 76 = 2 x 6 x 256 + 16 x 124 bytes per wave)
+constexpr int kWalk3List = 5;
+constexpr int kWalk3Stack = 76;
+static_assert(3 * kWalk3List * 256 + 16 * kWalk3Stack == 2 * kWalkList * 256 + 16 * kWalkStack, "k_pip_walk3_prepared: the LDS of k_pip_walk2, to the byte");
+static_assert(kWalk3List <= kWalkList, "a todo record has kWalkList slots");
+__host__ __device__ __forceinline__ int walk2_stack_entries(int top, int stack_max = kWalkStack) {
+  const int e = walk_stack_entries(top);
+  return e < stack_max ? e : stack_max;
+}
+__host__ __device__ __forceinline__ size_t walk2_wave_lds(int top, int P = 2, int list = kWalkList, int stack_max = kWalkStack) {
+  return (size_t) 16 * walk2_stack_entries(top, stack_max) + (size_t) list * 256 * P;
+}
 
 // (96 SGPRs: above that the hardware admits one block per CU fewer than the occupancy query reports, and the shared
 //  schedule's walk + k_lsi2 blocks per CU no longer fit -- the skyline pointer took it to 100: 0.785 -> 0.852 ms.
 //  256 threads x 9 blocks: the compiler then aims below 57 VGPRs -- at 56, six blocks fit beside two of k_lsi2's 80)
 constexpr int kWalkCycleStamps = 7777;  // "stack_cap" value that turns the instrumented walk's counters into cycle stamps (tools/walk_stats_probe.py --cycles)
-template <bool STATS, int P, bool PREP = false>
+template <bool STATS, int P, bool PREP = false, int LIST = kWalkList, int STACKMAX = kWalkStack>
 __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
   extern __shared__ uint4 walk_smem[];
   const int lane = lane_id();
-  const int wib = threadIdx.x >> 6;
+  // LEAN (three sets and more): five more live values per lane than two sets have, in the same 56 VGPRs.  What the compiler
+  // would derive from `lane` once and hold through the traversal -- list bases, lane-scaled offsets, 1 << lane, the address
+  // of the lane's point -- is derived again where it is used (`here()`), the wave's number is a scalar, and the list
+  // cursors are kept relative to the lane's column, so that they are compared with constants.
+  constexpr bool LEAN = P >= 3;
+  const int wib = LEAN ? (int) __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int) (threadIdx.x >> 6);
+  auto here = [&]() -> uint32_t {
+    uint32_t l = (uint32_t) lane;
+    if (LEAN) asm volatile("" : "+v"(l));
+    return l;
+  };
   const DeviceBvh& T = A.bvh;
   const uint32_t* const sky = (T.sky && T.sky[kSkyBuckets] == 0u) ? T.sky : nullptr;  // (exhaustive, or not used)
-  const int stack_entries = walk_stack_entries(T.top);
+  const int stack_entries = walk2_stack_entries(T.top, STACKMAX);
   const int stack_cap = A.walk_stack > 0 && A.walk_stack < stack_entries ? A.walk_stack : stack_entries;
-  uint4* const stack = walk_smem + (size_t) wib * (walk2_wave_lds(T.top, P) / 16);
-  uint32_t* const cand = reinterpret_cast<uint32_t*>(stack + stack_entries);  // [P][kWalkList][64], bank = lane
+  uint4* const stack = walk_smem + (size_t) wib * (walk2_wave_lds(T.top, P, LIST, STACKMAX) / 16);
+  uint32_t* const cand = reinterpret_cast<uint32_t*>(stack + stack_entries);  // [P][LIST][64], bank = lane
   const uint32_t stack_lds = (uint32_t) (uintptr_t) stack;
   constexpr uint32_t GP = 64u * P;  // positions per wave-group
   const uint64_t ngroups = (A.n + GP - 1) / GP;
@@ -2085,6 +2108,9 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
     int32_t qx[P], qy[P], qbest[P], sure_y0[P];
     uint32_t cand_base[P], cand_at[P];
     bool valid[P];
+    // (a set's list: slots base_of(p) + 64 k of `cand`, k < LIST, in the lane's column -- LEAN keeps the cursor without the lane)
+    auto base_of = [&](int p) -> uint32_t { return LEAN ? (uint32_t) p * (LIST * 64) : cand_base[p]; };
+    auto slot_of = [&](uint32_t at) -> uint32_t { return LEAN ? at + here() : at; };
     // Every load the group starts with is requested before the first one is waited for: the P points (positions past the
     // end read the last point: no branch around a load, so the compiler batches them) and the root's boxes, which do not
     // depend on the points at all.  Left in `if (valid)` regions each load was waited for inside its own region: three
@@ -2115,15 +2141,23 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
         ipl[p] = !prep && A.order ? A.order[ipc] : (uint32_t) ipc;
       }
     }
-    i4_t ext0 = {0, 0, 0, 0}, ext1 = {0, 0, 0, 0};
+    i4_t extp[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) extp[p] = i4_t{0, 0, 0, 0};
     if (ext) {
       const ext_ptr_t E = (ext_ptr_t) (uintptr_t) A.qext + (uint64_t) gu * P;
-      ext0 = E[0];
-      ext1 = E[1];
+#pragma unroll
+      for (int p = 0; p < P; p++) extp[p] = E[p];
     }
     ll2_t ptl[P];
     i2_t qpl[P];
-    if (full) {
+    if (full && LEAN) {
+      // (the group's scalar base plus a lane offset: no 64-bit address per lane lives across the traversal)
+      const i2_t* const q = reinterpret_cast<const i2_t*>(A.qpts) + (uint64_t) gu * GP;
+      const uint32_t l = here();
+#pragma unroll
+      for (int p = 0; p < P; p++) qpl[p] = __builtin_nontemporal_load(q + (l + 64u * p));
+    } else if (full) {
       const i2_t* const q = reinterpret_cast<const i2_t*>(A.qpts) + (uint64_t) gu * GP + lane;
 #pragma unroll
       for (int p = 0; p < P; p++) qpl[p] = __builtin_nontemporal_load(q + 64 * p);
@@ -2152,8 +2186,8 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
         qy[p] = valid[p] ? quant(ptl[p].y) : 0;
         qbest[p] = valid[p] ? 0x7FFFFFFF : -1;
       }
-      cand_base[p] = (uint32_t) lane + (uint32_t) p * (kWalkList * 64);
-      cand_at[p] = cand_base[p];
+      cand_base[p] = (uint32_t) lane + (uint32_t) p * (LIST * 64);
+      cand_at[p] = base_of(p);
       sure_y0[p] = INT32_MIN;
     }
     // (above the map's skyline: a certain miss -- the point sits the traversal out like a position past the end)
@@ -2173,9 +2207,13 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
       ext_ok = !__ballot(gone);
     }
     if (ext_ok) {
-      gx0 = ext0.x < ext1.x ? ext0.x : ext1.x;
-      gx1 = ext0.y > ext1.y ? ext0.y : ext1.y;
-      gy0 = ext0.z < ext1.z ? ext0.z : ext1.z;
+      gx0 = extp[0].x; gx1 = extp[0].y; gy0 = extp[0].z;
+#pragma unroll
+      for (int p = 1; p < P; p++) {  // (joined on the scalar side: the entries are wave-uniform)
+        gx0 = gx0 < extp[p].x ? gx0 : extp[p].x;
+        gx1 = gx1 > extp[p].y ? gx1 : extp[p].y;
+        gy0 = gy0 < extp[p].z ? gy0 : extp[p].z;
+      }
     } else {
       const bool l0 = qbest[0] >= 0, l1 = qbest[1] >= 0;
       const int32_t a0 = l0 ? qx[0] : kEmptyMin, a1 = l1 ? qx[1] : kEmptyMin;
@@ -2215,8 +2253,8 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
       const uint64_t higher = root_higher;
       uint64_t m = refine_if_many(b, __ballot(b.x0 <= gx1 && gx0 <= b.x1 && b.y1 >= gy0 - 1));
       if (__popcll(m) > stack_cap) { m = 0; ovf = true; }
-      if ((m >> lane) & 1)
-        stack[__popcll(m & higher)] = make_uint4(((uint32_t) T.top << 28) | (uint32_t) lane, (uint32_t) b.y0, (uint32_t) b.x0, (uint32_t) b.x1);
+      if ((m >> here()) & 1)
+        stack[__popcll(m & higher)] = make_uint4(((uint32_t) T.top << 28) | here(), (uint32_t) b.y0, (uint32_t) b.x0, (uint32_t) b.x1);
       sp = __popcll(m);
       wave_lds_fence();
       if (STATS) { st_groups++; st_pushed += (unsigned long long) sp; }
@@ -2262,9 +2300,9 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
         }
         uint64_t m = refine_if_many(b, __ballot(b.x0 <= gx1 && gx0 <= b.x1 && b.y1 >= gy0 - 1 && b.y0 <= gbest));
         if (sp + __popcll(m) > stack_cap) { ovf = true; break; }  // (the group leaves the walk: see kWalkStack)
-        if ((m >> lane) & 1)
+        if ((m >> here()) & 1)
           stack[sp + __popcll(m & higher)] =
-              make_uint4(((uint32_t) (lvl - 1) << 28) | (idx * 64 + lane), (uint32_t) b.y0, (uint32_t) b.x0, (uint32_t) b.x1);
+              make_uint4(((uint32_t) (lvl - 1) << 28) | (idx * 64 + here()), (uint32_t) b.y0, (uint32_t) b.x0, (uint32_t) b.x1);
         sp += __popcll(m);
         wave_lds_fence();
         if (STATS) { st_nodes++; st_pushed += (unsigned long long) __popcll(m); }
@@ -2311,10 +2349,10 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
             if ((sx0 <= qx[p]) & (qx[p] <= sx1) & (sy1 >= qy[p] - 1) & (qbest[p] >= sy0) & (j >= jlo)) {
               const bool certain = sx0 < qx[p] && qx[p] < sx1 && sy0 > qy[p];
               const bool replace = certain && sy1 < sure_y0[p];
-              const bool first = cand_at[p] == cand_base[p];
-              const bool over = !replace && cand_at[p] == cand_base[p] + kWalkList * 64;
+              const bool first = cand_at[p] == base_of(p);
+              const bool over = !replace && cand_at[p] == base_of(p) + LIST * 64;
               if (STATS && lane == __builtin_ctzll(__ballot(true))) st_hits++;
-              cand[(replace || over) ? cand_base[p] : cand_at[p]] = slot0 + (uint32_t) jj;
+              cand[slot_of((replace || over) ? base_of(p) : cand_at[p])] = slot0 + (uint32_t) jj;
               sure_y0[p] = (replace || (first && certain)) ? sy0 : INT32_MIN;
               cand_at[p] += replace ? 0u : 64u;
               const int32_t top = certain ? sy1 + 1 : 0x7FFFFFFF;
@@ -2345,7 +2383,7 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
             int kept = 0;
             if (STATS) st_sweeps++;
             for (int base = 0; base < sp; base += 64) {
-              const int i = base + lane;
+              const int i = base + (int) here();
               const bool have = i < sp;
               uint4 en = make_uint4(0, 0, 0, 0);
               if (have) en = stack[i];
@@ -2376,9 +2414,9 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
       // (the point's index is read again rather than held in a register through the traversal: the kernel keeps to 56
       //  VGPRs, six of its blocks fit beside two of k_lsi2)
       ipv[p] = !PREP && A.order ? A.order[valid[p] ? ipos : A.n - 1] : (uint32_t) ipos;
-      donev[p] = valid[p] && !ovf && (cand_at[p] == cand_base[p] || sure_y0[p] != INT32_MIN);
-      const bool hit = donev[p] && cand_at[p] != cand_base[p];
-      const uint32_t slot = hit ? cand[cand_base[p]] : 0u;
+      donev[p] = valid[p] && !ovf && (cand_at[p] == base_of(p) || sure_y0[p] != INT32_MIN);
+      const bool hit = donev[p] && cand_at[p] != base_of(p);
+      const uint32_t slot = hit ? cand[slot_of(base_of(p))] : 0u;
       const uint32_t e = T.seid[slot];
       const int32_t f = A.face ? T.sface[slot] : 0;
       out_e[p] = hit ? e : 0xFFFFFFFFu;
@@ -2386,15 +2424,16 @@ __device__ __forceinline__ void pip_walk_many(const PipArgs& A) {
     }
 #pragma unroll
     for (int p = 0; p < P; p++) {
-      const uint32_t fill = (cand_at[p] - cand_base[p]) >> 6;
-      const bool listed = valid[p] && !donev[p] && !ovf && fill <= (uint32_t) kWalkList;
+      const uint32_t fill = (cand_at[p] - base_of(p)) >> 6;
+      const bool listed = valid[p] && !donev[p] && !ovf && fill <= (uint32_t) LIST;
       const bool rest = valid[p] && !donev[p] && !listed;
       const uint64_t lm = __ballot(listed);
       const uint64_t g64 = (uint64_t) g32 * P + p;  // the 64-position group this set is
       if (listed) {
         const uint64_t rec = g64 * 64 + rank_below(lm);  // (records side by side at the head of the group's region: k_pip_walk)
 #pragma unroll
-        for (int k = 0; k < kWalkList; k++) A.todo[rec * kWalkList + k] = (uint32_t) k < fill ? cand[cand_base[p] + 64 * k] : 0xFFFFFFFFu;
+        // (a record is kWalkList slots whatever the list length: k_pip_exact reads the same records from every walk)
+        for (int k = 0; k < kWalkList; k++) A.todo[rec * kWalkList + k] = k < LIST && (uint32_t) k < fill ? cand[slot_of(base_of(p)) + 64 * k] : 0xFFFFFFFFu;
       }
       if (lane == 0 && g64 * 64 < A.n) A.todo_mask[g64] = lm;
       const uint64_t rm = __ballot(rest);
@@ -2464,6 +2503,10 @@ __global__ __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(96))) __attr
 __global__ __launch_bounds__(256, 4) __attribute__((amdgpu_num_sgpr(96))) void k_pip_walk2_stats(PipArgs A) { pip_walk_many<true, 2>(A); }
 // ... over the query map's prepared points (PipArgs::qpts, qext): the same body and budget with the other head
 __global__ __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(96))) __attribute__((amdgpu_num_vgpr(28))) void k_pip_walk2_prepared(PipArgs A) { pip_walk_many<false, 2, true>(A); }
+// ... and THREE 64-position sets per wave over the prepared points: a group's pops, expansions, leaf loads and bound
+// reductions are shared by 192 points instead of 128, in the same registers and the same LDS (five list slots per point, a
+// stack of 76: a sixth candidate sends the point to the rest list, a deeper group leaves the walk -- both exact)
+__global__ __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(96))) __attribute__((amdgpu_num_vgpr(28))) void k_pip_walk3_prepared(PipArgs A) { pip_walk_many<false, 3, true, kWalk3List, kWalk3Stack>(A); }
 
 
 // The walk's leftovers: the exact predicate (pip.h:36-95, as in k_pip's evaluate) over each listed point's complete
@@ -2873,15 +2916,20 @@ hipError_t launch_pip_walk(hipStream_t st, const PipArgs& a_in, bool stats, int 
   return hipGetLastError();
 }
 
-int pip_walk2_blocks_per_cu(int top) {
-  const size_t block = 4 * walk2_wave_lds(top) + 64;
+// (sets: 2, or 3 for k_pip_walk3_prepared -- the same bytes wherever the tree is high enough for either stack's cut)
+static size_t walk2_block_lds(int top, int sets) {
+  return 4 * (sets == 3 ? walk2_wave_lds(top, 3, kWalk3List, kWalk3Stack) : walk2_wave_lds(top));
+}
+
+int pip_walk2_blocks_per_cu(int top, int sets) {
+  const size_t block = walk2_block_lds(top, sets) + 64;
   const size_t by_lds = (size_t) 160 * 1024 / block;
   return (int) (by_lds < 8 ? by_lds : 8);
 }
 
 // ... beside `lsi_blocks_per_cu` resident blocks of k_lsi (17.5 KiB of LDS and one wave slot per SIMD each)
-int pip_walk2_blocks_beside(int top, int lsi_blocks_per_cu) {
-  const size_t block = 4 * walk2_wave_lds(top) + 64;
+int pip_walk2_blocks_beside(int top, int lsi_blocks_per_cu, int sets) {
+  const size_t block = walk2_block_lds(top, sets) + 64;
   const size_t left = (size_t) 160 * 1024 > (size_t) lsi_blocks_per_cu * 17920 ? (size_t) 160 * 1024 - (size_t) lsi_blocks_per_cu * 17920 : 0;
   int n = (int) (left / block);
   if (n > 8 - lsi_blocks_per_cu) n = 8 - lsi_blocks_per_cu;
@@ -2896,22 +2944,26 @@ int pip_walk2_blocks_beside(int top, int lsi_blocks_per_cu) {
   }
   const int by_vgpr = (512 - lsi_blocks_per_cu * lsi_regs) / walk_regs;
   if (n > by_vgpr) n = by_vgpr;
-  if (n > pip_walk2_blocks_per_cu(top)) n = pip_walk2_blocks_per_cu(top);
+  if (n > pip_walk2_blocks_per_cu(top, sets)) n = pip_walk2_blocks_per_cu(top, sets);
   return n < 1 ? 1 : n;
 }
 
-hipError_t launch_pip_walk2(hipStream_t st, const PipArgs& a_in, int max_blocks, int cus, bool stats) {
+hipError_t launch_pip_walk2(hipStream_t st, const PipArgs& a_in, int max_blocks, int cus, bool stats, int sets) {
   PipArgs a = a_in;
-  const size_t lds = 4 * walk2_wave_lds(a.bvh.top);
-  const int res = cus * pip_walk2_blocks_per_cu(a.bvh.top);
-  a.group_lanes = 64;  // (positions per mask; a wave takes two of them)
-  const uint64_t ngroups = (a.n + 127) / 128;
-  a.chunk_groups = a.chunk_groups ? a.chunk_groups : 3;  // (128-point groups: the same 6 x 64 positions per chunk)
+  if (sets != 3 || stats || !a.qpts) sets = 2;  // (three sets: over prepared points only, and never instrumented)
+  const size_t lds = walk2_block_lds(a.bvh.top, sets);
+  const int res = cus * pip_walk2_blocks_per_cu(a.bvh.top, sets);
+  a.group_lanes = 64;  // (positions per mask; a wave takes two or three of them)
+  const uint64_t gp = 64u * (uint64_t) sets;
+  const uint64_t ngroups = (a.n + gp - 1) / gp;
+  a.chunk_groups = a.chunk_groups ? a.chunk_groups : (sets == 3 ? 2 : 3);  // (128- or 192-point groups: the same 6 x 64 positions per chunk)
   const uint64_t nchunks = (ngroups + a.chunk_groups - 1) / a.chunk_groups;
   const int grid = grid_for(nchunks, 4, res < max_blocks ? res : max_blocks);
   note("k_pip_walk2", grid, 2);
   if (stats)
     hipLaunchKernelGGL(k_pip_walk2_stats, dim3(grid), dim3(256), lds, st, a);
+  else if (sets == 3)
+    hipLaunchKernelGGL(k_pip_walk3_prepared, dim3(grid), dim3(256), lds, st, a);  // (one of the k_pip_walk2 family, like the next)
   else if (a.qpts)
     hipLaunchKernelGGL(k_pip_walk2_prepared, dim3(grid), dim3(256), lds, st, a);  // (the plan and the profiles' tables know both as k_pip_walk2)
   else

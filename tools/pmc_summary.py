@@ -34,7 +34,8 @@ def short(name):
 
 
 WALK2_INT64 = "k_pip_walk2 (int64)"  # k_pip_walk2 proper in a run that also launched k_pip_walk2_prepared: see collect()
-KERNELS = ("k_lsi", "k_lsi2", "k_lsix", "k_lsi2x", "k_pip_walk", "k_pip_walk2", WALK2_INT64, "k_pip_strip", "k_pip_exact", "k_pip", "k_lsi_points", "k_lsi_points_gcd")
+WALK2_TWO_SETS = "k_pip_walk2 (two sets)"  # k_pip_walk2_prepared in a run that also launched k_pip_walk3_prepared
+KERNELS = ("k_lsi", "k_lsi2", "k_lsix", "k_lsi2x", "k_pip_walk", "k_pip_walk2", WALK2_INT64, WALK2_TWO_SETS, "k_pip_strip", "k_pip_exact", "k_pip", "k_lsi_points", "k_lsi_points_gcd")
 
 
 def full_grid(vals):
@@ -56,7 +57,15 @@ def collect(d):
     # tables know it as k_pip_walk2, and where a run launched both -- bench.py also times the query map's vertices as a
     # caller-owned array, which reads the int64 points -- the tables hold the one the timed steps ran
     # (... and the int64 kernel's launches of such a run keep a row of their own)
+    # (... and so is its three-set form, k_pip_walk3_prepared, which takes the name where a run launched it -- the paired
+    #  steps; the two-set prepared kernel of such a run, the queries that ran alone, then keeps a row of its own)
     for per_kernel in acc.values():
+        if "k_pip_walk3_prepared" in per_kernel:
+            if "k_pip_walk2" in per_kernel:
+                per_kernel[WALK2_INT64] = per_kernel.pop("k_pip_walk2")
+            if "k_pip_walk2_prepared" in per_kernel:
+                per_kernel[WALK2_TWO_SETS] = per_kernel.pop("k_pip_walk2_prepared")
+            per_kernel["k_pip_walk2"] = per_kernel.pop("k_pip_walk3_prepared")
         if "k_pip_walk2_prepared" in per_kernel:
             if "k_pip_walk2" in per_kernel:
                 per_kernel[WALK2_INT64] = per_kernel.pop("k_pip_walk2")

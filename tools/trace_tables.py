@@ -20,7 +20,11 @@ for r in csv.DictReader(open(a.csv)):
 rows.sort()
 # k_pip_walk2_prepared (the same body over the query map's prepared points) is what the plan calls k_pip_walk2: in a trace
 # that holds it, it takes that name and k_pip_walk2 proper (caller-owned arrays) is told apart as "k_pip_walk2 (int64)"
-if any(r[2] == "k_pip_walk2_prepared" for r in rows):
+# (k_pip_walk3_prepared, three sets per wave, likewise: where a trace holds it, it is the family's kernel of the timed steps
+#  and the two-set prepared kernel -- the queries that ran alone -- keeps its own name)
+if any(r[2] == "k_pip_walk3_prepared" for r in rows):
+    rows = [(s, e, {"k_pip_walk3_prepared": "k_pip_walk2", "k_pip_walk2": "k_pip_walk2 (int64)", "k_pip_walk2_prepared": "k_pip_walk2 (two sets)"}.get(n, n), b) for s, e, n, b in rows]
+elif any(r[2] == "k_pip_walk2_prepared" for r in rows):
     rows = [(s, e, {"k_pip_walk2_prepared": "k_pip_walk2", "k_pip_walk2": "k_pip_walk2 (int64)"}.get(n, n), b) for s, e, n, b in rows]
 if a.regimes:
     acc = collections.defaultdict(list)
