@@ -69,13 +69,14 @@ def levels_of(dctx):
     return [i for i in dctx.handle.get_plan()["index"] if i["map"] == 0][0]["levels"]
 
 
-def device_nearest(dctx, points=None, n=None, max_dist=None, records=True, dist=True):
-    """-> (tuples or eids, dist or None) through ops.NearestLBVH: points None = the first n vertices of the query map"""
+def device_nearest(dctx, points=None, n=None, max_dist=None, records=True, dist=True, begin=0):
+    """-> (tuples or eids, dist or None) through ops.NearestLBVH: points None = the n vertices of the query map from `begin`"""
     nn = len(points) if points is not None else n
     q = ops.NearestLBVH(dctx)
     q.Init(nn)
     try:
-        got_n = q.Query(1, query_points=points, point_range=None if points is not None else (0, nn), max_dist=max_dist, records=records, dist=dist)
+        got_n = q.Query(1, query_points=points, point_range=None if points is not None else (begin, begin + nn), max_dist=max_dist, records=records,
+                        dist=dist)
         assert got_n == nn
         eids = q.get_eids()
         if records:

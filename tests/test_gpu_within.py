@@ -61,14 +61,15 @@ def twin_answer(twin, seg, points, max_dist):
     return dict(off=off, eid=eid, rec=rec, dist=dist, counts=dict(zip(_capi.WITHIN_COUNTS, counts)))
 
 
-def device_answer(dctx, points=None, n=None, max_dist=0, records=True, dist=True, capacity=0):
-    """the same through ops.WithinLBVH (capacity 0: the counting call sizes the arrays); points None = the first n vertices of
-    the query map"""
+def device_answer(dctx, points=None, n=None, max_dist=0, records=True, dist=True, capacity=0, begin=0):
+    """the same through ops.WithinLBVH (capacity 0: the counting call sizes the arrays); points None = the n vertices of the
+    query map from `begin`"""
     nn = len(points) if points is not None else n
     q = ops.WithinLBVH(dctx)
     q.Init(nn, capacity)
     try:
-        n_pairs = q.Query(1, query_points=points, point_range=None if points is not None else (0, nn), max_dist=max_dist, records=records, dist=dist)
+        n_pairs = q.Query(1, query_points=points, point_range=None if points is not None else (begin, begin + nn), max_dist=max_dist, records=records,
+                          dist=dist)
         indptr, eids = q.to_csr()
         assert len(eids) == n_pairs == q.counts()["n_pairs"] and indptr.dtype == np.int64 and (indptr == q.get_offsets().astype(np.int64)).all()
         if not records:
