@@ -2380,6 +2380,43 @@ static int estimate_distance_points(rj_handle h, const int64_t* pts, uint64_t n)
   return RJ_OK;
 }
 
+// What the two distance queries refuse before they touch the device, with one wording, and where their points are.  fn: the
+// function's name, in front of every message.  own: the message of a check of the call's own (its outputs) that failed, or
+// null.  max_dist lies in [min_dist, 2^48] (min_dist < 0: negative is "unlimited").  largest: what has to stay below 2^32,
+// as size_rule says.  *pts_out: the caller's array, or vertex pt_begin of the query map (then *coh_begin_out = pt_begin).
+static int check_distance_call(rj_handle h, const char* fn, const char* own, int base_map_id, int query_map_id, const int64_t* pts_dev, uint64_t pt_begin,
+                               uint64_t n, int64_t max_dist, int64_t min_dist, uint64_t largest, const char* size_rule, const int64_t** pts_out,
+                               uint64_t* coh_begin_out) {
+  if (base_map_id < 0 || base_map_id > 1 || query_map_id != 1 - base_map_id) return fail(h, RJ_E_INVALID, "%s: base/query map ids must be {0,1} and differ", fn);
+  if (!h->bvh[base_map_id].built) return fail(h, RJ_E_INVALID, "%s: call rj_build_lbvh(base map) first", fn);
+  if (own) return fail(h, RJ_E_INVALID, "%s: %s", fn, own);
+  if (max_dist < min_dist || max_dist > nearest::kMaxDist)
+    return fail(h, RJ_E_INVALID, min_dist < 0 ? "%s: max_dist must not exceed 2^48 (negative: unlimited)" : "%s: max_dist must lie in [0, 2^48]", fn);
+  *pts_out = pts_dev;
+  *coh_begin_out = 0;
+  if (!pts_dev) {
+    const MapState& q = h->map[query_map_id];
+    if (!q.present || pt_begin + n > q.np || pt_begin + n < pt_begin) return fail(h, RJ_E_INVALID, "%s: bad point range of the query map", fn);
+    *pts_out = q.pts + 2 * pt_begin;
+    *coh_begin_out = pt_begin;
+  }
+  if (largest >= within::kMaxPoints) return fail(h, RJ_E_INVALID, "%s: %s", fn, size_rule);
+  return RJ_OK;
+}
+// ... and what both do behind the last synchronisation of the call: the counters of the instrumented kernel, and the call's
+// fault word (rj_distance_walk.h: the checked push), tested and cleared
+static int finish_distance_call(rj_handle h, uint32_t fault_word, const char* kernel) {
+  if (h->stats_on) {
+    RJ_HIP(h, hipMemcpy(h->h_pinned + 1, h->d_stats, 128, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 16; i++) h->last_stats[i] = h->h_pinned[1 + i];
+  }
+  if (h->h_fault[fault_word]) {
+    h->h_fault[fault_word] = 0;
+    return fail(h, RJ_E_INTERNAL, "traversal stack overflow in %s: results are incomplete", kernel);
+  }
+  return RJ_OK;
+}
+
 // ---- the nearest edge of the base map for every point (rj_nearest.h, rj_nearest.hip) ----------------------------------------
 int rj_nearest_query(rj_handle h, int base_map_id, int query_map_id, const int64_t* pts_dev, uint64_t pt_begin, uint64_t n, int64_t max_dist,
                      uint32_t* eid_dev, rj_near* rec_dev, double* dist_dev) {
@@ -2387,20 +2424,11 @@ int rj_nearest_query(rj_handle h, int base_map_id, int query_map_id, const int64
   static_assert(RJ_MISS_EID == nearest::kMissEid, "the miss value");
   RJ_CHECK_H(h);
   h->nearest_report = StageMs{};
-  if (base_map_id < 0 || base_map_id > 1 || query_map_id != 1 - base_map_id)
-    return fail(h, RJ_E_INVALID, "rj_nearest_query: base/query map ids must be {0,1} and differ");
-  if (!h->bvh[base_map_id].built) return fail(h, RJ_E_INVALID, "rj_nearest_query: call rj_build_lbvh(base map) first");
-  if (n && !eid_dev) return fail(h, RJ_E_INVALID, "rj_nearest_query: null output");
-  if (max_dist > nearest::kMaxDist) return fail(h, RJ_E_INVALID, "rj_nearest_query: max_dist must not exceed 2^48 (negative: unlimited)");
-  const int64_t* pts = pts_dev;
-  uint64_t coh_begin = 0;
-  if (!pts) {
-    coh_begin = pt_begin;
-    const MapState& q = h->map[query_map_id];
-    if (!q.present || pt_begin + n > q.np || pt_begin + n < pt_begin) return fail(h, RJ_E_INVALID, "rj_nearest_query: bad point range of the query map");
-    pts = q.pts + 2 * pt_begin;
-  }
-  if (n >= (1ull << 32)) return fail(h, RJ_E_INVALID, "rj_nearest_query: n < 2^32");
+  const int64_t* pts;
+  uint64_t coh_begin;
+  if (int r = check_distance_call(h, "rj_nearest_query", n && !eid_dev ? "null output" : nullptr, base_map_id, query_map_id, pts_dev, pt_begin, n, max_dist,
+                                  INT64_MIN, n, "n < 2^32", &pts, &coh_begin))
+    return r;
   if (n == 0) return RJ_OK;
   if (int r = set_device(h)) return r;
   StageEvents ev;
@@ -2421,15 +2449,9 @@ int rj_nearest_query(rj_handle h, int base_map_id, int query_map_id, const int64
   RJ_HIP(h, launch_nearest(h->stream, a, h->stats_on != 0, h->debug_nearest_blocks, h->cus));
   RJ_HIP(h, ev.mark(2, h->stream));
   if (int r = estimate_distance_points(h, pts, n)) return r;
-  if (h->stats_on) RJ_HIP(h, hipMemcpyAsync(h->h_pinned + 1, h->d_stats, 128, hipMemcpyDeviceToHost, h->stream));
   RJ_HIP(h, hipStreamSynchronize(h->stream));
   ev.times(2, h->nearest_report.ms);
-  if (h->stats_on) for (int i = 0; i < 16; i++) h->last_stats[i] = h->h_pinned[1 + i];
-  if (h->h_fault[kFaultNearestStack]) {
-    h->h_fault[kFaultNearestStack] = 0;
-    return fail(h, RJ_E_INTERNAL, "traversal stack overflow in k_nearest: results are incomplete");
-  }
-  return RJ_OK;
+  return finish_distance_call(h, kFaultNearestStack, "k_nearest");
 }
 
 // ---- every edge of the base map within a distance of each point (rj_within.h, rj_within.hip) --------------------------------
@@ -2438,21 +2460,12 @@ int rj_within_query(rj_handle h, int base_map_id, int query_map_id, const int64_
   static_assert(sizeof(rj_within_counts) == sizeof(within::Counts), "layouts");
   RJ_CHECK_H(h);
   h->within_report = StageMs{};
-  if (base_map_id < 0 || base_map_id > 1 || query_map_id != 1 - base_map_id)
-    return fail(h, RJ_E_INVALID, "rj_within_query: base/query map ids must be {0,1} and differ");
-  if (!h->bvh[base_map_id].built) return fail(h, RJ_E_INVALID, "rj_within_query: call rj_build_lbvh(base map) first");
-  if (!counts) return fail(h, RJ_E_INVALID, "rj_within_query: counts is null");
-  if (pair_capacity && !eid_dev) return fail(h, RJ_E_INVALID, "rj_within_query: pair_capacity without eid_dev");
-  if (max_dist < 0 || max_dist > nearest::kMaxDist) return fail(h, RJ_E_INVALID, "rj_within_query: max_dist must lie in [0, 2^48]");
-  const int64_t* pts = pts_dev;
-  uint64_t coh_begin = 0;
-  if (!pts) {
-    coh_begin = pt_begin;
-    const MapState& q = h->map[query_map_id];
-    if (!q.present || pt_begin + n > q.np || pt_begin + n < pt_begin) return fail(h, RJ_E_INVALID, "rj_within_query: bad point range of the query map");
-    pts = q.pts + 2 * pt_begin;
-  }
-  if (n >= within::kMaxPoints || pair_capacity >= within::kMaxPoints) return fail(h, RJ_E_INVALID, "rj_within_query: n < 2^32 and pair_capacity < 2^32");
+  const int64_t* pts;
+  uint64_t coh_begin;
+  if (int r = check_distance_call(h, "rj_within_query", !counts ? "counts is null" : (pair_capacity && !eid_dev ? "pair_capacity without eid_dev" : nullptr),
+                                  base_map_id, query_map_id, pts_dev, pt_begin, n, max_dist, 0, n > pair_capacity ? n : pair_capacity,
+                                  "n < 2^32 and pair_capacity < 2^32", &pts, &coh_begin))
+    return r;
   if (int r = set_device(h)) return r;
   memset(counts, 0, sizeof(*counts));
   if (n == 0) {
@@ -2482,14 +2495,7 @@ int rj_within_query(rj_handle h, int base_map_id, int query_map_id, const int64_
   a.stack_cap = h->debug_stack_cap;
   WithinResult res;
   RJ_HIP(h, within_device(h->stream, a, h->stats_on != 0, h->debug_within_blocks, h->cus, &ev, &res));
-  if (h->stats_on) {
-    RJ_HIP(h, hipMemcpy(h->h_pinned + 1, h->d_stats, 128, hipMemcpyDeviceToHost));
-    for (int i = 0; i < 16; i++) h->last_stats[i] = h->h_pinned[1 + i];
-  }
-  if (h->h_fault[kFaultWithinStack]) {
-    h->h_fault[kFaultWithinStack] = 0;
-    return fail(h, RJ_E_INTERNAL, "traversal stack overflow in k_within: results are incomplete");
-  }
+  if (int r = finish_distance_call(h, kFaultWithinStack, "k_within")) return r;
   if (res.appended != res.counts.n_pairs)
     return fail(h, RJ_E_INTERNAL, "rj_within_query: %llu pairs appended, %llu counted", (unsigned long long) res.appended, (unsigned long long) res.counts.n_pairs);
   ev.times(3, h->within_report.ms);

@@ -2,21 +2,16 @@
 // with the exact predicate of rj_nearest.h, and the pipeline that makes a CSR of what it finds (rj_within.h: ORDER).
 // gfx950 only (wave = 64 lanes).
 //
-// k_within   k_nearest's shape (rj_nearest.hip): one wave takes 64 consecutive points of the (possibly Morton-ordered) set,
-// one per lane, and walks the tree depth-first with ONE stack in LDS; a node's 64 children are one coalesced load, lane =
-// child; a child is pushed while SOME lane admits it, tested per lane with the child's box broadcast; padding slots and
-// the nodes over padding are excluded by box_empty.  What differs: the bound never tightens -- ub2 =
-// ub2_of_max_dist(max_dist) is wave-uniform -- so there is no pop order, no stale test at the pop and no candidate
-// held per lane.  In front of the per-lane ballots sits one lane-parallel test of all 64 children against the box of
-// the group's cells (group_lb2): it only shortens the loop over the children, every child it keeps is still tested per
-// lane.  In a leaf block the slots go one by one: the lanes whose cell admits the slot's box evaluate candidate and
-// within_filtered; a lane that hits counts the hit and puts the key (ORIGINAL point number << 32) | eid into the
-// wave's staging buffer in LDS, which is flushed 64 keys at a time with one atomicAdd per flush (k_lsi's
-// lsi_flush_hits): positions at or behind the capacity are counted and not written.  At the end of a group every live
-// lane writes its count.
-//
-// STACK   k_nearest's discipline, capacity and checked pushes (kPipStack, rj_device.h); the fault word is
-// kFaultWithinStack (-> RJ_E_INTERNAL).
+// k_within   THE WALK is rj_distance_walk.h's (SHAPE, STACK), without RETEST: the bound never tightens -- ub2 =
+// ub2_of_max_dist(max_dist) is wave-uniform -- so there is no pop order (a kept child lands by rank_below), no stale test
+// at the pop and no candidate held per lane.  What is k_within's own:
+//   * the test in front of the per-lane ballots: all 64 boxes, lane-parallel, against the box of the group's cells
+//     (group_lb2, rj_within.h: a lower bound of every lane's lower bound);
+//   * the body of a slot: the lanes that admit it evaluate candidate and within_filtered; a lane that hits counts the
+//     hit and puts the key (ORIGINAL point number << 32) | eid into the wave's staging buffer in LDS, which is flushed 64
+//     keys at a time with one atomicAdd per flush (k_lsi's lsi_flush_hits): positions at or behind the capacity are
+//     counted and not written.  At the end of a group every live lane writes its count;
+//   * the fault word is kFaultWithinStack.
 //
 // BEHIND IT   an exclusive scan of the counts (rocPRIM) gives the offsets, a small reduction the points hit and the
 // longest list; the counting call ends there.  Otherwise, if the pairs fit, a radix sort of the keys over
@@ -32,6 +27,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/functional.hpp>
 
+#include "rj_distance_walk.h"
 #include "rj_within.h"
 
 namespace rj {
@@ -41,13 +37,10 @@ using namespace within;
 
 namespace {
 
-constexpr int kWithinWaves = 4;          // waves per block
-constexpr int kWithinStack = kPipStack;  // 64 + 63 (kMaxTop - 1) and four to spare: k_nearest's bound
-constexpr int kWithinStage = 128;        // keys of the staging buffer: below 64 in front of a slot, at most 64 more behind it
+constexpr int kWithinStage = 128;  // keys of the staging buffer: below 64 in front of a slot, at most 64 more behind it
 
-struct WithinWaveLds {  // 20 bytes per entry and 8 per key: 7424 B per wave
-  uint4 box[kWithinStack];      // {x0, y0, x1, y1} of the node
-  uint32_t code[kWithinStack];  // level << 28 | index
+struct WithinWaveLds {  // the walk's stack and 8 bytes per key: 7424 B per wave
+  dwalk::Stack stack;
   uint64_t keys[kWithinStage];
 };
 
@@ -55,11 +48,6 @@ struct WithinMeta {
   unsigned long long appended;  // what the flushes counted
   unsigned long long n_points_hit, max_per_point;
 };
-
-__device__ __noinline__ void raise_within_fault(uint32_t* fault) {
-  // a plain store (idempotent), not an atomic: the word is pinned host memory the device writes directly
-  __hip_atomic_store(fault + kFaultWithinStack, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // the top n (<= 64) keys of the wave's staging buffer go out behind ONE atomic; a position at or behind the capacity is
 // counted and not written
@@ -85,114 +73,50 @@ struct WithinKernelArgs {
 };
 
 template <bool STATS>
-__global__ __launch_bounds__(64 * kWithinWaves) void k_within(WithinKernelArgs K) {
-  __shared__ WithinWaveLds lds[kWithinWaves];
+__global__ __launch_bounds__(64 * dwalk::kWaves) void k_within(WithinKernelArgs K) {
+  __shared__ WithinWaveLds lds[dwalk::kWaves];
   const WithinArgs& A = K.a;
   const int lane = lane_id();
   const int wib = threadIdx.x >> 6;
   WithinWaveLds& L = lds[wib];
-  const DeviceBvh& T = A.bvh;
   const uint64_t ngroups = (A.n + 63) / 64;
-  const int stack_cap = STATS && A.stack_cap < kWithinStack ? A.stack_cap : kWithinStack;  // (lowered only by tests of the fault path)
-  const uint64_t ub2 = ub2_of_max_dist(A.max_dist);
+  const int stack_cap = STATS && A.stack_cap < dwalk::kStack ? A.stack_cap : dwalk::kStack;  // (lowered only by tests of the fault path)
+  const uint64_t bound = ub2_of_max_dist(A.max_dist);
   const double m2 = approx_m2(A.max_dist);
   const bool filling = K.keys != nullptr;
-  unsigned long long st_leaf = 0, st_cand = 0, st_nodes = 0, st_wave_leaf = 0, st_pairs = 0;
+  dwalk::Stats st;
+  unsigned long long st_pairs = 0;
   int nk = 0;  // wave-uniform fill of L.keys
 
-  for (uint64_t g = (uint64_t) blockIdx.x * kWithinWaves + wib; g < ngroups; g += (uint64_t) gridDim.x * kWithinWaves) {
-    const uint64_t ipos = g * 64 + lane;
-    const bool live = ipos < A.n;
-    const uint64_t ip = A.order ? (live ? A.order[ipos] : 0) : ipos;
-    int64_t px = 0, py = 0;
-    if (live) {
-      px = A.pts[2 * ip];
-      py = A.pts[2 * ip + 1];
-    }
-    const int32_t qx = cell_of(px), qy = cell_of(py);
-    // the box of the group's cells: the wave-uniform reject looks from it
-    const int32_t gx0 = wave_min(live ? qx : kEmptyMin), gx1 = wave_max(live ? qx : kEmptyMax);
-    const int32_t gy0 = wave_min(live ? qy : kEmptyMin), gy1 = wave_max(live ? qy : kEmptyMax);
+  for (uint64_t g = (uint64_t) blockIdx.x * dwalk::kWaves + wib; g < ngroups; g += (uint64_t) gridDim.x * dwalk::kWaves) {
+    const dwalk::Group G = dwalk::load_group(A.pts, A.order, A.n, g, lane);
     uint32_t count = 0;
-    int sp = 0;
-
-    // the boxes b (one per lane, `have`: it exists) that some lane admits, as a mask
-    auto admitted = [&](const QBox& b, bool have) {
-      uint64_t keep = 0;
-      const bool near_group = have && !box_empty(b.x0, b.x1) && admits(ub2, group_lb2(b.x0, b.y0, b.x1, b.y1, gx0, gy0, gx1, gy1));
-      for (uint64_t um = __ballot(near_group); um; um &= um - 1) {
-        const int c = __builtin_ctzll(um);
-        const uint64_t lb2 = box_lb2(bcast(b.x0, c), bcast(b.y0, c), bcast(b.x1, c), bcast(b.y1, c), qx, qy);
-        if (__ballot(live && admits(ub2, lb2))) keep |= 1ull << c;
-      }
-      return keep;
-    };
-    // the children of a node (lane = child) onto the stack
-    auto push_children = [&](int lvl, uint32_t first, const QBox& b, bool have) {
-      const uint64_t keep = admitted(b, have);
-      const int n = __popcll(keep);
-      if (sp + n > stack_cap) {
-        if (lane == 0) raise_within_fault(A.fault);
-        return;
-      }
-      if ((keep >> lane) & 1) {
-        const int at = sp + rank_below(keep);
-        L.box[at] = make_uint4((uint32_t) b.x0, (uint32_t) b.y0, (uint32_t) b.x1, (uint32_t) b.y1);
-        L.code[at] = ((uint32_t) lvl << 28) | (first + (uint32_t) lane);
-      }
-      sp += n;
-      wave_lds_fence();
-    };
-
-    push_children(T.top, 0u, T.lvl[T.top][lane], (uint32_t) lane < T.nlvl[T.top]);
-    while (sp > 0) {
-      --sp;
-      const uint4 eb = L.box[sp];
-      const uint32_t e = (uint32_t) __builtin_amdgcn_readfirstlane((int32_t) L.code[sp]);
-      const int lvl = (int) (e >> 28);
-      const uint32_t idx = e & 0x0FFFFFFFu;
-      if (lvl > 1) {
-        if (STATS) st_nodes++;
-        push_children(lvl - 1, idx * 64u, T.lvl[lvl - 1][(uint64_t) idx * 64 + lane], true);
-        continue;
-      }
-      const int32_t ex0 = __builtin_amdgcn_readfirstlane((int32_t) eb.x), ey0 = __builtin_amdgcn_readfirstlane((int32_t) eb.y);
-      const int32_t ex1 = __builtin_amdgcn_readfirstlane((int32_t) eb.z), ey1 = __builtin_amdgcn_readfirstlane((int32_t) eb.w);
-      // the lanes that admit the block (some do: it was pushed); the others skip its slots
-      const bool want = live && admits(ub2, box_lb2(ex0, ey0, ex1, ey1, qx, qy));
-      if (STATS) st_leaf += (unsigned long long) __popcll(__ballot(want)), st_wave_leaf++;
-      const uint64_t slot0 = (uint64_t) idx * 64;
-      const QBox bb = T.box0[slot0 + lane];  // one base segment per lane
-      const bool near_group = !box_empty(bb.x0, bb.x1) && admits(ub2, group_lb2(bb.x0, bb.y0, bb.x1, bb.y1, gx0, gy0, gx1, gy1));
-      for (uint64_t um = __ballot(near_group); um; um &= um - 1) {
-        const int j = __builtin_ctzll(um);
-        const uint64_t lb2 = box_lb2(bcast(bb.x0, j), bcast(bb.y0, j), bcast(bb.x1, j), bcast(bb.y1, j), qx, qy);
-        const bool adm = want && admits(ub2, lb2);
-        const uint64_t am = __ballot(adm);
-        if (!am) continue;
-        if (STATS) st_cand += (unsigned long long) __popcll(am);
-        const Seg s = T.sseg[slot0 + j];  // (one address for the wave)
-        const uint32_t eid = T.seid[slot0 + j];
-        const bool hit = adm && within_filtered(candidate(s, eid, px, py), A.max_dist, m2, true);
-        count += hit ? 1u : 0u;
-        if (!filling) continue;
-        const uint64_t hm = __ballot(hit);
-        if (!hm) continue;
-        if (hit) L.keys[nk + rank_below(hm)] = pair_key((uint32_t) ip, eid);
-        nk += __popcll(hm);
-        wave_lds_fence();
-        if (STATS) st_pairs += (unsigned long long) __popcll(hm);
-        if (nk >= 64) within_flush(L, nk, 64, &K.meta->appended, K.keys, A.capacity, lane);
-      }
-    }
-    if (live) K.cnt[ip] = count;
+    uint64_t ub2 = bound;
+    dwalk::walk_group<STATS, false>(
+        A.bvh, L.stack, G, stack_cap, A.fault + kFaultWithinStack, lane, ub2,
+        [&](const QBox& b) { return admits(bound, group_lb2(b.x0, b.y0, b.x1, b.y1, G.gx0, G.gy0, G.gx1, G.gy1)); },
+        [](uint64_t keep, int, const QBox&, bool, int) { return rank_below(keep); },
+        [&](bool adm, const Seg& s, uint32_t eid) {
+          const bool hit = adm && within_filtered(candidate(s, eid, G.px, G.py), A.max_dist, m2, true);
+          count += hit ? 1u : 0u;
+          if (!filling) return;
+          const uint64_t hm = __ballot(hit);
+          if (!hm) return;
+          if (hit) L.keys[nk + rank_below(hm)] = pair_key((uint32_t) G.ip, eid);
+          nk += __popcll(hm);
+          wave_lds_fence();
+          if (STATS) st_pairs += (unsigned long long) __popcll(hm);
+          if (nk >= 64) within_flush(L, nk, 64, &K.meta->appended, K.keys, A.capacity, lane);
+        },
+        st);
+    if (G.live) K.cnt[G.ip] = count;
   }
   if (nk > 0) within_flush(L, nk, nk, &K.meta->appended, K.keys, A.capacity, lane);
   if (STATS && lane == 0 && A.stats) {
-    atomicAdd(&A.stats[0], st_leaf);
-    atomicAdd(&A.stats[1], st_cand);
-    atomicAdd(&A.stats[2], st_nodes);
-    atomicAdd(&A.stats[3], st_wave_leaf);
+    atomicAdd(&A.stats[0], st.leaf);
+    atomicAdd(&A.stats[1], st.cand);
+    atomicAdd(&A.stats[2], st.nodes);
+    atomicAdd(&A.stats[3], st.wave_leaf);
     atomicAdd(&A.stats[4], st_pairs);
   }
 }
@@ -272,16 +196,11 @@ hipError_t within_device(hipStream_t st, const WithinArgs& a, bool stats, int bl
     if ((e = hipMemsetAsync(cnt + n, 0, sizeof(uint32_t), st)) != hipSuccess) break;
     if (n) {
       WithinKernelArgs K{a, cnt, cap ? keys : nullptr, meta};
-      const uint64_t ngroups = (n + 63) / 64;
-      const uint64_t full = (ngroups + kWithinWaves - 1) / kWithinWaves;
-      // by size: a block per four groups up to 16 blocks per CU (7424 B of LDS per wave: 5 blocks of four waves are resident
-      // on a CU, the rest queue behind them); the grid-stride loop takes what is left
-      uint64_t grid = blocks > 0 ? (uint64_t) blocks : (uint64_t) (cus > 0 ? cus : 256) * 16;
-      if (grid > full) grid = full;
+      const dim3 grid = dwalk::grid_for(n, blocks, cus);  // (7424 B of LDS per wave: 5 blocks of four waves are resident on a CU)
       if (stats)
-        hipLaunchKernelGGL(k_within<true>, dim3((uint32_t) grid), dim3(64 * kWithinWaves), 0, st, K);
+        hipLaunchKernelGGL(k_within<true>, grid, dim3(64 * dwalk::kWaves), 0, st, K);
       else
-        hipLaunchKernelGGL(k_within<false>, dim3((uint32_t) grid), dim3(64 * kWithinWaves), 0, st, K);
+        hipLaunchKernelGGL(k_within<false>, grid, dim3(64 * dwalk::kWaves), 0, st, K);
       if ((e = hipGetLastError()) != hipSuccess) break;
     }
     if ((e = ev->mark(2, st)) != hipSuccess) break;

@@ -254,16 +254,64 @@ class PIPLBVH:
         return face_points(self.h, self.faces, self.n, values=values, value_stride=value_stride, faces=faces, members=members, **kw)
 
 
-class NearestLBVH:
-    """The nearest edge of the indexed base map for every query point (rj_nearest_query), mirroring PIPLBVH: the eid, the
-    exact record (which end or the interior, and d^2 as a rational) and the distance in double."""
+class _DistanceQuery:
+    """What NearestLBVH and WithinLBVH share: where the points of a call come from, the per-row outputs (eid, exact record,
+    distance in double; `rows_`: how many the last call filled) and the freeing of the device buffers."""
 
     def __init__(self, dctx):
         self.ctx_ = dctx
         self.h = dctx.handle
         self.eids = self.records = self.dist = None
-        self.n = 0
+        self.n = self.rows_ = 0
         self.has_records = self.has_dist = False
+
+    def _over_points(self, query_map_id, query_points, point_range, call):
+        """call(device points or None, begin, n) over int64[n,2] scaled host points, staged for the call and freed behind it,
+        or over the query map's own vertices, optionally a [begin, end) sub-range (a shard) -> (n, what call returned)"""
+        if query_points is not None:
+            pts = np.ascontiguousarray(query_points, dtype=np.int64).reshape(-1, 2)
+            n = pts.shape[0]
+            assert n <= self.n_alloc
+            buf = self.h.alloc(16 * max(1, n)).from_host(pts)
+            try:
+                return n, call(buf, 0, n)
+            finally:
+                buf.free()
+        b, e = point_range if point_range is not None else (0, self.ctx_.get_map(query_map_id).n_points)
+        n = e - b
+        assert n <= self.n_alloc
+        return n, call(None, b, n)
+
+    def get_eids(self):
+        return self.eids.to_host(np.uint32, self.rows_)
+
+    def get_records(self):
+        """-> NEAR_DTYPE rows; ValueError after a Query with records=False"""
+        if not self.has_records:
+            raise ValueError("the last Query ran with records=False")
+        return self.records.to_host(_capi.NEAR_DTYPE, self.rows_)
+
+    def get_dist(self):
+        if not self.has_dist:
+            raise ValueError("the last Query ran with dist=False")
+        return self.dist.to_host(np.float64, self.rows_)
+
+    @staticmethod
+    def exact(records):
+        """NEAR_DTYPE rows -> [(eid, where, num, den)] with num (signed) and den as Python ints: d^2 = num^2 / den where
+        `where` is 0, num / den (den = 1) at an end"""
+        return [(int(r["eid"]), int(r["where"]), (int(r["num_hi"]) << 64) + int(r["num_lo"]), (int(r["den_hi"]) << 64) + int(r["den_lo"])) for r in records]
+
+    def _free(self, *names):
+        for name in names:
+            if getattr(self, name) is not None:
+                getattr(self, name).free()
+                setattr(self, name, None)
+
+
+class NearestLBVH(_DistanceQuery):
+    """The nearest edge of the indexed base map for every query point (rj_nearest_query), mirroring PIPLBVH: the eid, the
+    exact record (which end or the interior, and d^2 as a rational) and the distance in double, one row per point."""
 
     def Init(self, n_points):
         self.n_alloc = int(n_points)
@@ -275,68 +323,31 @@ class NearestLBVH:
         """query_points: int64[n,2] scaled host points, or None for the query map's own vertices, optionally a [begin, end)
         sub-range (a shard).  max_dist (scaled units, None: unlimited): only edges within it qualify, the others' points
         miss.  records / dist: whether the call fills them.  Returns the number of points."""
-        base = 1 - query_map_id
         md = -1 if max_dist is None else int(max_dist)
         rec, dst = (self.records if records else None), (self.dist if dist else None)
-        if query_points is not None:
-            pts = np.ascontiguousarray(query_points, dtype=np.int64).reshape(-1, 2)
-            n = pts.shape[0]
-            assert n <= self.n_alloc
-            buf = self.h.alloc(16 * max(1, n)).from_host(pts)
-            try:
-                self.h.nearest_query(base, query_map_id, buf, 0, n, self.eids, rec, dst, md)
-            finally:
-                buf.free()
-        else:
-            b, e = point_range if point_range is not None else (0, self.ctx_.get_map(query_map_id).n_points)
-            n = e - b
-            assert n <= self.n_alloc
-            self.h.nearest_query(base, query_map_id, None, b, n, self.eids, rec, dst, md)
-        self.n, self.has_records, self.has_dist = n, bool(records), bool(dist)
+        n, _ = self._over_points(query_map_id, query_points, point_range,
+                                 lambda buf, b, n: self.h.nearest_query(1 - query_map_id, query_map_id, buf, b, n, self.eids, rec, dst, md))
+        self.n = self.rows_ = n
+        self.has_records, self.has_dist = bool(records), bool(dist)
         return n
-
-    def get_eids(self):
-        return self.eids.to_host(np.uint32, self.n)
-
-    def get_records(self):
-        """-> NEAR_DTYPE rows; ValueError after a Query with records=False"""
-        if not self.has_records:
-            raise ValueError("the last Query ran with records=False")
-        return self.records.to_host(_capi.NEAR_DTYPE, self.n)
-
-    def get_dist(self):
-        if not self.has_dist:
-            raise ValueError("the last Query ran with dist=False")
-        return self.dist.to_host(np.float64, self.n)
-
-    @staticmethod
-    def exact(records):
-        """NEAR_DTYPE rows -> [(eid, where, num, den)] with num (signed) and den as Python ints: d^2 = num^2 / den where
-        `where` is 0, num / den (den = 1) at an end"""
-        return [(int(r["eid"]), int(r["where"]), (int(r["num_hi"]) << 64) + int(r["num_lo"]), (int(r["den_hi"]) << 64) + int(r["den_lo"])) for r in records]
 
     def nums(self):
         """-> the exact num of every record as a list of Python ints"""
         return [t[2] for t in self.exact(self.get_records())]
 
     def free(self):
-        for b in (self.eids, self.records, self.dist):
-            if b is not None:
-                b.free()
-        self.eids = self.records = self.dist = None
+        self._free("eids", "records", "dist")
 
 
-class WithinLBVH:
+class WithinLBVH(_DistanceQuery):
     """Every edge of the indexed base map within max_dist of each query point (rj_within_query), mirroring NearestLBVH: a
-    CSR over the points -- offsets, and per pair the eid (ascending per point), the exact record and the distance."""
+    CSR over the points -- offsets, and one row per pair: the eid (ascending per point), the exact record and the distance."""
 
     def __init__(self, dctx):
-        self.ctx_ = dctx
-        self.h = dctx.handle
-        self.offsets = self.eids = self.records = self.dist = None
-        self.n = self.n_pairs = 0
+        super().__init__(dctx)
+        self.offsets = None
+        self.n_pairs = 0
         self.n_alloc = self.capacity = 0
-        self.has_records = self.has_dist = False
         self.counts_ = dict.fromkeys(_capi.WITHIN_COUNTS, 0)
 
     def Init(self, n_points, pair_capacity):
@@ -346,37 +357,27 @@ class WithinLBVH:
         self._alloc_pairs(int(pair_capacity))
 
     def _alloc_pairs(self, capacity):
-        for b in (self.eids, self.records, self.dist):
-            if b is not None:
-                b.free()
+        self._free("eids", "records", "dist")
         self.capacity = capacity
         self.eids = self.h.alloc(4 * max(1, capacity))
         self.records = self.h.alloc(_capi.NEAR_DTYPE.itemsize * max(1, capacity))
         self.dist = self.h.alloc(8 * max(1, capacity))
 
     def _call(self, query_map_id, query_points, point_range, max_dist, capacity, rec, dst):
-        base = 1 - query_map_id
         eids = self.eids if capacity else None
-        if query_points is not None:
-            pts = np.ascontiguousarray(query_points, dtype=np.int64).reshape(-1, 2)
-            n = pts.shape[0]
-            assert n <= self.n_alloc
-            buf = self.h.alloc(16 * max(1, n)).from_host(pts)
-            try:
-                return n, self.h.within_query(base, query_map_id, buf, 0, n, max_dist, capacity, self.offsets, eids, rec, dst)
-            finally:
-                buf.free()
-        b, e = point_range if point_range is not None else (0, self.ctx_.get_map(query_map_id).n_points)
-        n = e - b
-        assert n <= self.n_alloc
-        return n, self.h.within_query(base, query_map_id, None, b, n, max_dist, capacity, self.offsets, eids, rec, dst)
+        return self._over_points(query_map_id, query_points, point_range,
+                                 lambda buf, b, n: self.h.within_query(1 - query_map_id, query_map_id, buf, b, n, max_dist, capacity, self.offsets, eids, rec, dst))
+
+    def _set(self, n, n_pairs, counts, records, dist):
+        self.n, self.n_pairs, self.rows_, self.counts_ = n, n_pairs, n_pairs, counts
+        self.has_records, self.has_dist = bool(records), bool(dist)
 
     def Query(self, query_map_id, query_points=None, point_range=None, max_dist=0, records=True, dist=True, grow=True):
         """query_points: int64[n,2] scaled host points, or None for the query map's own vertices, optionally a [begin, end)
         sub-range (a shard).  max_dist (scaled units, 0 .. 2^48): every edge with d <= max_dist is listed.  records / dist:
         whether the call fills them.  grow: on an overflow (or with a capacity of 0) the pair arrays are allocated again at
         the true count and the call repeats once; otherwise _capi.WithinOverflow with the true counts.  Returns n_pairs."""
-        self.n_pairs = 0
+        self.n_pairs = self.rows_ = 0
         self.has_records = self.has_dist = False
         args = (query_map_id, query_points, point_range, int(max_dist))
         if self.capacity == 0:  # (a capacity of 0 is the counting call: it sizes the arrays)
@@ -393,34 +394,18 @@ class WithinLBVH:
                     raise
                 self._alloc_pairs(e.counts["n_pairs"])
                 n, counts = self._call(*args, self.capacity, self.records if records else None, self.dist if dist else None)
-        self.n, self.n_pairs, self.counts_ = n, counts["n_pairs"], counts
-        self.has_records, self.has_dist = bool(records), bool(dist)
+        self._set(n, counts["n_pairs"], counts, records, dist)
         return self.n_pairs
 
     def Count(self, query_map_id, query_points=None, point_range=None, max_dist=0):
         """the counting call: how many edges lie within max_dist of each point -> uint64[n]; nothing but the offsets and the
         counts is written"""
         n, counts = self._call(query_map_id, query_points, point_range, int(max_dist), 0, None, None)
-        self.n, self.n_pairs, self.counts_ = n, 0, counts
-        self.has_records = self.has_dist = False
+        self._set(n, 0, counts, False, False)
         return np.diff(self.get_offsets())
 
     def get_offsets(self):
         return self.offsets.to_host(np.uint64, self.n + 1)
-
-    def get_eids(self):
-        return self.eids.to_host(np.uint32, self.n_pairs)
-
-    def get_records(self):
-        """-> NEAR_DTYPE rows, one per pair; ValueError after a Query with records=False"""
-        if not self.has_records:
-            raise ValueError("the last Query ran with records=False")
-        return self.records.to_host(_capi.NEAR_DTYPE, self.n_pairs)
-
-    def get_dist(self):
-        if not self.has_dist:
-            raise ValueError("the last Query ran with dist=False")
-        return self.dist.to_host(np.float64, self.n_pairs)
 
     def to_csr(self):
         """-> (indptr int64[n + 1], eids uint32[n_pairs]): row i lists the edges within the distance of point i, ascending"""
@@ -430,13 +415,8 @@ class WithinLBVH:
         """the counts of the last call: n_pairs, n_points_hit, max_per_point"""
         return dict(self.counts_)
 
-    exact = staticmethod(NearestLBVH.exact)
-
     def free(self):
-        for b in (self.offsets, self.eids, self.records, self.dist):
-            if b is not None:
-                b.free()
-        self.offsets = self.eids = self.records = self.dist = None
+        self._free("offsets", "eids", "records", "dist")
         self.capacity = 0
 
 

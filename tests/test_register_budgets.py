@@ -4,28 +4,20 @@ kernel one register more -- or a source change that does -- silently costs a res
 0.79 -> 0.83 ms), so the budgets are pinned here against the resource report of the build
 (`make` writes rayjoin_amd/csrc/resource_usage.txt: -Rpass-analysis=kernel-resource-usage)."""
 import os
-import re
+import sys
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPORT = os.path.join(os.path.dirname(HERE), "rayjoin_amd", "csrc", "resource_usage.txt")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import resource_report  # noqa: E402
+
+REPORT = "resource_usage.txt"
 
 
 def _kernels():
-    if not os.path.exists(REPORT):
-        pytest.skip("no resource report: build the library first (__graft_entry__.build)")
-    out, name = {}, None
-    for line in open(REPORT):
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            out[name][m.group(1).strip()] = int(m.group(2))
-    return out
+    if not os.path.exists(resource_report.path(REPORT)):
+        pytest.skip(resource_report.MISSING)
+    return resource_report.kernels(REPORT)
 
 
 def _one(kernels, fragment):

@@ -3,24 +3,17 @@ limbs in registers: no scratch memory and at most 128 VGPRs, in either instantia
 report of the build (`make` writes rayjoin_amd/csrc/resource_usage_within.txt: -Rpass-analysis=kernel-resource-usage)."""
 import os
 import re
+import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPORT = os.path.join(os.path.dirname(HERE), "rayjoin_amd", "csrc", "resource_usage_within.txt")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import resource_report  # noqa: E402
+
+REPORT = "resource_usage_within.txt"
 
 
 def kernels():
-    assert os.path.exists(REPORT), "no resource report: build the library first (__graft_entry__.build)"
-    out, name = {}, None
-    for line in open(REPORT):
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            out[name][m.group(1).strip()] = int(m.group(2))
-    return out
+    assert os.path.exists(resource_report.path(REPORT)), resource_report.MISSING
+    return resource_report.kernels(REPORT)
 
 
 def test_the_traversal_kernel_uses_no_scratch():
