@@ -37,6 +37,7 @@ XSECT_DTYPE = np.dtype(
 FACE_DTYPE = np.dtype([("face", "<i4", (2,)), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
 # rj_ring: a closed boundary of a chain map -- its face, RJ_RING_MIXED, its smallest half-chain, twice its signed area
 RING_DTYPE = np.dtype([("face", "<i4"), ("flags", "<u4"), ("leader", "<u4"), ("_pad", "<u4"), ("area2_lo", "<u8"), ("area2_hi", "<i8")])
+OVERLAY_MAP_COUNTS = ("n_chains", "n_points", "n_faces")  # (Handle.overlay_map gives and takes them as a plain tuple)
 RINGS_COUNTS = ("n_rings", "n_halves", "n_points", "n_mixed", "n_skipped")
 RJ_POLY_NONE = 0xFFFFFFFF  # rj_rings_polygons' parent of a ring of face 0 and of an orphan
 # rj_polygon: one outer ring with its holes -- its face, the shell's ring index, its holes, twice its area
@@ -341,6 +342,14 @@ def _ptr(a):
     return a.ctypes.data
 
 
+def _tol_words(tol):
+    """a tolerance, a Python int in [0, 2^128) -> its (low, high) 64-bit words"""
+    tol = int(tol)
+    if not 0 <= tol < 1 << 128:
+        raise ValueError("tol must lie in [0, 2^128), not %d" % tol)
+    return tol & 0xFFFFFFFFFFFFFFFF, tol >> 64
+
+
 class DeviceBuffer:
     """Device memory owned through the C ABI (rj_dev_alloc) for hosts without torch."""
 
@@ -412,6 +421,20 @@ class Handle:
     def _check(self, rc):
         if rc != RJ_OK:
             raise RayJoinError(rc, self.L.rj_last_error_string(self.h).decode())
+
+    def _counted(self, fn, names, overflow, *args, tail=(), invalid=None):
+        """fn(h, *args, counts, *tail) of a library call that reports len(names) uint64 counts -> the counts as a dict by
+        name.  RJ_E_OVERFLOW raises `overflow` with that dict; invalid = (cls, name): RJ_E_INVALID with a nonzero count
+        `name` raises cls with it; any other failure is _check's RayJoinError."""
+        counts = (_u64 * len(names))()
+        rc = fn(self.h, *args, counts, *tail)
+        named = dict(zip(names, (int(v) for v in counts)))
+        if rc == RJ_E_OVERFLOW:
+            raise overflow(self.L.rj_last_error_string(self.h).decode(), named)
+        if rc == RJ_E_INVALID and invalid is not None and named[invalid[1]]:
+            raise invalid[0](self.L.rj_last_error_string(self.h).decode(), named[invalid[1]])
+        self._check(rc)
+        return named
 
     def set_stream(self, stream_ptr):
         self._check(self.L.rj_set_stream(self.h, stream_ptr))
@@ -628,131 +651,84 @@ class Handle:
                     left_dev, right_dev, face_pairs_dev, origin_dev=None, op=None):
         """rj_overlay_map into the caller's device arrays; capacities = (chains, points, faces).  Returns the counts
         (chains, points, faces); MapOverflow (with the true counts) past a capacity.  op = (how, by): rj_overlay_map_op"""
-        counts = (_u64 * 3)()
         cc, pc, fc = (int(v) for v in capacities)
-        args = (self.h, _ptr(xsects0_dev), _ptr(xsects1_dev), n, _ptr(vertex_face0_dev), _ptr(vertex_face1_dev), int(flags), cc, pc, fc,
-                _ptr(xy_dev), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev), _ptr(face_pairs_dev), _ptr(origin_dev), counts)
-        rc = self.L.rj_overlay_map(*args) if op is None else self.L.rj_overlay_map_op(*args, int(op[0]), int(op[1]))
-        if rc == RJ_E_OVERFLOW:
-            raise MapOverflow(self.L.rj_last_error_string(self.h).decode(), tuple(counts))
-        self._check(rc)
-        return tuple(counts)
+        fn, tail = (self.L.rj_overlay_map, ()) if op is None else (self.L.rj_overlay_map_op, (int(op[0]), int(op[1])))
+        try:
+            return tuple(self._counted(fn, OVERLAY_MAP_COUNTS, MapOverflow, _ptr(xsects0_dev), _ptr(xsects1_dev), n, _ptr(vertex_face0_dev),
+                                       _ptr(vertex_face1_dev), int(flags), cc, pc, fc, _ptr(xy_dev), _ptr(row_index_dev), _ptr(left_dev),
+                                       _ptr(right_dev), _ptr(face_pairs_dev), _ptr(origin_dev), tail=tail).values())
+        except MapOverflow as e:
+            e.counts = tuple(e.counts.values())  # (this call's counts are a plain tuple, in and out)
+            raise
 
     def map_rings(self, xy_dev, n_points, row_index_dev, left_dev, right_dev, n_chains, flags, capacities, rings_dev, ring_first_dev,
                   ring_half_dev, ring_row_dev, ring_xy_dev):
         """rj_map_rings of a chain map in device memory into the caller's device arrays; capacities = (rings, half-chains,
         points).  Returns the counts as a dict (RINGS_COUNTS); RingsOverflow (with the true counts) past a capacity."""
-        counts = (_u64 * 5)()
-        rc_, hc, pc = (int(v) for v in capacities)
-        rc = self.L.rj_map_rings(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev), int(n_chains),
-                                 int(flags), rc_, hc, pc, _ptr(rings_dev), _ptr(ring_first_dev), _ptr(ring_half_dev), _ptr(ring_row_dev),
-                                 _ptr(ring_xy_dev), counts)
-        named = dict(zip(RINGS_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise RingsOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        self._check(rc)
-        return named
+        rc, hc, pc = (int(v) for v in capacities)
+        return self._counted(self.L.rj_map_rings, RINGS_COUNTS, RingsOverflow, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), _ptr(left_dev),
+                             _ptr(right_dev), int(n_chains), int(flags), rc, hc, pc, _ptr(rings_dev), _ptr(ring_first_dev), _ptr(ring_half_dev),
+                             _ptr(ring_row_dev), _ptr(ring_xy_dev))
 
     def rings_polygons(self, rings_dev, n_rings, ring_row_dev, ring_xy_dev, n_points, flags, capacities, parent_dev, polygons_dev,
                        poly_first_dev, poly_ring_dev):
         """rj_rings_polygons of rj_map_rings' arrays in device memory into the caller's device arrays; capacities =
         (polygons, members); parent_dev may be None.  Returns the counts as a dict (POLYGONS_COUNTS); PolygonsOverflow
         (with the true counts) past a capacity."""
-        counts = (_u64 * 5)()
         pc, mc = (int(v) for v in capacities)
-        rc = self.L.rj_rings_polygons(self.h, _ptr(rings_dev), int(n_rings), _ptr(ring_row_dev), _ptr(ring_xy_dev), int(n_points), int(flags),
-                                      pc, mc, _ptr(parent_dev), _ptr(polygons_dev), _ptr(poly_first_dev), _ptr(poly_ring_dev), counts)
-        named = dict(zip(POLYGONS_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise PolygonsOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        self._check(rc)
-        return named
+        return self._counted(self.L.rj_rings_polygons, POLYGONS_COUNTS, PolygonsOverflow, _ptr(rings_dev), int(n_rings), _ptr(ring_row_dev),
+                             _ptr(ring_xy_dev), int(n_points), int(flags), pc, mc, _ptr(parent_dev), _ptr(polygons_dev), _ptr(poly_first_dev),
+                             _ptr(poly_ring_dev))
 
     def rings_map(self, ring_row_dev, ring_xy_dev, n_points, ring_face_dev, face_stride, n_rings, flags, capacities, xy_dev, row_index_dev,
                   left_dev, right_dev):
         """rj_rings_map of labelled rings in device memory (ring_face_dev read through face_stride bytes) into the caller's
         device arrays; capacities = (chains, points).  Returns the counts as a dict (RINGS_MAP_COUNTS); RingsMapOverflow
         (with the true counts) past a capacity."""
-        counts = (_u64 * 7)()
         cc, pc = (int(v) for v in capacities)
-        rc = self.L.rj_rings_map(self.h, _ptr(ring_row_dev), _ptr(ring_xy_dev), int(n_points), _ptr(ring_face_dev), int(face_stride),
-                                 int(n_rings), int(flags), cc, pc, _ptr(xy_dev), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev), counts)
-        named = dict(zip(RINGS_MAP_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise RingsMapOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        self._check(rc)
-        return named
+        return self._counted(self.L.rj_rings_map, RINGS_MAP_COUNTS, RingsMapOverflow, _ptr(ring_row_dev), _ptr(ring_xy_dev), int(n_points),
+                             _ptr(ring_face_dev), int(face_stride), int(n_rings), int(flags), cc, pc, _ptr(xy_dev), _ptr(row_index_dev),
+                             _ptr(left_dev), _ptr(right_dev))
 
     def map_crossings(self, xy_dev, n_points, row_index_dev, n_chains, capacity, out_dev, flags=0):
         """rj_map_crossings of a chain map in device memory into the caller's device array of `capacity` rj_crossing records
         (capacity 0, out_dev None: the sizing call).  Returns the counts as a dict (CROSSINGS_COUNTS); CrossingsOverflow (with
         the true counts) past the capacity."""
-        counts = (_u64 * 7)()
-        rc = self.L.rj_map_crossings(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains), int(flags), int(capacity), _ptr(out_dev),
-                                     counts)
-        named = dict(zip(CROSSINGS_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise CrossingsOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        self._check(rc)
-        return named
+        return self._counted(self.L.rj_map_crossings, CROSSINGS_COUNTS, CrossingsOverflow, _ptr(xy_dev), int(n_points), _ptr(row_index_dev),
+                             int(n_chains), int(flags), int(capacity), _ptr(out_dev))
 
     def map_node(self, xy_dev, n_points, row_index_dev, n_chains, cross_dev, n_cross, flags, capacity, out_xy_dev, out_row_index_dev,
                  edge_origin_dev=None):
         """rj_map_node of a chain map and its rj_map_crossings records, both in device memory, into the caller's device arrays
         of `capacity` points, n_chains + 1 row entries and (or None) n_edges origins (capacity 0, arrays None: the sizing
         call).  Returns the counts as a dict (NODE_COUNTS); NodeOverflow (with the true counts) past the capacity."""
-        counts = (_u64 * 8)()
-        rc = self.L.rj_map_node(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains), _ptr(cross_dev), int(n_cross), int(flags),
-                                int(capacity), _ptr(out_xy_dev), _ptr(out_row_index_dev), _ptr(edge_origin_dev), counts)
-        named = dict(zip(NODE_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise NodeOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        self._check(rc)
-        return named
+        return self._counted(self.L.rj_map_node, NODE_COUNTS, NodeOverflow, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains),
+                             _ptr(cross_dev), int(n_cross), int(flags), int(capacity), _ptr(out_xy_dev), _ptr(out_row_index_dev),
+                             _ptr(edge_origin_dev))
 
     def map_snap(self, xy_dev, n_points, row_index_dev, n_chains, cross_dev, n_cross, flags, capacity, out_xy_dev, out_row_index_dev,
                  edge_origin_dev=None):
         """rj_map_snap of a chain map and its rj_map_crossings records, both in device memory, into the caller's device arrays
         of `capacity` points, n_chains + 1 row entries and (or None) n_edges origins (capacity 0, arrays None: the sizing
         call).  Returns the counts as a dict (SNAP_COUNTS); SnapOverflow (with the true counts) past the capacity."""
-        counts = (_u64 * len(SNAP_COUNTS))()
-        rc = self.L.rj_map_snap(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains), _ptr(cross_dev), int(n_cross), int(flags),
-                                int(capacity), _ptr(out_xy_dev), _ptr(out_row_index_dev), _ptr(edge_origin_dev), counts)
-        named = dict(zip(SNAP_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise SnapOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        self._check(rc)
-        return named
+        return self._counted(self.L.rj_map_snap, SNAP_COUNTS, SnapOverflow, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains),
+                             _ptr(cross_dev), int(n_cross), int(flags), int(capacity), _ptr(out_xy_dev), _ptr(out_row_index_dev),
+                             _ptr(edge_origin_dev))
 
     def map_simplify(self, xy_dev, n_points, row_index_dev, n_chains, tol, capacity, out_xy_dev, out_row_index_dev, origin_dev=None, flags=0):
         """rj_map_simplify of a chain map in device memory into the caller's device arrays of `capacity` points, n_chains + 1
         row entries and (or None) `capacity` origins (capacity 0, arrays None: the sizing call); tol a Python int in
         [0, 2^128).  Returns the counts as a dict (SIMPLIFY_COUNTS); SimplifyOverflow (with the true counts) past the capacity."""
-        tol = int(tol)
-        if not 0 <= tol < 1 << 128:
-            raise ValueError("tol must lie in [0, 2^128), not %d" % tol)
-        counts = (_u64 * 6)()
-        rc = self.L.rj_map_simplify(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains), tol & 0xFFFFFFFFFFFFFFFF, tol >> 64,
-                                    int(flags), int(capacity), _ptr(out_xy_dev), _ptr(out_row_index_dev), _ptr(origin_dev), counts)
-        named = dict(zip(SIMPLIFY_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise SimplifyOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        self._check(rc)
-        return named
+        return self._counted(self.L.rj_map_simplify, SIMPLIFY_COUNTS, SimplifyOverflow, _ptr(xy_dev), int(n_points), _ptr(row_index_dev),
+                             int(n_chains), *_tol_words(tol), int(flags), int(capacity), _ptr(out_xy_dev), _ptr(out_row_index_dev), _ptr(origin_dev))
 
     def map_faces(self, xy_dev, n_points, row_index_dev, n_chains, left_dev, right_dev, faces_dev=None, face_capacity=0, in_left_dev=None,
                   in_right_dev=None, flags=0):
         """rj_map_faces of a chain map in device memory: the computed faces into left_dev / right_dev (n_chains int32 each) and,
         where faces_dev is given, `face_capacity` rj_face records; in_left_dev / in_right_dev: the labels to check, or None.
         Returns the counts as a dict (MAP_FACES_COUNTS); FacesOverflow (with the true counts) past the capacity."""
-        counts = (_u64 * 7)()
-        rc = self.L.rj_map_faces(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains), _ptr(in_left_dev), _ptr(in_right_dev),
-                                 int(flags), int(face_capacity), _ptr(left_dev), _ptr(right_dev), _ptr(faces_dev), counts)
-        named = dict(zip(MAP_FACES_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise FacesOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        self._check(rc)
-        return named
+        return self._counted(self.L.rj_map_faces, MAP_FACES_COUNTS, FacesOverflow, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), int(n_chains),
+                             _ptr(in_left_dev), _ptr(in_right_dev), int(flags), int(face_capacity), _ptr(left_dev), _ptr(right_dev), _ptr(faces_dev))
 
     def map_eliminate(self, xy_dev, n_points, row_index_dev, left_dev, right_dev, n_chains, tol, capacities, out_left_dev, out_right_dev,
                       out_xy_dev=None, out_row_index_dev=None, chain_origin_dev=None, faces_dev=None, flags=0):
@@ -761,19 +737,11 @@ class Handle:
         is given, the rj_elim_face records.  capacities = (faces, chains, points); (0, 0, 0) with arrays None is the sizing
         call.  tol a Python int in [0, 2^128).  Returns the counts as a dict (ELIMINATE_COUNTS); EliminateOverflow (with the
         true counts) past a capacity."""
-        tol = int(tol)
-        if not 0 <= tol < 1 << 128:
-            raise ValueError("tol must lie in [0, 2^128), not %d" % tol)
+        tol_lo, tol_hi = _tol_words(tol)
         fc, cc, pc = (int(v) for v in capacities)
-        counts = (_u64 * len(ELIMINATE_COUNTS))()
-        rc = self.L.rj_map_eliminate(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev), int(n_chains),
-                                     tol & 0xFFFFFFFFFFFFFFFF, tol >> 64, int(flags), fc, cc, pc, _ptr(faces_dev), _ptr(out_left_dev), _ptr(out_right_dev),
-                                     _ptr(out_xy_dev), _ptr(out_row_index_dev), _ptr(chain_origin_dev), counts)
-        named = dict(zip(ELIMINATE_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise EliminateOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        self._check(rc)
-        return named
+        return self._counted(self.L.rj_map_eliminate, ELIMINATE_COUNTS, EliminateOverflow, _ptr(xy_dev), int(n_points), _ptr(row_index_dev),
+                             _ptr(left_dev), _ptr(right_dev), int(n_chains), tol_lo, tol_hi, int(flags), fc, cc, pc, _ptr(faces_dev), _ptr(out_left_dev),
+                             _ptr(out_right_dev), _ptr(out_xy_dev), _ptr(out_row_index_dev), _ptr(chain_origin_dev))
 
     def map_dissolve(self, xy_dev, n_points, row_index_dev, left_dev, right_dev, n_chains, class_dev, n_labels, capacities, out_left_dev, out_right_dev,
                      out_xy_dev, out_row_index_dev, chain_origin_dev=None, chain_out_dev=None, classes_dev=None, flags=0):
@@ -784,17 +752,10 @@ class Handle:
         as a dict (DISSOLVE_COUNTS); DissolveOverflow (with the true counts) past a capacity, DissolveUnmapped (with
         n_unmapped) for nonzero labels outside the table."""
         kc, cc, pc = (int(v) for v in capacities)
-        counts = (_u64 * len(DISSOLVE_COUNTS))()
-        rc = self.L.rj_map_dissolve(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev), int(n_chains), _ptr(class_dev),
-                                    int(n_labels), int(flags), kc, cc, pc, _ptr(classes_dev), _ptr(out_left_dev), _ptr(out_right_dev), _ptr(out_xy_dev),
-                                    _ptr(out_row_index_dev), _ptr(chain_origin_dev), _ptr(chain_out_dev), counts)
-        named = dict(zip(DISSOLVE_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise DissolveOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        if rc == RJ_E_INVALID and named["n_unmapped"]:
-            raise DissolveUnmapped(self.L.rj_last_error_string(self.h).decode(), named["n_unmapped"])
-        self._check(rc)
-        return named
+        return self._counted(self.L.rj_map_dissolve, DISSOLVE_COUNTS, DissolveOverflow, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), _ptr(left_dev),
+                             _ptr(right_dev), int(n_chains), _ptr(class_dev), int(n_labels), int(flags), kc, cc, pc, _ptr(classes_dev), _ptr(out_left_dev),
+                             _ptr(out_right_dev), _ptr(out_xy_dev), _ptr(out_row_index_dev), _ptr(chain_origin_dev), _ptr(chain_out_dev),
+                             invalid=(DissolveUnmapped, "n_unmapped"))
 
     def map_neighbours(self, xy_dev, n_points, row_index_dev, left_dev, right_dev, n_chains, capacities, faces_dev=None, offsets_dev=None, entries_dev=None,
                        flags=0):
@@ -804,16 +765,9 @@ class Handle:
         neighbours.  Returns the counts as a dict (NEIGHBOURS_COUNTS); NeighboursOverflow (with the true counts) past a capacity,
         NeighboursNodePairs (with the count) where the nodes give 2^32 directed pairs or more."""
         fc, ec = (int(v) for v in capacities)
-        counts = (_u64 * len(NEIGHBOURS_COUNTS))()
-        rc = self.L.rj_map_neighbours(self.h, _ptr(xy_dev), int(n_points), _ptr(row_index_dev), _ptr(left_dev), _ptr(right_dev), int(n_chains), int(flags), fc,
-                                      ec, _ptr(faces_dev), _ptr(offsets_dev), _ptr(entries_dev), counts)
-        named = dict(zip(NEIGHBOURS_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise NeighboursOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        if rc == RJ_E_INVALID and named["n_node_pairs_raw"]:
-            raise NeighboursNodePairs(self.L.rj_last_error_string(self.h).decode(), named["n_node_pairs_raw"])
-        self._check(rc)
-        return named
+        return self._counted(self.L.rj_map_neighbours, NEIGHBOURS_COUNTS, NeighboursOverflow, _ptr(xy_dev), int(n_points), _ptr(row_index_dev),
+                             _ptr(left_dev), _ptr(right_dev), int(n_chains), int(flags), fc, ec, _ptr(faces_dev), _ptr(offsets_dev), _ptr(entries_dev),
+                             invalid=(NeighboursNodePairs, "n_node_pairs_raw"))
 
     def face_points(self, label_dev, n, capacities, value_dev=None, value_stride=1, face_label_dev=None, n_face_labels=0, faces_dev=None, offsets_dev=None,
                     members_dev=None, flags=0):
@@ -825,14 +779,8 @@ class Handle:
         the points.  capacities = (faces, members); (0, 0) with arrays None is the sizing call.  Returns the counts as a dict
         (FACE_POINTS_COUNTS); FacePointsOverflow (with the true counts) past a capacity."""
         fc, mc = (int(v) for v in capacities)
-        counts = (_u64 * len(FACE_POINTS_COUNTS))()
-        rc = self.L.rj_face_points(self.h, _ptr(label_dev), int(n), _ptr(value_dev), int(value_stride), _ptr(face_label_dev), int(n_face_labels), int(flags),
-                                   fc, mc, _ptr(faces_dev), _ptr(offsets_dev), _ptr(members_dev), counts)
-        named = dict(zip(FACE_POINTS_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise FacePointsOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        self._check(rc)
-        return named
+        return self._counted(self.L.rj_face_points, FACE_POINTS_COUNTS, FacePointsOverflow, _ptr(label_dev), int(n), _ptr(value_dev), int(value_stride),
+                             _ptr(face_label_dev), int(n_face_labels), int(flags), fc, mc, _ptr(faces_dev), _ptr(offsets_dev), _ptr(members_dev))
 
     def neighbours_labels(self, faces_dev, n_faces, label_dev):
         """label_dev[k] = the label of record k of rj_map_neighbours' faces_dev, on the device (rj_neighbours_labels)"""
@@ -861,14 +809,8 @@ class Handle:
         None) and sqrt(d^2) into dist_dev (float64, or None), each of pair_capacity entries.  pair_capacity 0 is the counting
         call.  Returns the counts as a dict (WITHIN_COUNTS); WithinOverflow (with the true counts) past the capacity.
         Synchronous."""
-        counts = (_u64 * len(WITHIN_COUNTS))()
-        rc = self.L.rj_within_query(self.h, base_map_id, query_map_id, _ptr(pts_dev), int(pt_begin), int(n), int(max_dist), int(pair_capacity),
-                                    _ptr(offsets_dev), _ptr(eid_dev), _ptr(rec_dev), _ptr(dist_dev), counts)
-        named = dict(zip(WITHIN_COUNTS, (int(v) for v in counts)))
-        if rc == RJ_E_OVERFLOW:
-            raise WithinOverflow(self.L.rj_last_error_string(self.h).decode(), named)
-        self._check(rc)
-        return named
+        return self._counted(self.L.rj_within_query, WITHIN_COUNTS, WithinOverflow, base_map_id, query_map_id, _ptr(pts_dev), int(pt_begin), int(n),
+                             int(max_dist), int(pair_capacity), _ptr(offsets_dev), _ptr(eid_dev), _ptr(rec_dev), _ptr(dist_dev))
 
     def last_ms(self, which):
         ms = C.c_float()

@@ -79,6 +79,73 @@ from . import _capi
 from .maps import Context
 
 
+class _Owned:
+    """The DeviceBuffers of a call while it runs, as a context manager: alloc(nbytes) records the buffer, and leaving the
+    block -- by any exception, or at its end -- frees every buffer still owned, each once.  release() hands them to the
+    caller: an output's owner releases when its call has succeeded, a staging temporary's owner never does."""
+
+    def __init__(self, handle):
+        self.handle, self.bufs = handle, []
+
+    def alloc(self, nbytes):
+        self.bufs.append(self.handle.alloc(nbytes))
+        return self.bufs[-1]
+
+    def release(self):
+        self.bufs = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        bufs, self.bufs = self.bufs, []
+        for b in bufs:
+            b.free()
+
+
+def _sizing_counts(call, overflow, *args, **kw):
+    """The counts of a sizing call (zero capacities, no arrays in args), whether it returned them or raised `overflow` with them"""
+    try:
+        return call(*args, **kw)
+    except overflow as e:
+        return e.counts
+
+
+def _over_points(op, query_map_id, query_points, point_range, call):
+    """call(device points or None, begin, n) for a query operator (its h, ctx_, n_alloc) over int64[n,2] scaled host points,
+    staged for the call and freed behind it, or over the query map's own vertices, optionally a [begin, end) sub-range (a
+    shard) -> (n, what call returned)"""
+    if query_points is not None:
+        pts = np.ascontiguousarray(query_points, dtype=np.int64).reshape(-1, 2)
+        n = pts.shape[0]
+        assert n <= op.n_alloc
+        with _Owned(op.h) as tmp:
+            return n, call(tmp.alloc(16 * max(1, n)).from_host(pts), 0, n)
+    b, e = point_range if point_range is not None else (0, op.ctx_.get_map(query_map_id).n_points)
+    n = e - b
+    assert n <= op.n_alloc
+    return n, call(None, b, n)
+
+
+def _stage_map(own, m, sides):
+    """The host image of a map in temporaries of `own` -> [xy, row_index] and, with sides, [.., left, right]"""
+    cols = [(m.pts, np.int64, 16 * max(1, m.n_points)), (m.row_index, np.uint32, 4 * (m.n_chains + 1))]
+    if sides:
+        cols += [(m.left, np.int32, 4 * max(1, m.n_chains)), (m.right, np.int32, 4 * max(1, m.n_chains))]
+    return [own.alloc(nbytes).from_host(np.ascontiguousarray(a, dtype=dtype)) for a, dtype, nbytes in cols]
+
+
+class _OwnsBuffers:
+    """An object that owns device buffers: _buffers names the attributes that hold them (None: not there).  free() frees
+    them; a second free() is harmless, as DeviceBuffer.free is."""
+    _buffers = ()
+
+    def free(self):
+        for name in self._buffers:
+            if getattr(self, name) is not None:
+                getattr(self, name).free()
+
+
 class DeviceContext:
     """A maps.Context plus its GPU residency: uploads both maps, owns the rj_handle."""
 
@@ -136,29 +203,17 @@ class DeviceContext:
     def Rings(self, im, **kw):
         """face_rings of input map `im` (its host image goes to temporaries on the device): the boundaries of its faces"""
         m = self.get_map(im)
-        h = self.handle
-        bufs = [h.alloc(16 * max(1, m.n_points)).from_host(np.ascontiguousarray(m.pts, dtype=np.int64)),
-                h.alloc(4 * (m.n_chains + 1)).from_host(np.ascontiguousarray(m.row_index, dtype=np.uint32)),
-                h.alloc(4 * max(1, m.n_chains)).from_host(np.ascontiguousarray(m.left, dtype=np.int32)),
-                h.alloc(4 * max(1, m.n_chains)).from_host(np.ascontiguousarray(m.right, dtype=np.int32))]
-        try:
-            return face_rings(h, bufs[0], m.n_points, bufs[1], bufs[2], bufs[3], m.n_chains, **kw)
-        finally:
-            for b in bufs:
-                b.free()
+        with _Owned(self.handle) as tmp:
+            xy, row_index, left, right = _stage_map(tmp, m, True)
+            return face_rings(self.handle, xy, m.n_points, row_index, left, right, m.n_chains, **kw)
 
     def Crossings(self, im, **kw):
         """map_crossings of input map `im` (its host image goes to temporaries on the device): empty when the map is a
         planar subdivision"""
         m = self.get_map(im)
-        h = self.handle
-        bufs = [h.alloc(16 * max(1, m.n_points)).from_host(np.ascontiguousarray(m.pts, dtype=np.int64)),
-                h.alloc(4 * (m.n_chains + 1)).from_host(np.ascontiguousarray(m.row_index, dtype=np.uint32))]
-        try:
-            return map_crossings(h, bufs[0], m.n_points, bufs[1], m.n_chains, **kw)
-        finally:
-            for b in bufs:
-                b.free()
+        with _Owned(self.handle) as tmp:
+            xy, row_index = _stage_map(tmp, m, False)
+            return map_crossings(self.handle, xy, m.n_points, row_index, m.n_chains, **kw)
 
     def close(self):
         self.handle.close()
@@ -208,6 +263,8 @@ class LSILBVH:
 
 
 class PIPLBVH:
+    _query = "pip_query"  # the handle's call that Query makes
+
     def __init__(self, dctx):
         self.ctx_ = dctx
         self.h = dctx.handle
@@ -223,21 +280,10 @@ class PIPLBVH:
     def Query(self, query_map_id, query_points=None, point_range=None):
         """query_points: int64[n,2] scaled host points, or None for the query map's own vertices
         (RunPIPQuery, src/run_query.cu:346), optionally a [begin, end) sub-range (a shard)."""
-        base = 1 - query_map_id
-        if query_points is not None:
-            pts = np.ascontiguousarray(query_points, dtype=np.int64).reshape(-1, 2)
-            n = pts.shape[0]
-            buf = self.h.alloc(16 * max(1, n)).from_host(pts)
-            assert n <= self.n_alloc
-            self.h.pip_query(base, query_map_id, buf, 0, n, self.closest, self.faces)
-            buf.free()
-        else:
-            b, e = point_range if point_range is not None else (0, self.ctx_.get_map(query_map_id).n_points)
-            n = e - b
-            assert n <= self.n_alloc
-            self.h.pip_query(base, query_map_id, None, b, n, self.closest, self.faces)
-        self.n = n
-        return n
+        query = getattr(self.h, self._query)
+        self.n, _ = _over_points(self, query_map_id, query_points, point_range,
+                                 lambda buf, b, n: query(1 - query_map_id, query_map_id, buf, b, n, self.closest, self.faces))
+        return self.n
 
     def get_closest_eids(self):
         return self.closest.to_host(np.uint32, self.n)
@@ -255,8 +301,8 @@ class PIPLBVH:
 
 
 class _DistanceQuery:
-    """What NearestLBVH and WithinLBVH share: where the points of a call come from, the per-row outputs (eid, exact record,
-    distance in double; `rows_`: how many the last call filled) and the freeing of the device buffers."""
+    """What NearestLBVH and WithinLBVH share: the per-row outputs (eid, exact record, distance in double; `rows_`: how many
+    the last call filled) and the freeing of the device buffers."""
 
     def __init__(self, dctx):
         self.ctx_ = dctx
@@ -264,23 +310,6 @@ class _DistanceQuery:
         self.eids = self.records = self.dist = None
         self.n = self.rows_ = 0
         self.has_records = self.has_dist = False
-
-    def _over_points(self, query_map_id, query_points, point_range, call):
-        """call(device points or None, begin, n) over int64[n,2] scaled host points, staged for the call and freed behind it,
-        or over the query map's own vertices, optionally a [begin, end) sub-range (a shard) -> (n, what call returned)"""
-        if query_points is not None:
-            pts = np.ascontiguousarray(query_points, dtype=np.int64).reshape(-1, 2)
-            n = pts.shape[0]
-            assert n <= self.n_alloc
-            buf = self.h.alloc(16 * max(1, n)).from_host(pts)
-            try:
-                return n, call(buf, 0, n)
-            finally:
-                buf.free()
-        b, e = point_range if point_range is not None else (0, self.ctx_.get_map(query_map_id).n_points)
-        n = e - b
-        assert n <= self.n_alloc
-        return n, call(None, b, n)
 
     def get_eids(self):
         return self.eids.to_host(np.uint32, self.rows_)
@@ -325,8 +354,8 @@ class NearestLBVH(_DistanceQuery):
         miss.  records / dist: whether the call fills them.  Returns the number of points."""
         md = -1 if max_dist is None else int(max_dist)
         rec, dst = (self.records if records else None), (self.dist if dist else None)
-        n, _ = self._over_points(query_map_id, query_points, point_range,
-                                 lambda buf, b, n: self.h.nearest_query(1 - query_map_id, query_map_id, buf, b, n, self.eids, rec, dst, md))
+        n, _ = _over_points(self, query_map_id, query_points, point_range,
+                            lambda buf, b, n: self.h.nearest_query(1 - query_map_id, query_map_id, buf, b, n, self.eids, rec, dst, md))
         self.n = self.rows_ = n
         self.has_records, self.has_dist = bool(records), bool(dist)
         return n
@@ -365,8 +394,8 @@ class WithinLBVH(_DistanceQuery):
 
     def _call(self, query_map_id, query_points, point_range, max_dist, capacity, rec, dst):
         eids = self.eids if capacity else None
-        return self._over_points(query_map_id, query_points, point_range,
-                                 lambda buf, b, n: self.h.within_query(1 - query_map_id, query_map_id, buf, b, n, max_dist, capacity, self.offsets, eids, rec, dst))
+        return _over_points(self, query_map_id, query_points, point_range,
+                            lambda buf, b, n: self.h.within_query(1 - query_map_id, query_map_id, buf, b, n, max_dist, capacity, self.offsets, eids, rec, dst))
 
     def _set(self, n, n_pairs, counts, records, dist):
         self.n, self.n_pairs, self.rows_, self.counts_ = n, n_pairs, n_pairs, counts
@@ -438,23 +467,7 @@ class LSIGrid(LSILBVH):
 
 class PIPGrid(PIPLBVH):
     """-mode=grid PIP (src/app/pip_grid.h): needs DeviceContext.BuildGrid(g, (base_map_id,))."""
-
-    def Query(self, query_map_id, query_points=None, point_range=None):
-        base = 1 - query_map_id
-        if query_points is not None:
-            pts = np.ascontiguousarray(query_points, dtype=np.int64).reshape(-1, 2)
-            n = pts.shape[0]
-            buf = self.h.alloc(16 * max(1, n)).from_host(pts)
-            assert n <= self.n_alloc
-            self.h.pip_query_grid(base, query_map_id, buf, 0, n, self.closest, self.faces)
-            buf.free()
-        else:
-            b, e = point_range if point_range is not None else (0, self.ctx_.get_map(query_map_id).n_points)
-            n = e - b
-            assert n <= self.n_alloc
-            self.h.pip_query_grid(base, query_map_id, None, b, n, self.closest, self.faces)
-        self.n = n
-        return n
+    _query = "pip_query_grid"
 
 
 FACE_TABLE_DTYPE = np.dtype([("face0", "<i4"), ("face1", "<i4"), ("area2", object), ("area", "<f8")])
@@ -558,47 +571,33 @@ class MapOverlay:
         op = overlay_op(how, by)
         args = (self.xsects[0], self.xsects[1], self.n_xsects, self.faces[0], self.faces[1], flags)
         if capacities is None:
-            try:
-                capacities = self.h.overlay_map(*args, (0, 0, 0), None, None, None, None, None, None, op=op)
-            except _capi.MapOverflow as e:
-                capacities = e.counts
+            capacities = _sizing_counts(self.h.overlay_map, _capi.MapOverflow, *args, (0, 0, 0), None, None, None, None, None, None, op=op)
         cc, pc, fc = (int(v) for v in capacities)
-        bufs = [self.h.alloc(16 * max(1, pc)), self.h.alloc(4 * (cc + 1)), self.h.alloc(4 * max(1, cc)), self.h.alloc(4 * max(1, cc)),
-                self.h.alloc(8 * max(1, fc)), self.h.alloc(4 * max(1, cc))]
-        try:
+        with _Owned(self.h) as own:
+            bufs = [own.alloc(16 * max(1, pc)), own.alloc(4 * (cc + 1)), own.alloc(4 * max(1, cc)), own.alloc(4 * max(1, cc)),
+                    own.alloc(8 * max(1, fc)), own.alloc(4 * max(1, cc))]
             counts = self.h.overlay_map(*args, (cc, pc, fc), *bufs, op=op)
-        except _capi.RayJoinError:
-            for b in bufs:
-                b.free()
-            raise
+            own.release()
         return DeviceOutputMap(*bufs, counts, drop_degenerate, merge)
 
 
-class DeviceOutputMap:
-    """The overlay's output map in device memory (rj_overlay_map): xy (int64 x,y pairs, scaled units), row_index
-    (uint32, n_chains + 1), left / right (int32 output face ids), face_pairs (int32 pairs: face k is face_pairs[k - 1])
-    and origin (uint32: (im << 31) | source chain) as DeviceBuffers, the counts, and the flags it was computed under
-    (drop_degenerate, merged)."""
+class _ChainMapOps(_OwnsBuffers):
+    """What every labelled chain map in device memory offers, over its xy, n_points, row_index, left, right, n_chains: the
+    host image and the map operations, each on the device with a result of its own."""
 
-    def __init__(self, xy, row_index, left, right, face_pairs, origin, counts, drop_degenerate, merged=False):
-        self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin = xy, row_index, left, right, face_pairs, origin
-        self.n_chains, self.n_points, self.n_faces = (int(v) for v in counts)
-        self.drop_degenerate = bool(drop_degenerate)
-        self.merged = bool(merged)
-
-    def to_host(self):
-        """-> (maps.ScaledMap of the output map, face_pairs int32 [n_faces, 2], origin uint32 [n_chains])"""
+    def _scaled_map(self):
         from .maps import ScaledMap
-        m = ScaledMap(0, self.xy.to_host(np.int64, 2 * self.n_points).reshape(-1, 2), self.row_index.to_host(np.uint32, self.n_chains + 1),
-                      self.left.to_host(np.int32, self.n_chains).astype(np.int64), self.right.to_host(np.int32, self.n_chains).astype(np.int64))
-        return m, self.face_pairs.to_host(np.int32, 2 * self.n_faces).reshape(-1, 2), self.origin.to_host(np.uint32, self.n_chains)
+        return ScaledMap(0, self.xy.to_host(np.int64, 2 * self.n_points).reshape(-1, 2), self.row_index.to_host(np.uint32, self.n_chains + 1),
+                         self.left.to_host(np.int32, self.n_chains).astype(np.int64), self.right.to_host(np.int32, self.n_chains).astype(np.int64))
 
     def Rings(self, handle, **kw):
-        """face_rings of this map: the closed boundaries of its faces (face k is row k - 1 of FaceTable()), on the device"""
+        """face_rings of this map: the closed boundaries of its faces, on the device (of an overlay's output map, face k is
+        row k - 1 of FaceTable())"""
         return face_rings(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, **kw)
 
     def Crossings(self, handle, **kw):
-        """map_crossings of this map, on the device: does it still have no crossings (its cut points are truncated to integers)"""
+        """map_crossings of this map, on the device: overlapping or self-crossing polygons show here, and whether an output
+        map still has no crossings (its cut points are truncated to integers)"""
         return map_crossings(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
 
     def Node(self, handle, **kw):
@@ -620,7 +619,10 @@ class DeviceOutputMap:
         """map_eliminate of this map, on the device, as a DeviceEliminatedMap of its own: every face of area2 <= tol merged
         into the neighbour with the longest shared border, the chains between merged faces dropped.  rounds > 1: repeated
         (map_eliminate_rounds) until a round eliminates nothing or `rounds` have run; .rounds holds the counts of each"""
-        return _eliminated(handle, self, tol, rounds, faces)
+        args = (self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, tol)
+        if int(rounds) <= 1:
+            return map_eliminate(handle, *args, drop=True, faces=faces)
+        return map_eliminate_rounds(handle, *args, max_rounds=rounds, faces=faces)
 
     def Dissolve(self, handle, classes=None, **kw):
         """map_dissolve of this map, on the device, as a DeviceDissolvedMap of its own: the faces merged by class (classes: an
@@ -637,9 +639,23 @@ class DeviceOutputMap:
         and (vertex=True) at how many nodes, with the faces that meet only at a vertex"""
         return map_neighbours(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, vertex=vertex, **kw)
 
-    def free(self):
-        for b in (self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin):
-            b.free()
+
+class DeviceOutputMap(_ChainMapOps):
+    """The overlay's output map in device memory (rj_overlay_map): xy (int64 x,y pairs, scaled units), row_index
+    (uint32, n_chains + 1), left / right (int32 output face ids), face_pairs (int32 pairs: face k is face_pairs[k - 1])
+    and origin (uint32: (im << 31) | source chain) as DeviceBuffers, the counts, and the flags it was computed under
+    (drop_degenerate, merged)."""
+    _buffers = ("xy", "row_index", "left", "right", "face_pairs", "origin")
+
+    def __init__(self, xy, row_index, left, right, face_pairs, origin, counts, drop_degenerate, merged=False):
+        self.xy, self.row_index, self.left, self.right, self.face_pairs, self.origin = xy, row_index, left, right, face_pairs, origin
+        self.n_chains, self.n_points, self.n_faces = (int(v) for v in counts)
+        self.drop_degenerate = bool(drop_degenerate)
+        self.merged = bool(merged)
+
+    def to_host(self):
+        """-> (maps.ScaledMap of the output map, face_pairs int32 [n_faces, 2], origin uint32 [n_chains])"""
+        return self._scaled_map(), self.face_pairs.to_host(np.int32, 2 * self.n_faces).reshape(-1, 2), self.origin.to_host(np.uint32, self.n_chains)
 
 
 def map_crossings(handle, xy, n_points, row_index, n_chains, capacity=None):
@@ -649,34 +665,23 @@ def map_crossings(handle, xy, n_points, row_index, n_chains, capacity=None):
     RJ_CROSS_PROPER / TOUCH / OVERLAP / EQUAL), ascending by (eid[0], eid[1]); counts a dict (CROSSINGS_COUNTS).  No
     record: the map is a planar subdivision.  capacity: CrossingsOverflow with the true counts when it is too small;
     left open, a sizing call finds it."""
-    buf, counts = _crossings_on_device(handle, xy, n_points, row_index, n_chains, capacity)
-    if buf is None:
-        return np.zeros(0, _capi.CROSSING_DTYPE), counts
-    try:
-        return buf.to_host(_capi.CROSSING_DTYPE, counts["n_found"]), counts
-    finally:
-        buf.free()
+    with _Owned(handle) as tmp:
+        buf, counts = _crossings_on_device(tmp, xy, n_points, row_index, n_chains, capacity)
+        return (np.zeros(0, _capi.CROSSING_DTYPE) if buf is None else buf.to_host(_capi.CROSSING_DTYPE, counts["n_found"])), counts
 
 
-def _crossings_on_device(handle, xy, n_points, row_index, n_chains, capacity=None):
-    """map_crossings whose records stay on the device -> (a DeviceBuffer of counts["n_found"] records, counts); no buffer
-    where a sizing call found no record"""
+def _crossings_on_device(own, xy, n_points, row_index, n_chains, capacity=None):
+    """map_crossings whose records stay on the device, in a buffer of `own` -> (a DeviceBuffer of counts["n_found"] records,
+    counts); no buffer where a sizing call found no record"""
     args = (xy, n_points, row_index, n_chains)
     if capacity is None:
-        try:
-            c = handle.map_crossings(*args, 0, None)
-        except _capi.CrossingsOverflow as e:
-            c = e.counts
+        c = _sizing_counts(own.handle.map_crossings, _capi.CrossingsOverflow, *args, 0, None)
         if c["n_found"] == 0:
             return None, c
         capacity = c["n_found"]
     capacity = int(capacity)
-    buf = handle.alloc(_capi.CROSSING_DTYPE.itemsize * max(1, capacity))
-    try:
-        return buf, handle.map_crossings(*args, capacity, buf)
-    except _capi.RayJoinError:
-        buf.free()
-        raise
+    buf = own.alloc(_capi.CROSSING_DTYPE.itemsize * max(1, capacity))
+    return buf, own.handle.map_crossings(*args, capacity, buf)
 
 
 def map_simplify(handle, xy, n_points, row_index, n_chains, tol, origin=False, capacity=None):
@@ -686,29 +691,22 @@ def map_simplify(handle, xy, n_points, row_index, n_chains, tol, origin=False, c
     every chain stay, and a closed chain keeps a triangle: chains, their number and their order do not change, and the
     caller's left / right arrays go with the result as they are.  origin: also the input point of every output point.
     capacity (points): SimplifyOverflow with the true counts when it is too small; left open, a sizing call finds it."""
-    bufs = []
     args = (xy, n_points, row_index, n_chains, tol)
-    try:
-        if capacity is None:
-            try:
-                capacity = handle.map_simplify(*args, 0, None, None)["n_points"]
-            except _capi.SimplifyOverflow as e:
-                capacity = e.counts["n_points"]
-        capacity = int(capacity)
-        bufs = [handle.alloc(16 * max(1, capacity)), handle.alloc(4 * (int(n_chains) + 1)), handle.alloc(4 * max(1, capacity)) if origin else None]
+    if capacity is None:
+        capacity = _sizing_counts(handle.map_simplify, _capi.SimplifyOverflow, *args, 0, None, None)["n_points"]
+    capacity = int(capacity)
+    with _Owned(handle) as own:
+        bufs = [own.alloc(16 * max(1, capacity)), own.alloc(4 * (int(n_chains) + 1)), own.alloc(4 * max(1, capacity)) if origin else None]
         counts = handle.map_simplify(*args, capacity, *bufs)
-    except _capi.RayJoinError:
-        for b in bufs:
-            if b is not None:
-                b.free()
-        raise
+        own.release()
     return DeviceSimplifiedMap(*bufs, counts, n_chains)
 
 
-class DeviceSimplifiedMap:
+class DeviceSimplifiedMap(_OwnsBuffers):
     """A thinned chain map in device memory (rj_map_simplify): xy (int64 x,y pairs), row_index (uint32, n_chains + 1) and,
     where asked for, origin (uint32 per output point: its input point) as DeviceBuffers, and the counts n_points,
     n_removed, n_rounds, n_closed, n_pinned_extra, n_max_round."""
+    _buffers = ("xy", "row_index", "origin")
 
     def __init__(self, xy, row_index, origin, counts, n_chains):
         self.xy, self.row_index, self.origin = xy, row_index, origin
@@ -720,58 +718,42 @@ class DeviceSimplifiedMap:
         return (self.xy.to_host(np.int64, 2 * self.n_points).reshape(-1, 2), self.row_index.to_host(np.uint32, self.n_chains + 1),
                 self.origin.to_host(np.uint32, self.n_points) if self.origin is not None else None)
 
-    def free(self):
-        for b in (self.xy, self.row_index, self.origin):
-            if b is not None:
-                b.free()
-
 
 def _simplified_chain_map(handle, m, tol, check, capacity):
     """DeviceOutputMap.Simplify / DeviceChainMap.Simplify: the thinned map with device copies of m's left / right"""
     sm = map_simplify(handle, m.xy, m.n_points, m.row_index, m.n_chains, tol, capacity=capacity)
-    sides = []
-    try:
-        sides = [handle.alloc(4 * max(1, m.n_chains)).from_device(b, 4 * m.n_chains) for b in (m.left, m.right)]
+    with _Owned(handle) as own:
+        own.bufs += [sm.xy, sm.row_index]  # (the thinned map's buffers become the chain map's)
+        sides = [own.alloc(4 * max(1, m.n_chains)).from_device(b, 4 * m.n_chains) for b in (m.left, m.right)]
         counts = dict(sm.counts, n_chains=m.n_chains, n_edges=sm.n_points - m.n_chains)
         out = DeviceChainMap(sm.xy, sm.row_index, sides[0], sides[1], counts)
-        return (out, out.Crossings(handle)[1]) if check else out
-    except _capi.RayJoinError:
-        for b in sides:
-            b.free()
-        sm.free()
-        raise
+        res = (out, out.Crossings(handle)[1]) if check else out
+        own.release()
+    return res
 
 
-def _records_on_device(handle, xy, n_points, row_index, n_chains, records):
-    """The records that map_node / map_snap take -> (a DeviceBuffer that the caller frees, or None; their number).  records:
+def _records_on_device(own, xy, n_points, row_index, n_chains, records):
+    """The records that map_node / map_snap take, in a temporary of `own` -> (a DeviceBuffer or None, their number).  records:
     the host CROSSING_DTYPE array, uploaded; None: rj_map_crossings runs here and its records stay on the device"""
     if records is None:
-        rec, c = _crossings_on_device(handle, xy, n_points, row_index, n_chains)
+        rec, c = _crossings_on_device(own, xy, n_points, row_index, n_chains)
         return rec, c["n_found"]
     records = np.ascontiguousarray(records, dtype=_capi.CROSSING_DTYPE)
     n_rec = len(records)
-    return (handle.alloc(_capi.CROSSING_DTYPE.itemsize * n_rec).from_host(records) if n_rec else None), n_rec
+    return (own.alloc(_capi.CROSSING_DTYPE.itemsize * n_rec).from_host(records) if n_rec else None), n_rec
 
 
 def _cuts_call(call, overflow, handle, xy, n_points, row_index, n_chains, rec, n_rec, flags, edge_origin, capacity):
     """handle.map_node or handle.map_snap (call, with its overflow class) with the records in device memory (rec may be None
     with n_rec == 0) -> DeviceNodedMap.  capacity None: a sizing call finds it.  The three buffers are freed on an error"""
-    bufs = []
-    try:
-        args = (xy, n_points, row_index, n_chains, rec, n_rec, flags)
-        if capacity is None:
-            try:
-                capacity = call(*args, 0, None, None)["n_points"]
-            except overflow as e:
-                capacity = e.counts["n_points"]
-        capacity = int(capacity)
-        bufs = [handle.alloc(16 * max(1, capacity)), handle.alloc(4 * (int(n_chains) + 1)), handle.alloc(4 * max(1, capacity)) if edge_origin else None]
+    args = (xy, n_points, row_index, n_chains, rec, n_rec, flags)
+    if capacity is None:
+        capacity = _sizing_counts(call, overflow, *args, 0, None, None)["n_points"]
+    capacity = int(capacity)
+    with _Owned(handle) as own:
+        bufs = [own.alloc(16 * max(1, capacity)), own.alloc(4 * (int(n_chains) + 1)), own.alloc(4 * max(1, capacity)) if edge_origin else None]
         counts = call(*args, capacity, *bufs)
-    except _capi.RayJoinError:
-        for b in bufs:
-            if b is not None:
-                b.free()
-        raise
+        own.release()
     return DeviceNodedMap(*bufs, counts, n_chains, bool(flags & _capi.RJ_NODE_DROP_LAST))  # (RJ_SNAP_DROP_LAST is the same bit)
 
 
@@ -784,13 +766,10 @@ def map_node(handle, xy, n_points, row_index, n_chains, records=None, drop_last=
     point == last) and writes each without its last point, the ring layout that rings_map takes.  edge_origin: also the
     input edge of every output edge.  counts["n_proper"]: the crossings that noding cannot repair.  capacity (points):
     NodeOverflow with the true counts when it is too small; left open, a sizing call finds it."""
-    rec, n_rec = _records_on_device(handle, xy, n_points, row_index, n_chains, records)
-    try:
+    with _Owned(handle) as tmp:
+        rec, n_rec = _records_on_device(tmp, xy, n_points, row_index, n_chains, records)
         return _cuts_call(handle.map_node, _capi.NodeOverflow, handle, xy, n_points, row_index, n_chains, rec, n_rec,
                           _capi.RJ_NODE_DROP_LAST if drop_last else 0, edge_origin, capacity)
-    finally:
-        if rec is not None:
-            rec.free()
 
 
 def _snap_call(handle, xy, n_points, row_index, n_chains, rec, n_rec, flags, edge_origin, capacity):
@@ -803,12 +782,9 @@ def map_snap(handle, xy, n_points, row_index, n_chains, records=None, drop_last=
     every RJ_CROSS_PROPER record cuts both of its edges at the crossing point rounded to integers (halves toward
     +infinity), the other kinds cut as in map_node.  One call: the rounding can make new crossings -- map_snap_rounds
     repeats it.  records, drop_last, edge_origin, capacity: as map_node (SnapOverflow past the capacity)."""
-    rec, n_rec = _records_on_device(handle, xy, n_points, row_index, n_chains, records)
-    try:
+    with _Owned(handle) as tmp:
+        rec, n_rec = _records_on_device(tmp, xy, n_points, row_index, n_chains, records)
         return _snap_call(handle, xy, n_points, row_index, n_chains, rec, n_rec, _capi.RJ_SNAP_DROP_LAST if drop_last else 0, edge_origin, capacity)
-    finally:
-        if rec is not None:
-            rec.free()
 
 
 def map_snap_rounds(handle, xy, n_points, row_index, n_chains, max_rounds=8, drop_last=False):
@@ -828,14 +804,11 @@ def map_snap_rounds(handle, xy, n_points, row_index, n_chains, max_rounds=8, dro
     try:
         while True:
             at = (xy, n_points, row_index) if cur is None else (cur.xy, cur.n_points, cur.row_index)
-            rec, c = _crossings_on_device(handle, at[0], at[1], at[2], n_chains)
-            try:
+            with _Owned(handle) as tmp:
+                rec, c = _crossings_on_device(tmp, at[0], at[1], at[2], n_chains)
                 if c["n_proper"] + c["n_touch"] + c["n_overlap"] == 0 or len(rounds) >= max_rounds:
                     break
                 nm = _snap_call(handle, at[0], at[1], at[2], n_chains, rec, c["n_found"], 0, False, None)
-            finally:
-                if rec is not None:
-                    rec.free()
             rounds.append(dict(crossings=c, snap=nm.counts))
             if cur is not None:
                 cur.free()
@@ -846,7 +819,7 @@ def map_snap_rounds(handle, xy, n_points, row_index, n_chains, max_rounds=8, dro
             if cur is not None:
                 cur.free()
             cur = nm
-    except _capi.RayJoinError:
+    except BaseException:
         if cur is not None:
             cur.free()
         raise
@@ -854,11 +827,12 @@ def map_snap_rounds(handle, xy, n_points, row_index, n_chains, max_rounds=8, dro
     return cur
 
 
-class DeviceNodedMap:
+class DeviceNodedMap(_OwnsBuffers):
     """A noded chain map in device memory (rj_map_node): xy (int64 x,y pairs), row_index (uint32, n_chains + 1) and, where
     asked for, edge_origin (uint32 per output edge: its input edge) as DeviceBuffers, the counts n_points, n_edges, n_cuts,
     n_cut_edges, n_max_cuts, n_used, n_proper, n_equal (from map_snap also n_exact, n_at_end, n_stale), and drop_last: the
     chains are rings without their closing point.  From map_snap_rounds also rounds, clean and remaining."""
+    _buffers = ("xy", "row_index", "edge_origin")
 
     def __init__(self, xy, row_index, edge_origin, counts, n_chains, drop_last=False):
         self.xy, self.row_index, self.edge_origin = xy, row_index, edge_origin
@@ -885,10 +859,12 @@ class DeviceNodedMap:
             raise ValueError("a map written with drop_last has no closing points: snap before dropping them")
         return map_snap_rounds(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
 
-    def free(self):
-        for b in (self.xy, self.row_index, self.edge_origin):
-            if b is not None:
-                b.free()
+
+def _stage_closed_rings(own, ring_row, ring_xy):
+    """Host rings closed into chains (maps.closed_chains_of_rings) in temporaries of `own` -> (xy, n_points, row_index, n_chains)"""
+    from .maps import closed_chains_of_rings
+    row, xy = closed_chains_of_rings(ring_row, ring_xy)
+    return own.alloc(16 * max(1, len(xy))).from_host(xy), len(xy), own.alloc(4 * len(row)).from_host(row), len(row) - 1
 
 
 def node_rings(handle, ring_row, ring_xy):
@@ -896,14 +872,8 @@ def node_rings(handle, ring_row, ring_xy):
     device: closed into chains (maps.closed_chains_of_rings), uploaded, map_crossings, map_node with drop_last ->
     (ring_row buffer, ring_xy buffer, n_points, counts), ready for rings_map with the caller's unchanged ring_face.
     counts["n_proper"] is what noding could not repair: rings that cross each other properly."""
-    from .maps import closed_chains_of_rings
-    row, xy = closed_chains_of_rings(ring_row, ring_xy)
-    bufs = [handle.alloc(16 * max(1, len(xy))).from_host(xy), handle.alloc(4 * len(row)).from_host(row)]
-    try:
-        nm = map_node(handle, bufs[0], len(xy), bufs[1], len(row) - 1, drop_last=True)
-    finally:
-        for b in bufs:
-            b.free()
+    with _Owned(handle) as tmp:
+        nm = map_node(handle, *_stage_closed_rings(tmp, ring_row, ring_xy), drop_last=True)
     return nm.row_index, nm.xy, nm.n_points, nm.counts
 
 
@@ -912,14 +882,8 @@ def snap_rings(handle, ring_row, ring_xy, max_rounds=8):
     drop_last -> (ring_row buffer, ring_xy buffer, n_points, clean, rounds), the first three ready for rings_map with the
     caller's unchanged ring_face -- where polygons overlapped, the labels of the chain map that comes out conflict
     (its counts tell) and map_faces labels the linework from its geometry.  clean / rounds: as map_snap_rounds."""
-    from .maps import closed_chains_of_rings
-    row, xy = closed_chains_of_rings(ring_row, ring_xy)
-    bufs = [handle.alloc(16 * max(1, len(xy))).from_host(xy), handle.alloc(4 * len(row)).from_host(row)]
-    try:
-        nm = map_snap_rounds(handle, bufs[0], len(xy), bufs[1], len(row) - 1, max_rounds=max_rounds, drop_last=True)
-    finally:
-        for b in bufs:
-            b.free()
+    with _Owned(handle) as tmp:
+        nm = map_snap_rounds(handle, *_stage_closed_rings(tmp, ring_row, ring_xy), max_rounds=max_rounds, drop_last=True)
     return nm.row_index, nm.xy, nm.n_points, nm.clean, nm.rounds
 
 
@@ -931,29 +895,23 @@ def face_rings(handle, xy, n_points, row_index, left, right, n_chains, skip_face
     flags = (_capi.RJ_RINGS_SKIP_FACE0 if skip_face0 else 0) | (0 if points else _capi.RJ_RINGS_NO_POINTS)
     args = (xy, n_points, row_index, left, right, n_chains, flags)
     if capacities is None:
-        try:
-            c = handle.map_rings(*args, (0, 0, 0), None, None, None, None, None)
-        except _capi.RingsOverflow as e:
-            c = e.counts
+        c = _sizing_counts(handle.map_rings, _capi.RingsOverflow, *args, (0, 0, 0), None, None, None, None, None)
         capacities = (c["n_rings"], c["n_halves"], c["n_points"])
     rc, hc, pc = (int(v) for v in capacities)
-    bufs = [handle.alloc(_capi.RING_DTYPE.itemsize * max(1, rc)), handle.alloc(4 * (rc + 1)), handle.alloc(4 * max(1, hc)),
-            handle.alloc(4 * (rc + 1)) if points else None, handle.alloc(16 * max(1, pc)) if points else None]
-    try:
+    with _Owned(handle) as own:
+        bufs = [own.alloc(_capi.RING_DTYPE.itemsize * max(1, rc)), own.alloc(4 * (rc + 1)), own.alloc(4 * max(1, hc)),
+                own.alloc(4 * (rc + 1)) if points else None, own.alloc(16 * max(1, pc)) if points else None]
         counts = handle.map_rings(*args, (rc, hc, pc), *bufs)
-    except _capi.RayJoinError:
-        for b in bufs:
-            if b is not None:
-                b.free()
-        raise
+        own.release()
     return DeviceRings(*bufs, counts)
 
 
-class DeviceRings:
+class DeviceRings(_OwnsBuffers):
     """The rings of a chain map in device memory (rj_map_rings): rings (RING_DTYPE rows, ascending by (face, leader)),
     ring_first (uint32 CSR of the rings into ring_half), ring_half (uint32 half-chains: 2 c = chain c forward, 2 c + 1
     backward), ring_row (uint32 CSR into ring_xy) and ring_xy (int64 x,y pairs, scaled units) as DeviceBuffers -- the last
     two None without points -- and the counts n_rings, n_halves, n_points, n_mixed, n_skipped."""
+    _buffers = ("rings", "ring_first", "ring_half", "ring_row", "ring_xy")
 
     def __init__(self, rings, ring_first, ring_half, ring_row, ring_xy, counts):
         self.rings, self.ring_first, self.ring_half, self.ring_row, self.ring_xy = rings, ring_first, ring_half, ring_row, ring_xy
@@ -994,20 +952,14 @@ class DeviceRings:
             raise RuntimeError("DeviceRings.Polygons needs the points (points=True)")
         args = (self.rings, self.n_rings, self.ring_row, self.ring_xy, self.n_points, 0)
         if capacities is None:
-            try:
-                c = handle.rings_polygons(*args, (0, 0), None, None, None, None)
-            except _capi.PolygonsOverflow as e:
-                c = e.counts
+            c = _sizing_counts(handle.rings_polygons, _capi.PolygonsOverflow, *args, (0, 0), None, None, None, None)
             capacities = (c["n_polygons"], c["n_members"])
         pc, mc = (int(v) for v in capacities)
-        bufs = [handle.alloc(4 * max(1, self.n_rings)), handle.alloc(_capi.POLYGON_DTYPE.itemsize * max(1, pc)), handle.alloc(4 * (pc + 1)),
-                handle.alloc(4 * max(1, mc))]
-        try:
+        with _Owned(handle) as own:
+            bufs = [own.alloc(4 * max(1, self.n_rings)), own.alloc(_capi.POLYGON_DTYPE.itemsize * max(1, pc)), own.alloc(4 * (pc + 1)),
+                    own.alloc(4 * max(1, mc))]
             counts = handle.rings_polygons(*args, (pc, mc), *bufs)
-        except _capi.RayJoinError:
-            for b in bufs:
-                b.free()
-            raise
+            own.release()
         return DevicePolygons(*bufs, self.n_rings, counts)
 
     def Map(self, handle, dissolve=False):
@@ -1017,11 +969,6 @@ class DeviceRings:
             raise RuntimeError("DeviceRings.Map needs the points (points=True)")
         return rings_map(handle, self.ring_row, self.ring_xy, self.n_points, self.rings, self.n_rings, face_stride=_capi.RING_DTYPE.itemsize,
                          dissolve=dissolve)
-
-    def free(self):
-        for b in (self.rings, self.ring_first, self.ring_half, self.ring_row, self.ring_xy):
-            if b is not None:
-                b.free()
 
 
 def rings_map(handle, ring_row, ring_xy, n_points, ring_face, n_rings, face_stride=4, dissolve=False, capacities=None):
@@ -1034,27 +981,22 @@ def rings_map(handle, ring_row, ring_xy, n_points, ring_face, n_rings, face_stri
     flags = _capi.RJ_RMAP_DISSOLVE if dissolve else 0
     args = (ring_row, ring_xy, n_points, ring_face, face_stride, n_rings, flags)
     if capacities is None:
-        try:
-            c = handle.rings_map(*args, (0, 0), None, None, None, None)
-        except _capi.RingsMapOverflow as e:
-            c = e.counts
+        c = _sizing_counts(handle.rings_map, _capi.RingsMapOverflow, *args, (0, 0), None, None, None, None)
         capacities = (c["n_chains"], c["n_points"])
     cc, pc = (int(v) for v in capacities)
-    bufs = [handle.alloc(16 * max(1, pc)), handle.alloc(4 * (cc + 1)), handle.alloc(4 * max(1, cc)), handle.alloc(4 * max(1, cc))]
-    try:
+    with _Owned(handle) as own:
+        bufs = [own.alloc(16 * max(1, pc)), own.alloc(4 * (cc + 1)), own.alloc(4 * max(1, cc)), own.alloc(4 * max(1, cc))]
         counts = handle.rings_map(*args, (cc, pc), *bufs)
-    except _capi.RayJoinError:
-        for b in bufs:
-            b.free()
-        raise
+        own.release()
     return DeviceChainMap(*bufs, counts)
 
 
-class DeviceChainMap:
+class DeviceChainMap(_ChainMapOps):
     """The chain map of a set of labelled rings in device memory (rj_rings_map): xy (int64 x,y pairs, scaled units),
     row_index (uint32, n_chains + 1), left / right (int32 faces) as DeviceBuffers -- the arrays rj_upload_map_dev takes, so
     DeviceContext.InstallMap takes it as it takes a DeviceOutputMap -- and the counts n_chains, n_points, n_edges, n_closed,
     n_zero_edges, n_conflicts, n_dissolved."""
+    _buffers = ("xy", "row_index", "left", "right")
 
     def __init__(self, xy, row_index, left, right, counts):
         self.xy, self.row_index, self.left, self.right = xy, row_index, left, right
@@ -1063,64 +1005,13 @@ class DeviceChainMap:
 
     def to_host(self):
         """-> (maps.ScaledMap of the map, the counts)"""
-        from .maps import ScaledMap
-        m = ScaledMap(0, self.xy.to_host(np.int64, 2 * self.n_points).reshape(-1, 2), self.row_index.to_host(np.uint32, self.n_chains + 1),
-                      self.left.to_host(np.int32, self.n_chains).astype(np.int64), self.right.to_host(np.int32, self.n_chains).astype(np.int64))
-        return m, dict(self.counts)
-
-    def Rings(self, handle, **kw):
-        """face_rings of this map, on the device"""
-        return face_rings(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, **kw)
-
-    def Crossings(self, handle, **kw):
-        """map_crossings of this map, on the device: overlapping or self-crossing polygons show here"""
-        return map_crossings(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
-
-    def Node(self, handle, **kw):
-        """map_node of this map, on the device: its edges cut at the vertices that lie inside them (left / right stay valid)"""
-        return map_node(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
-
-    def Snap(self, handle, **kw):
-        """map_snap_rounds of this map, on the device: cut at its touches, overlaps and rounded proper crossings until a check
-        finds none (.clean) or max_rounds is hit; the chains stay, so left / right stay valid as chain labels"""
-        return map_snap_rounds(handle, self.xy, self.n_points, self.row_index, self.n_chains, **kw)
-
-    def Simplify(self, handle, tol, check=False, capacity=None):
-        """map_simplify of this map, on the device, as a DeviceChainMap of its own (copies of left / right: the chains do not
-        change): what InstallMap, Rings() and Crossings() take; its counts are those of rj_map_simplify with n_chains and
-        n_edges.  check: -> (the map, the counts of Crossings() on it) -- thinning can push a chain across another one"""
-        return _simplified_chain_map(handle, self, tol, check, capacity)
-
-    def Eliminate(self, handle, tol, rounds=1, faces=False):
-        """map_eliminate of this map, on the device, as a DeviceEliminatedMap of its own: every face of area2 <= tol merged
-        into the neighbour with the longest shared border, the chains between merged faces dropped.  rounds > 1: repeated
-        (map_eliminate_rounds) until a round eliminates nothing or `rounds` have run; .rounds holds the counts of each"""
-        return _eliminated(handle, self, tol, rounds, faces)
-
-    def Dissolve(self, handle, classes=None, **kw):
-        """map_dissolve of this map, on the device, as a DeviceDissolvedMap of its own: the faces merged by class (classes: an
-        int32 table indexed by label, on the device or as a numpy array; None: the labels themselves), the borders between
-        faces of one class dropped, the chains that meet two by two with equal classes joined"""
-        return map_dissolve(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, classes=classes, **kw)
-
-    def Join(self, handle, **kw):
-        """Dissolve with identity classes and keep_equal: no chain goes, the chains that meet two by two are joined"""
-        return self.Dissolve(handle, None, keep_equal=True, **kw)
-
-    def Neighbours(self, handle, vertex=False, **kw):
-        """map_neighbours of this map, on the device, as a DeviceNeighbours: which faces touch which, along how much border
-        and (vertex=True) at how many nodes, with the faces that meet only at a vertex"""
-        return map_neighbours(handle, self.xy, self.n_points, self.row_index, self.left, self.right, self.n_chains, vertex=vertex, **kw)
+        return self._scaled_map(), dict(self.counts)
 
     def Faces(self, handle, check=False):
         """map_faces of this map, on the device: its faces computed from the geometry alone, as a DeviceFacedMap of its own.
         check: this map's own left / right go in as the labels to check -- counts["n_conflicts"] == 0 tells that they and
         the geometry describe the same partition, and the records' label is the given label of every computed face"""
         return map_faces(handle, self.xy, self.n_points, self.row_index, self.n_chains, labels=(self.left, self.right) if check else None)
-
-    def free(self):
-        for b in (self.xy, self.row_index, self.left, self.right):
-            b.free()
 
 
 def map_faces(handle, xy, n_points, row_index, n_chains, labels=None, records=True):
@@ -1137,34 +1028,28 @@ def map_faces(handle, xy, n_points, row_index, n_chains, labels=None, records=Tr
     n_points, n_chains = int(n_points), int(n_chains)
     in_left, in_right = labels if labels is not None else (None, None)
     rec = _capi.MAP_FACE_DTYPE.itemsize
-    bufs, faces, room, done = [], None, None, False
-    try:
-        bufs.append(handle.alloc(16 * max(1, n_points)).from_device(xy, 16 * n_points))
-        bufs.append(handle.alloc(4 * (n_chains + 1)))
-        bufs.append(handle.alloc(4 * max(1, n_chains)))
-        bufs.append(handle.alloc(4 * max(1, n_chains)))
+    faces = None
+    with _Owned(handle) as own, _Owned(handle) as tmp:
+        bufs = [own.alloc(16 * max(1, n_points)).from_device(xy, 16 * n_points), own.alloc(4 * (n_chains + 1)), own.alloc(4 * max(1, n_chains)),
+                own.alloc(4 * max(1, n_chains))]
         if n_chains:
             bufs[1].from_device(row_index, 4 * (n_chains + 1))
         else:
             bufs[1].from_host(np.zeros(1, np.uint32))
-        if records:
-            room = handle.alloc(rec * max(1, 2 * n_chains))
+        room = tmp.alloc(rec * max(1, 2 * n_chains)) if records else None
         counts = handle.map_faces(bufs[0], n_points, bufs[1], n_chains, bufs[2], bufs[3], room, 2 * n_chains, in_left, in_right)
         if records:
-            faces = handle.alloc(rec * max(1, counts["n_faces"]))
+            faces = own.alloc(rec * max(1, counts["n_faces"]))
             if counts["n_faces"]:
                 faces.from_device(room, rec * counts["n_faces"])
-        done = True
-    finally:
-        for b in [room] + ([] if done else bufs + [faces]):
-            if b is not None:
-                b.free()
+        own.release()
     return DeviceFacedMap(*bufs, dict(counts, n_chains=n_chains, n_points=n_points, n_edges=n_points - n_chains), faces)
 
 
 class DeviceFacedMap(DeviceChainMap):
     """A chain map in device memory whose left / right are the faces that rj_map_faces computed, with faces (MAP_FACE_DTYPE rows
     as a DeviceBuffer, or None) and the counts n_faces, n_rings, n_holes, n_outer, n_skipped, n_dangling, n_conflicts."""
+    _buffers = DeviceChainMap._buffers + ("faces",)
 
     def __init__(self, xy, row_index, left, right, counts, faces):
         super().__init__(xy, row_index, left, right, counts)
@@ -1173,11 +1058,6 @@ class DeviceFacedMap(DeviceChainMap):
     def faces_to_host(self):
         """-> the face records (MAP_FACE_DTYPE), record k - 1 for face k"""
         return self.faces.to_host(_capi.MAP_FACE_DTYPE, self.n_faces)
-
-    def free(self):
-        super().free()
-        if self.faces is not None:
-            self.faces.free()
 
 
 def map_eliminate(handle, xy, n_points, row_index, left, right, n_chains, tol, drop=True, faces=False):
@@ -1193,19 +1073,13 @@ def map_eliminate(handle, xy, n_points, row_index, left, right, n_chains, tol, d
     n_points, n_chains = int(n_points), int(n_chains)
     flags = _capi.RJ_ELIM_DROP if drop else 0
     args = (xy, n_points, row_index, left, right, n_chains, tol)
-    try:
-        c = handle.map_eliminate(*args, (0, 0, 0), None, None, flags=flags)
-    except _capi.EliminateOverflow as e:
-        c = e.counts
+    c = _sizing_counts(handle.map_eliminate, _capi.EliminateOverflow, *args, (0, 0, 0), None, None, flags=flags)
     fc, cc, pc = c["n_faces"] if faces else 0, c["n_chains"], c["n_points"]
-    bufs, records, origin, done = [], None, None, False
-    try:
-        bufs.append(handle.alloc(16 * max(1, pc)))
-        bufs.append(handle.alloc(4 * (cc + 1)))
-        bufs.append(handle.alloc(4 * max(1, cc)))
-        bufs.append(handle.alloc(4 * max(1, cc)))
+    origin = None
+    with _Owned(handle) as own:
+        bufs = [own.alloc(16 * max(1, pc)), own.alloc(4 * (cc + 1)), own.alloc(4 * max(1, cc)), own.alloc(4 * max(1, cc))]
         if drop:
-            origin = handle.alloc(4 * max(1, cc))
+            origin = own.alloc(4 * max(1, cc))
         else:
             if n_points:
                 bufs[0].from_device(xy, 16 * n_points)
@@ -1213,16 +1087,10 @@ def map_eliminate(handle, xy, n_points, row_index, left, right, n_chains, tol, d
                 bufs[1].from_device(row_index, 4 * (n_chains + 1))
         if not n_chains:
             bufs[1].from_host(np.zeros(1, np.uint32))
-        if faces:
-            records = handle.alloc(_capi.ELIM_FACE_DTYPE.itemsize * max(1, fc))
+        records = own.alloc(_capi.ELIM_FACE_DTYPE.itemsize * max(1, fc)) if faces else None
         counts = handle.map_eliminate(*args, (fc, cc, pc), bufs[2], bufs[3], bufs[0] if drop else None, bufs[1] if drop else None, origin, records,
                                       flags=flags)
-        done = True
-    finally:
-        if not done:
-            for b in bufs + [records, origin]:
-                if b is not None:
-                    b.free()
+        own.release()
     return DeviceEliminatedMap(*bufs, dict(counts, n_edges=counts["n_points"] - counts["n_chains"]), records, origin)
 
 
@@ -1249,6 +1117,7 @@ class DeviceEliminatedMap(DeviceChainMap):
     """A chain map in device memory whose left / right are the targets that rj_map_eliminate gave, with faces
     (ELIM_FACE_DTYPE rows as a DeviceBuffer, or None), origin (uint32 per chain: its input chain; None without drop) and the
     counts n_faces, n_slivers, n_eliminated, n_islands, n_mutual, n_negative, n_chains, n_points, n_dropped, n_edges."""
+    _buffers = DeviceChainMap._buffers + ("faces", "origin")
 
     def __init__(self, xy, row_index, left, right, counts, faces, origin):
         super().__init__(xy, row_index, left, right, counts)
@@ -1261,20 +1130,6 @@ class DeviceEliminatedMap(DeviceChainMap):
 
     def origin_to_host(self):
         return self.origin.to_host(np.uint32, self.n_chains)
-
-    def free(self):
-        super().free()
-        for b in (self.faces, self.origin):
-            if b is not None:
-                b.free()
-
-
-def _eliminated(handle, m, tol, rounds, faces):
-    """DeviceOutputMap.Eliminate / DeviceChainMap.Eliminate"""
-    args = (m.xy, m.n_points, m.row_index, m.left, m.right, m.n_chains, tol)
-    if int(rounds) <= 1:
-        return map_eliminate(handle, *args, drop=True, faces=faces)
-    return map_eliminate_rounds(handle, *args, max_rounds=rounds, faces=faces)
 
 
 def map_dissolve(handle, xy, n_points, row_index, left, right, n_chains, classes=None, keep_equal=False, records=False, origin=False):
@@ -1289,42 +1144,25 @@ def map_dissolve(handle, xy, n_points, row_index, left, right, n_chains, classes
     the capacities.  counts: DISSOLVE_COUNTS with n_edges."""
     n_points, n_chains = int(n_points), int(n_chains)
     flags = _capi.RJ_DISS_KEEP_EQUAL if keep_equal else 0
-    table, n_labels, own_table = None, 0, None
-    if isinstance(classes, tuple):
-        table, n_labels = classes[0], int(classes[1])
-    elif isinstance(classes, _capi.DeviceBuffer):
-        table, n_labels = classes, classes.nbytes // 4
-    elif classes is not None:
-        host = np.ascontiguousarray(classes, np.int32)
-        if host.ndim != 1 or len(host) == 0:
-            raise ValueError("classes must be a one-dimensional table with an entry for label 0")
-        table = own_table = handle.alloc(4 * len(host)).from_host(host)
-        n_labels = len(host)
-    bufs, recs, org, cout, done = [], None, None, None, False
-    try:
+    table, n_labels = None, 0
+    with _Owned(handle) as own, _Owned(handle) as tmp:
+        if isinstance(classes, tuple):
+            table, n_labels = classes[0], int(classes[1])
+        elif isinstance(classes, _capi.DeviceBuffer):
+            table, n_labels = classes, classes.nbytes // 4
+        elif classes is not None:
+            host = np.ascontiguousarray(classes, np.int32)
+            if host.ndim != 1 or len(host) == 0:
+                raise ValueError("classes must be a one-dimensional table with an entry for label 0")
+            table, n_labels = tmp.alloc(4 * len(host)).from_host(host), len(host)
         args = (xy, n_points, row_index, left, right, n_chains, table, n_labels)
-        try:
-            c = handle.map_dissolve(*args, (0, 0, 0), None, None, None, None, flags=flags)
-        except _capi.DissolveOverflow as e:
-            c = e.counts
+        c = _sizing_counts(handle.map_dissolve, _capi.DissolveOverflow, *args, (0, 0, 0), None, None, None, None, flags=flags)
         kc, cc, pc = c["n_classes"] if records else 0, c["n_chains"], c["n_points"]
-        bufs.append(handle.alloc(16 * max(1, pc)))
-        bufs.append(handle.alloc(4 * (cc + 1)))
-        bufs.append(handle.alloc(4 * max(1, cc)))
-        bufs.append(handle.alloc(4 * max(1, cc)))
-        if origin:
-            org, cout = handle.alloc(4 * max(1, cc)), handle.alloc(4 * max(1, n_chains))
-        if records:
-            recs = handle.alloc(_capi.DISS_CLASS_DTYPE.itemsize * max(1, kc))
+        bufs = [own.alloc(16 * max(1, pc)), own.alloc(4 * (cc + 1)), own.alloc(4 * max(1, cc)), own.alloc(4 * max(1, cc))]
+        org, cout = (own.alloc(4 * max(1, cc)), own.alloc(4 * max(1, n_chains))) if origin else (None, None)
+        recs = own.alloc(_capi.DISS_CLASS_DTYPE.itemsize * max(1, kc)) if records else None
         counts = handle.map_dissolve(*args, (kc, cc, pc), bufs[2], bufs[3], bufs[0], bufs[1], org, cout, recs, flags=flags)
-        done = True
-    finally:
-        if own_table is not None:
-            own_table.free()
-        if not done:
-            for b in bufs + [recs, org, cout]:
-                if b is not None:
-                    b.free()
+        own.release()
     return DeviceDissolvedMap(*bufs, dict(counts, n_edges=counts["n_points"] - counts["n_chains"]), recs, org, cout, n_chains)
 
 
@@ -1333,6 +1171,7 @@ class DeviceDissolvedMap(DeviceChainMap):
     (DISS_CLASS_DTYPE rows as a DeviceBuffer, or None), origin (uint32 per chain: its leader's input chain, or None),
     chain_out (uint32 per INPUT chain, or None) and the counts n_kept, n_dropped, n_skipped, n_chains, n_points, n_closed,
     n_classes, n_unmapped, n_edges."""
+    _buffers = DeviceChainMap._buffers + ("classes", "origin", "chain_out")
 
     def __init__(self, xy, row_index, left, right, counts, classes, origin, chain_out, n_input_chains):
         super().__init__(xy, row_index, left, right, counts)
@@ -1349,12 +1188,6 @@ class DeviceDissolvedMap(DeviceChainMap):
     def chain_out_to_host(self):
         return self.chain_out.to_host(np.uint32, self.n_input_chains)
 
-    def free(self):
-        super().free()
-        for b in (self.classes, self.origin, self.chain_out):
-            if b is not None:
-                b.free()
-
 
 def map_neighbours(handle, xy, n_points, row_index, left, right, n_chains, vertex=False, records=True):
     """The face adjacency table of a labelled chain map in device memory (rj_map_neighbours) as a DeviceNeighbours, in CSR
@@ -1366,31 +1199,22 @@ def map_neighbours(handle, xy, n_points, row_index, left, right, n_chains, verte
     n_points, n_chains = int(n_points), int(n_chains)
     flags = _capi.RJ_NB_VERTEX if vertex else 0
     args = (xy, n_points, row_index, left, right, n_chains)
-    try:
-        c = handle.map_neighbours(*args, (0, 0), flags=flags)
-    except _capi.NeighboursOverflow as e:
-        c = e.counts
+    c = _sizing_counts(handle.map_neighbours, _capi.NeighboursOverflow, *args, (0, 0), flags=flags)
     fc, ec = c["n_faces"], c["n_entries"]
-    faces, offsets, entries, done = None, None, None, False
-    try:
-        if records:
-            faces = handle.alloc(_capi.NB_FACE_DTYPE.itemsize * max(1, fc))
-        offsets = handle.alloc(8 * (fc + 1))
-        entries = handle.alloc(_capi.NB_ENTRY_DTYPE.itemsize * max(1, ec))
+    with _Owned(handle) as own:
+        faces = own.alloc(_capi.NB_FACE_DTYPE.itemsize * max(1, fc)) if records else None
+        offsets = own.alloc(8 * (fc + 1))
+        entries = own.alloc(_capi.NB_ENTRY_DTYPE.itemsize * max(1, ec))
         counts = handle.map_neighbours(*args, (fc, ec), faces, offsets, entries, flags=flags)
-        done = True
-    finally:
-        if not done:
-            for b in (faces, offsets, entries):
-                if b is not None:
-                    b.free()
+        own.release()
     return DeviceNeighbours(faces, offsets, entries, counts)
 
 
-class DeviceNeighbours:
+class DeviceNeighbours(_OwnsBuffers):
     """The face adjacency table of a chain map in device memory (rj_map_neighbours): faces (NB_FACE_DTYPE rows as a
     DeviceBuffer, or None), offsets (uint64 [n_faces + 1]), entries (NB_ENTRY_DTYPE rows) and the counts n_faces, n_entries,
     n_edge_pairs, n_vertex_pairs, n_nodes, n_node_pairs_raw, max_labels_at_node."""
+    _buffers = ("faces", "offsets", "entries")
 
     def __init__(self, faces, offsets, entries, counts):
         self.faces, self.offsets, self.entries = faces, offsets, entries
@@ -1423,11 +1247,6 @@ class DeviceNeighbours:
         handle.neighbours_labels(self.faces, self.n_faces, out)
         return out
 
-    def free(self):
-        for b in (self.faces, self.offsets, self.entries):
-            if b is not None:
-                b.free()
-
 
 def face_points(handle, labels, n, values=None, value_stride=1, faces=None, members=False, records=True):
     """Per-face counts, sums and members of n located points in device memory (rj_face_points) as a DeviceFacePoints.
@@ -1440,36 +1259,25 @@ def face_points(handle, labels, n, values=None, value_stride=1, faces=None, memb
     flags = _capi.RJ_FP_MEMBERS if members else 0
     universe, n_universe = (None, 0) if faces is None else (tuple(faces) if isinstance(faces, (tuple, list)) else (faces, faces.count))
     kw = dict(value_dev=values, value_stride=value_stride, face_label_dev=universe, n_face_labels=n_universe, flags=flags)
-    try:
-        c = handle.face_points(labels, n, (0, 0), **kw)
-    except _capi.FacePointsOverflow as e:
-        c = e.counts
+    c = _sizing_counts(handle.face_points, _capi.FacePointsOverflow, labels, n, (0, 0), **kw)
     fc, mc = c["n_faces"], c["n_members"] if members else 0
-    recs, offsets, mem, done = None, None, None, False
-    try:
-        if records:
-            recs = handle.alloc(_capi.FP_FACE_DTYPE.itemsize * max(1, fc))
-        if members:
-            offsets = handle.alloc(8 * (fc + 1))
-            mem = handle.alloc(4 * max(1, mc))
-        counts = handle.face_points(labels, n, (fc if records or members else 0, mc), faces_dev=recs, offsets_dev=offsets, members_dev=mem, **kw)
-        done = True
-    except _capi.FacePointsOverflow as e:
+    with _Owned(handle) as own:
+        recs = own.alloc(_capi.FP_FACE_DTYPE.itemsize * max(1, fc)) if records else None
+        offsets, mem = (own.alloc(8 * (fc + 1)), own.alloc(4 * max(1, mc))) if members else (None, None)
         if records or members:
-            raise
-        counts, done = e.counts, True  # (neither records nor members: the counts are all there is)
-    finally:
-        if not done:
-            for b in (recs, offsets, mem):
-                if b is not None:
-                    b.free()
+            counts = handle.face_points(labels, n, (fc, mc), faces_dev=recs, offsets_dev=offsets, members_dev=mem, **kw)
+        else:  # (neither records nor members: the counts are all there is, and the call may raise them again)
+            counts = _sizing_counts(handle.face_points, _capi.FacePointsOverflow, labels, n, (0, mc), faces_dev=None, offsets_dev=None,
+                                    members_dev=None, **kw)
+        own.release()
     return DeviceFacePoints(recs, offsets, mem, counts)
 
 
-class DeviceFacePoints:
+class DeviceFacePoints(_OwnsBuffers):
     """Per-face counts, sums and members of located points in device memory (rj_face_points): faces (FP_FACE_DTYPE rows as a
     DeviceBuffer, or None), under members offsets (uint64 [n_faces + 1]) and members (uint32 point numbers, ascending
     inside every face), else None, and the counts n_faces, n_members, n_outside, n_unmatched, n_runs."""
+    _buffers = ("faces", "offsets", "members")
 
     def __init__(self, faces, offsets, members, counts):
         self.faces, self.offsets, self.members = faces, offsets, members
@@ -1499,17 +1307,13 @@ class DeviceFacePoints:
         f = self.faces_to_host()
         return [(int(hi) << 64) + int(lo) for lo, hi in zip(f["sum_lo"], f["sum_hi"])]
 
-    def free(self):
-        for b in (self.faces, self.offsets, self.members):
-            if b is not None:
-                b.free()
 
-
-class DevicePolygons:
+class DevicePolygons(_OwnsBuffers):
     """The polygons of a DeviceRings in device memory (rj_rings_polygons): parent (uint32 per ring: the shell's ring index
     for a hole, its own for a shell, RJ_POLY_NONE for a ring of face 0 and for an orphan), polygons (POLYGON_DTYPE rows,
     ascending by shell), poly_first (uint32 CSR of the polygons into poly_ring) and poly_ring (uint32 ring indices: the
     shell, then its holes) as DeviceBuffers, and the counts n_polygons, n_members, n_holes, n_orphans, n_face0."""
+    _buffers = ("parent", "polygons_", "poly_first", "poly_ring")
 
     def __init__(self, parent, polygons, poly_first, poly_ring, n_rings, counts):
         self.parent, self.polygons_, self.poly_first, self.poly_ring = parent, polygons, poly_first, poly_ring
@@ -1541,10 +1345,6 @@ class DevicePolygons:
             members = host["poly_ring"][first[k]:first[k + 1]].tolist()
             out.append((int(g["face"]), (int(g["area2_hi"]) << 64) | int(g["area2_lo"]), points(members[0]), [points(r) for r in members[1:]]))
         return out
-
-    def free(self):
-        for b in (self.parent, self.polygons_, self.poly_first, self.poly_ring):
-            b.free()
 
 
 def overlay_op(how, by):
