@@ -1077,6 +1077,51 @@ int rj_within_query(rj_handle h, int base_map_id, int query_map_id, const int64_
                     rj_near* rec_dev /* [pair_capacity], may be NULL */, double* dist_dev /* [pair_capacity], may be NULL */,
                     rj_within_counts* counts);
 
+/* ---- window: the edges of the base map that meet each rectangle, as a CSR ---- */
+typedef struct { uint64_t n_pairs, n_windows_hit, max_per_window; } rj_window_counts;
+
+/* extends: the question every spatial index is asked first -- which edges meet this rectangle: a bounding-box select,
+ * sindex.query(box) / .cx[...], the linework of a tile, "which chains does this extent touch, before I clip", a bbox join
+ * of a million feature envelopes against a map.  The fifth query over the index of rj_build_lbvh.  (The reference has no
+ * counterpart.)
+ * Windows: win_dev[nw][4] = (x0, y0, x1, y1) in device memory, in the scaled coordinates of the maps: the CLOSED rectangle
+ * [x0, x1] x [y0, y1].  x0 > x1 or y0 > y1 is the empty window: it lists nothing and is no error.  A point and an
+ * axis-parallel segment are valid windows.  Coordinates may lie outside the scaled range [-2^46, 2^46): a window is cut to
+ * the range first, which changes no result (a window wholly beside the range lists nothing).  nw < 2^32.
+ * The definition, in full in rayjoin_amd/csrc/rj_window.h: edge e = (A, B) belongs to window w iff the closed segment and
+ * the closed rectangle share a point -- the bounding box of (A, B) overlaps w, and the four corners of w are not all
+ * strictly on one side of the line through A and B (cross products in 128 bits, exact).  Touching counts.
+ * Output, caller-owned device memory: offsets_dev[nw + 1] (may be NULL), eid_dev[pair_capacity]: the eids of window i lie
+ * at eid_dev[offsets[i] .. offsets[i + 1]), ASCENDING in eid, offsets[0] == 0 and offsets[nw] == n_pairs.
+ * flags_dev[pair_capacity] (may be NULL): one byte per pair, bit 0: the edge's first point lies in w (closed), bit 1: its
+ * second point does -- 3: wholly inside, 0: it passes through or touches with both ends outside, 1 or 2: it leaves
+ * through the border; what a clipper needs.  *counts: n_pairs, n_windows_hit = the windows with a list that is not empty,
+ * max_per_window = the longest list.
+ * pair_capacity == 0 is the counting call: eid_dev and flags_dev may be NULL and are not touched, offsets_dev (if given)
+ * and *counts are written, RJ_OK.  RJ_E_OVERFLOW when pair_capacity > 0 and n_pairs > pair_capacity: *counts holds the
+ * true counts and offsets_dev (if given) the true offsets; eid_dev and flags_dev are untouched.  nw == 0 is valid: the
+ * counts are zero and offsets_dev[0] = 0 if given.
+ * RJ_E_INVALID, with nothing written, *counts neither: a base map id that is not 0 or 1, no index on the base map, a null
+ * counts, nw > 0 with a null win_dev, pair_capacity > 0 with a null eid_dev, nw >= 2^32, pair_capacity >= 2^32.
+ * RJ_E_INTERNAL when the traversal's stack overflowed (cannot happen on a tree that rj_build_lbvh accepts).
+ * Runs on the handle's stream and is synchronised when it returns; inside it one more host sync, behind the scan of the
+ * counts.  The result depends on no option.  No map, index, option or cached point order of the handle changes.
+ * Scratch is allocated per call and freed: 12 bytes per window and 8 bytes per pair of capacity, then 8 bytes per pair
+ * found, plus rocPRIM's temporaries of one scan and one radix sort (rayjoin_amd/csrc/rj_window.h); the counting call takes
+ * the per-window part only.
+ * rj_get_option: "window_last_us0" .. "window_last_us2" (HIP-event microseconds of the stages: traversal, sort + outputs,
+ * all; -1: no call yet, or the last call was refused or had nw == 0).  Under "stats" 1 rj_last_stats gives [0] nodes
+ * expanded, [1] leaf blocks loaded, [2] pairs tested exactly, [3] pairs handed out by containment (below a box inside
+ * the window: no test), [4] pairs appended.  For tests and sweeps, through rj_set_debug_option: "window_blocks" (0: by
+ * size) is the grid of the traversal, "window_start_level" (0: by rule, otherwise 1 .. 5, above the tree's top: the top)
+ * the level of the tree its work items start at, "window_contained" (1; 0 switches the containment shortcut off); any
+ * value of any of them gives the same result.
+ * Not here: the faces a window meets, clipping the geometry, sharding across GPUs. */
+int rj_window_query(rj_handle h, int base_map_id, const int64_t* win_dev /* [nw][4] */, uint64_t nw,
+                    uint64_t pair_capacity, uint64_t* offsets_dev /* [nw + 1], may be NULL */,
+                    uint32_t* eid_dev /* [pair_capacity] */, uint8_t* flags_dev /* [pair_capacity], may be NULL */,
+                    rj_window_counts* counts);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 typedef enum {
   RJ_T_BUILD = 0,     /* whole rj_build_lbvh */

@@ -82,6 +82,7 @@ FACE_POINTS_COUNTS = ("n_faces", "n_members", "n_outside", "n_unmatched", "n_run
 # squared length of the edge, d^2 = num^2 / den; where 1, 2 (first, second end): num = d^2, den = 1; a miss: eid = MISS_EID, the rest 0
 NEAR_DTYPE = np.dtype([("eid", "<u4"), ("where", "<u4"), ("num_lo", "<u8"), ("num_hi", "<i8"), ("den_lo", "<u8"), ("den_hi", "<u8")])
 WITHIN_COUNTS = ("n_pairs", "n_points_hit", "max_per_point")
+WINDOW_COUNTS = ("n_pairs", "n_windows_hit", "max_per_window")
 ELIMINATE_COUNTS = ("n_faces", "n_slivers", "n_eliminated", "n_islands", "n_mutual", "n_negative", "n_chains", "n_points", "n_dropped")
 
 # every symbol include/rayjoin_amd.h declares: name -> (restype, argtypes)
@@ -146,6 +147,7 @@ SYMBOLS = {
     "rj_neighbours_labels": (_int, [_vp, _vp, _u64, _vp]),
     "rj_nearest_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _i64, _vp, _vp, _vp]),
     "rj_within_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _i64, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "rj_window_query": (_int, [_vp, _int, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_pip_query_async": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
     "rj_build_grid": (_int, [_vp, _int, _int]),
@@ -281,6 +283,10 @@ class FacePointsOverflow(CountsOverflow):
 
 class WithinOverflow(CountsOverflow):
     """RJ_E_OVERFLOW of rj_within_query: counts = a dict of WITHIN_COUNTS, the true counts; the offsets are written, the pairs are not"""
+
+
+class WindowOverflow(CountsOverflow):
+    """RJ_E_OVERFLOW of rj_window_query: counts = a dict of WINDOW_COUNTS, the true counts; the offsets are written, the pairs are not"""
 
 
 class NeighboursNodePairs(RayJoinError):
@@ -811,6 +817,16 @@ class Handle:
         Synchronous."""
         return self._counted(self.L.rj_within_query, WITHIN_COUNTS, WithinOverflow, base_map_id, query_map_id, _ptr(pts_dev), int(pt_begin), int(n),
                              int(max_dist), int(pair_capacity), _ptr(offsets_dev), _ptr(eid_dev), _ptr(rec_dev), _ptr(dist_dev))
+
+    def window_query(self, base_map_id, win_dev, nw, pair_capacity=0, offsets_dev=None, eid_dev=None, flags_dev=None):
+        """rj_window_query: for nw windows (win_dev: int64 (x0, y0, x1, y1) in device memory, closed rectangles in scaled
+        coordinates) every edge of the indexed base map that shares a point with the window, exactly, as a CSR: the uint64
+        offsets_dev [nw + 1] (or None) and, ascending per window, the eids into eid_dev (uint32) and one byte of flags into
+        flags_dev (uint8, or None: bit 0 the first point lies in the window, bit 1 the second), each of pair_capacity
+        entries.  pair_capacity 0 is the counting call.  Returns the counts as a dict (WINDOW_COUNTS); WindowOverflow (with
+        the true counts) past the capacity.  Synchronous."""
+        return self._counted(self.L.rj_window_query, WINDOW_COUNTS, WindowOverflow, base_map_id, _ptr(win_dev), int(nw), int(pair_capacity),
+                             _ptr(offsets_dev), _ptr(eid_dev), _ptr(flags_dev))
 
     def last_ms(self, which):
         ms = C.c_float()

@@ -23,6 +23,7 @@
 #include "rj_face_points.h"
 #include "rj_nearest.h"
 #include "rj_within.h"
+#include "rj_window.h"
 #include "rj_neighbours.h"
 #include "rj_overlay_dev.h"
 #include "rj_overlay_ops.h"
@@ -325,6 +326,10 @@ struct rj_handle_s {
   int nearest_unordered_next = 0;
   int debug_within_blocks = 0;  // rj_within_query: the grid of the traversal (0: by size; tests and sweeps: the same result)
   StageMs within_report;  // what the last rj_within_query took: ordering, traversal, sort + outputs, (nothing), (nothing), all (reports only)
+  // rj_window_query: the grid of the traversal (0: by size), the level it starts at (0: by rule), the containment shortcut
+  // (1: on) -- tests and sweeps: the same result
+  int debug_window_blocks = 0, debug_window_start_level = 0, debug_window_contained = 1;
+  StageMs window_report;  // what the last rj_window_query took: traversal, sort + outputs, (nothing) x 3, all (reports only)
   uint32_t stitch_stats[4] = {0, 0, 0, 0};  // the last run cutting: ranking rounds, incidences on closed loops, rounds of the second ranking, closed chains
   char* strip_scratch = nullptr;  // grow-only temporaries of the column index's build
   size_t strip_scratch_bytes = 0;
@@ -686,6 +691,9 @@ const Option kOptions[] = {
     {"nearest_blocks", true, &rj_handle_s::debug_nearest_blocks, 0, 1 << 20},  // rj_nearest_query: blocks of its traversal (0: by size)
     {"nearest_order_nomem", true, &rj_handle_s::debug_nearest_order_nomem, 0, 1},  // rj_nearest_query and rj_within_query: the ordering pass behaves as without memory (the fallback)
     {"within_blocks", true, &rj_handle_s::debug_within_blocks, 0, 1 << 20},  // rj_within_query: blocks of its traversal (0: by size)
+    {"window_blocks", true, &rj_handle_s::debug_window_blocks, 0, 1 << 20},  // rj_window_query: blocks of its traversal (0: by size)
+    {"window_start_level", true, &rj_handle_s::debug_window_start_level, 0, kMaxTop},  // ... the level its work items start at (0: by rule; above the top: the top)
+    {"window_contained", true, &rj_handle_s::debug_window_contained, 0, 1},  // ... 0: no containment shortcut, every pair is tested exactly
 };
 
 const Option* find_option(const char* name, bool debug) {
@@ -783,6 +791,7 @@ const Report kReports[] = {
     {"face_points_last_us", 5, RJ_READ(h->face_points_report.ms[k == 4 ? 5 : k] < 0 ? -1 : (int64_t) (h->face_points_report.ms[k == 4 ? 5 : k] * 1000.0f))},  // the last rj_face_points: universe, table, records, members, all
     {"nearest_last_us", 3, RJ_READ(h->nearest_report.ms[k == 2 ? 5 : k] < 0 ? -1 : (int64_t) (h->nearest_report.ms[k == 2 ? 5 : k] * 1000.0f))},  // the last rj_nearest_query: ordering, traversal, all
     {"within_last_us", 4, RJ_READ(h->within_report.ms[k == 3 ? 5 : k] < 0 ? -1 : (int64_t) (h->within_report.ms[k == 3 ? 5 : k] * 1000.0f))},  // the last rj_within_query: ordering, traversal, sort + outputs, all
+    {"window_last_us", 3, RJ_READ(h->window_report.ms[k == 2 ? 5 : k] < 0 ? -1 : (int64_t) (h->window_report.ms[k == 2 ? 5 : k] * 1000.0f))},  // the last rj_window_query: traversal, sort + outputs, all
     {"comm_ranks", 0, read_comm_ranks},
     {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
     {"pip_share_blocks", 0, RJ_READ(h->last_pip_share ? h->last_pip_share : h->pip_share_blocks())},
@@ -896,7 +905,7 @@ int rj_create(int device_id, rj_handle* out) {
             hipHostMalloc((void**) &h->h_est, 64, hipHostMallocMapped) == hipSuccess &&
             hipHostGetDevicePointer((void**) &h->d_est, h->h_est, 0) == hipSuccess;
   if (ok) {
-    h->h_fault[0] = h->h_fault[1] = h->h_fault[kFaultNearestStack] = h->h_fault[kFaultWithinStack] = 0;
+    h->h_fault[0] = h->h_fault[1] = h->h_fault[kFaultNearestStack] = h->h_fault[kFaultWithinStack] = h->h_fault[kFaultWindowStack] = 0;
     h->h_rest[0] = h->h_rest[1] = ~0ull;  // (no finished two-pass query yet)
     h->h_rest[2] = ~0ull;                 // (... and no records produced yet: k_lsi_points' pair count)
     h->h_rest[rj_handle_s::kRest3Word] = ~0ull;
@@ -2502,6 +2511,58 @@ int rj_within_query(rj_handle h, int base_map_id, int query_map_id, const int64_
   memcpy(counts, &res.counts, sizeof(*counts));
   if (pair_capacity && !res.emitted)
     return fail(h, RJ_E_OVERFLOW, "rj_within_query: %llu pairs; capacity %llu", (unsigned long long) counts->n_pairs, (unsigned long long) pair_capacity);
+  return RJ_OK;
+}
+
+// ---- the edges of the base map that meet each rectangle (rj_window.h, rj_window.hip) ----------------------------------------
+int rj_window_query(rj_handle h, int base_map_id, const int64_t* win_dev, uint64_t nw, uint64_t pair_capacity, uint64_t* offsets_dev, uint32_t* eid_dev,
+                    uint8_t* flags_dev, rj_window_counts* counts) {
+  static_assert(sizeof(rj_window_counts) == sizeof(window::Counts), "layouts");
+  static_assert(window::kMaxWindows == within::kMaxPoints, "the size rule of check_distance_call");
+  RJ_CHECK_H(h);
+  h->window_report = StageMs{};
+  // the distance queries' frame: the windows stand where a caller's points stand (no query map is looked at), no distance
+  static const int64_t no_window[4] = {0, 0, 0, 0};
+  const int64_t* win;
+  uint64_t unused;
+  if (int r = check_distance_call(h, "rj_window_query",
+                                  !counts ? "counts is null" : (nw && !win_dev ? "nw without win_dev" : (pair_capacity && !eid_dev ? "pair_capacity without eid_dev" : nullptr)),
+                                  base_map_id, 1 - base_map_id, win_dev ? win_dev : no_window, 0, nw, 0, 0, nw > pair_capacity ? nw : pair_capacity,
+                                  "nw < 2^32 and pair_capacity < 2^32", &win, &unused))
+    return r;
+  if (int r = set_device(h)) return r;
+  memset(counts, 0, sizeof(*counts));
+  if (nw == 0) {
+    if (offsets_dev) {
+      RJ_HIP(h, hipMemsetAsync(offsets_dev, 0, sizeof(uint64_t), h->stream));
+      RJ_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return RJ_OK;
+  }
+  StageEvents ev;
+  RJ_HIP(h, ev.create());
+  if (h->stats_on) RJ_HIP(h, hipMemsetAsync(h->d_stats, 0, 128, h->stream));
+  WindowArgs a;
+  a.bvh = bvh_view(h->bvh[base_map_id]);
+  a.seg = h->map[base_map_id].seg;
+  a.win = win; a.nw = nw;
+  a.capacity = pair_capacity;
+  a.offsets = offsets_dev;
+  a.eid = eid_dev; a.flags = flags_dev;
+  a.fault = h->d_fault;
+  a.stats = h->stats_on ? h->d_stats : nullptr;
+  a.stack_cap = h->debug_stack_cap;
+  a.start_level = h->debug_window_start_level;
+  a.contained = h->debug_window_contained != 0;
+  WindowResult res;
+  RJ_HIP(h, window_device(h->stream, a, h->stats_on != 0, h->debug_window_blocks, h->cus, &ev, &res));
+  if (int r = finish_distance_call(h, kFaultWindowStack, "k_window")) return r;
+  if (res.appended != res.counts.n_pairs)
+    return fail(h, RJ_E_INTERNAL, "rj_window_query: %llu pairs appended, %llu counted", (unsigned long long) res.appended, (unsigned long long) res.counts.n_pairs);
+  ev.times(2, h->window_report.ms);
+  memcpy(counts, &res.counts, sizeof(*counts));
+  if (pair_capacity && !res.emitted)
+    return fail(h, RJ_E_OVERFLOW, "rj_window_query: %llu pairs; capacity %llu", (unsigned long long) counts->n_pairs, (unsigned long long) pair_capacity);
   return RJ_OK;
 }
 

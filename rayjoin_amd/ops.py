@@ -68,6 +68,10 @@
       .get_eids(); .get_records(); .get_dist(); .to_csr(); .counts()
       -- every edge of the indexed map within max_dist of each point, as a CSR over the points (rj_within_query): dwithin,
          Select by distance, Generate Near Table (all)
+  WindowLBVH(ctx).Init(n_windows, pair_capacity); .Query(base_map_id, windows, flags=, grow=); .Count(...); .get_offsets();
+      .get_eids(); .get_flags(); .to_csr(); .counts()
+      -- every edge of the indexed map that meets each closed rectangle (x0, y0, x1, y1), as a CSR over the windows
+         (rj_window_query): the bounding-box select, sindex.query(box), the linework of a tile
 
 Same names, argument meaning and error behaviour, with two deliberate differences recorded in
 DESIGN.md: LSI pairs are always evaluated as (e1 = map-0 edge, e2 = map-1 edge) so results
@@ -446,6 +450,106 @@ class WithinLBVH(_DistanceQuery):
 
     def free(self):
         self._free("offsets", "eids", "records", "dist")
+        self.capacity = 0
+
+
+class WindowLBVH(_OwnsBuffers):
+    """The edges of the indexed base map that meet each window (rj_window_query): a CSR over the windows -- offsets, and one
+    row per pair: the eid (ascending per window) and the flags byte (bit 0: the edge's first point lies in the window,
+    bit 1: its second point does)."""
+    _buffers = ("offsets", "eids", "flags")
+
+    def __init__(self, dctx):
+        self.ctx_ = dctx
+        self.h = dctx.handle
+        self.offsets = self.eids = self.flags = None
+        self.n = self.n_pairs = self.n_alloc = self.capacity = 0
+        self.has_flags = False
+        self.counts_ = dict.fromkeys(_capi.WINDOW_COUNTS, 0)
+
+    def Init(self, n_windows, pair_capacity):
+        self.free()
+        self.n_alloc = int(n_windows)
+        self.offsets = self.h.alloc(8 * (self.n_alloc + 1))
+        self._alloc_pairs(int(pair_capacity))
+
+    def _alloc_pairs(self, capacity):
+        for name in ("eids", "flags"):
+            if getattr(self, name) is not None:
+                getattr(self, name).free()
+        self.capacity = capacity
+        self.eids = self.h.alloc(4 * max(1, capacity))
+        self.flags = self.h.alloc(max(1, capacity))
+
+    def _over_windows(self, windows, call):
+        """call(device windows, n) over an (n, 4) int64 host array, staged for the call and freed behind it, or over a
+        contiguous int64 device tensor of that shape (anything with data_ptr() and shape) -> (n, what call returned)"""
+        if hasattr(windows, "data_ptr"):
+            shape = tuple(windows.shape)
+            assert len(shape) == 2 and shape[1] == 4
+            assert not hasattr(windows, "is_contiguous") or (windows.is_contiguous() and windows.element_size() == 8)
+            n = int(shape[0])
+            assert n <= self.n_alloc
+            return n, call(windows, n)
+        win = np.ascontiguousarray(windows, dtype=np.int64).reshape(-1, 4)
+        n = win.shape[0]
+        assert n <= self.n_alloc
+        with _Owned(self.h) as tmp:
+            return n, call(tmp.alloc(32 * max(1, n)).from_host(win), n)
+
+    def _call(self, base_map_id, windows, capacity, flags):
+        eids = self.eids if capacity else None
+        return self._over_windows(windows, lambda buf, n: self.h.window_query(base_map_id, buf, n, capacity, self.offsets, eids, flags))
+
+    def Query(self, base_map_id, windows, flags=True, grow=True):
+        """windows: (n, 4) int64 (x0, y0, x1, y1), closed rectangles in scaled coordinates, a host array or a device tensor.
+        flags: whether the call fills them.  grow: on an overflow (or with a capacity of 0) the pair arrays are allocated
+        again at the true count and the call repeats once; otherwise _capi.WindowOverflow with the true counts.  Returns
+        n_pairs."""
+        self.n_pairs, self.has_flags = 0, False
+        if self.capacity and not grow:
+            n, counts = self._call(base_map_id, windows, self.capacity, self.flags if flags else None)
+        else:  # the counted call: the counting call of a capacity of 0, or a call whose overflow carries the true counts
+            eids, fl = (self.eids, self.flags if flags else None) if self.capacity else (None, None)
+            n, counts = self._over_windows(windows, lambda buf, n: _sizing_counts(self.h.window_query, _capi.WindowOverflow, base_map_id, buf, n,
+                                                                                  self.capacity, self.offsets, eids, fl))
+            if counts["n_pairs"] > self.capacity:
+                if not grow:
+                    raise _capi.WindowOverflow("rj_window_query: %d pairs; capacity 0" % counts["n_pairs"], counts)
+                self._alloc_pairs(counts["n_pairs"])  # the sized call: once more at the true count
+                n, counts = self._call(base_map_id, windows, self.capacity, self.flags if flags else None)
+        self.n, self.n_pairs, self.counts_, self.has_flags = n, counts["n_pairs"], counts, bool(flags)
+        return self.n_pairs
+
+    def Count(self, base_map_id, windows):
+        """the counting call: how many edges meet each window -> uint64[n]; nothing but the offsets and the counts is written"""
+        n, counts = self._call(base_map_id, windows, 0, None)
+        self.n, self.n_pairs, self.counts_, self.has_flags = n, 0, counts, False
+        return np.diff(self.get_offsets())
+
+    def get_offsets(self):
+        return self.offsets.to_host(np.uint64, self.n + 1)
+
+    def get_eids(self):
+        return self.eids.to_host(np.uint32, self.n_pairs)
+
+    def get_flags(self):
+        """-> uint8 per pair; ValueError after a Query with flags=False"""
+        if not self.has_flags:
+            raise ValueError("the last Query ran with flags=False")
+        return self.flags.to_host(np.uint8, self.n_pairs)
+
+    def to_csr(self):
+        """-> (indptr int64[n + 1], eids uint32[n_pairs]): row i lists the edges that meet window i, ascending"""
+        return self.get_offsets().astype(np.int64), self.get_eids()
+
+    def counts(self):
+        """the counts of the last call: n_pairs, n_windows_hit, max_per_window"""
+        return dict(self.counts_)
+
+    def free(self):
+        super().free()
+        self.offsets = self.eids = self.flags = None
         self.capacity = 0
 
 
