@@ -1030,6 +1030,48 @@ int rj_nearest_query(rj_handle h, int base_map_id, int query_map_id, const int64
                      uint64_t pt_begin, uint64_t n, int64_t max_dist,
                      uint32_t* eid_dev, rj_near* rec_dev /* may be NULL */, double* dist_dev /* may be NULL */);
 
+/* ---- k nearest: the k nearest edges of the base map for every point, in order ---- */
+#define RJ_KNEAREST_MAX_K 32
+
+/* extends: rj_nearest_query returns ONE edge, rj_within_query needs a distance that fits no two points alike; this call
+ * returns the k nearest edges of every point -- the closest-count field of Near and Generate Near Table, the candidate list
+ * of map matching (the three nearest road segments of a GPS fix).  The sixth query over the index of rj_build_lbvh.  (The
+ * reference has no counterpart.)
+ * Points, pt_begin, n and max_dist: exactly as rj_nearest_query, the cached Morton order and "nearest_order_nomem"
+ * included.  1 <= k <= RJ_KNEAREST_MAX_K.
+ * The definition, in full in rayjoin_amd/csrc/rj_knearest.h on the functions of rj_nearest.h: order all edges of the base
+ * map by (d^2, eid) ascending, d^2 = N / D as in rj_nearest_query and compared exactly, equal distances to the smaller
+ * eid; with max_dist >= 0 only edges with N <= max_dist^2 D qualify.  The answer for point i is the first
+ * count[i] = min(k, qualifying edges) entries of that order, in that order.  k = 1 gives rj_nearest_query's three arrays bit
+ * for bit.
+ * Output, caller-owned device memory, row i at the entries [i k, i k + k) (indexed in 64 bits): count_dev[n] (may be NULL);
+ * eid_dev[n][k], entry j of row i the (j + 1)-th nearest qualifying edge; rec_dev[n][k] (may be NULL) and dist_dev[n][k]
+ * (may be NULL) mean what they mean in rj_nearest_query, dist within 2^-50 relative.  The entries of a row from count[i]
+ * on are the miss: RJ_MISS_EID, the record with eid = RJ_MISS_EID and everything else 0, +inf.
+ * RJ_E_INVALID, with nothing written: everything rj_nearest_query refuses (map ids that are not {0, 1} and different, no
+ * index on the base map, a point range outside the query map, n >= 2^32, max_dist > 2^48), k == 0, k > RJ_KNEAREST_MAX_K,
+ * a null eid_dev with n > 0.  n == 0 is valid and writes nothing.  RJ_E_INTERNAL when the traversal's stack overflowed
+ * (cannot happen on a tree that rj_build_lbvh accepts).
+ * Runs on the handle's stream and is synchronised when it returns.  The result does not depend on the grid, on which wave
+ * takes which points, the order of the points, "leaf_order", "query_order", the double filter or the layout of the scratch.
+ * No map, index or option of the handle changes; the cached point orders are those of rj_pip_query.
+ * Scratch is allocated per call and freed.  It goes by the grid and by k, NOT by n: a list belongs to a wave of the grid,
+ * not to a point.  3072 k bytes per wave (64 lists of k slots of 48 bytes), four waves per block, and by size at most four
+ * blocks per compute unit -- those that are resident at once: 12 MiB x k on 256 compute units (192 MiB at k = 16, 384 MiB at
+ * k = 32) for any number of points, less where n is below 256 points per block of that grid.
+ * rj_get_option: "knearest_last_us0" .. "knearest_last_us2" (HIP-event microseconds of the stages: ordering, traversal,
+ * all; -1: no call yet, or the last call was refused or had n == 0) and "knearest_last_scratch_bytes" (the scratch of the
+ * last call; 0 where the times are -1).  Under "stats" 1 rj_last_stats gives [0] .. [3] as after rj_nearest_query and
+ * [4] the candidates that entered a list (at least the sum of the counts).  For tests and
+ * sweeps, through rj_set_debug_option: "knearest_blocks" (0: by size) is the grid -- and with it the scratch; any grid
+ * gives the same result; "nearest_order_nomem" acts here as in rj_nearest_query.
+ * Not here: k above 32 (rj_within_query is the tool there), nearest faces or chains instead of edges, sharding across
+ * GPUs. */
+int rj_knearest_query(rj_handle h, int base_map_id, int query_map_id, const int64_t* pts_dev,
+                      uint64_t pt_begin, uint64_t n, uint32_t k, int64_t max_dist,
+                      uint32_t* count_dev /* [n], may be NULL */, uint32_t* eid_dev /* [n][k] */,
+                      rj_near* rec_dev /* [n][k], may be NULL */, double* dist_dev /* [n][k], may be NULL */);
+
 /* ---- within: every edge of the base map within a distance of each point, as a CSR ---- */
 typedef struct { uint64_t n_pairs, n_points_hit, max_per_point; } rj_within_counts;
 

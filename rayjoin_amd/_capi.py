@@ -29,6 +29,7 @@ RJ_CROSS_PROPER, RJ_CROSS_TOUCH, RJ_CROSS_OVERLAP, RJ_CROSS_EQUAL = 1, 2, 3, 4  
 RJ_T_BUILD, RJ_T_LSI_KERNEL, RJ_T_PIP_KERNEL, RJ_T_LSI_POINTS, RJ_T_SORT, RJ_T_ORDER = 0, 1, 2, 3, 4, 5
 RJ_T_BUILD_KEYS, RJ_T_BUILD_SORT, RJ_T_BUILD_LEAVES, RJ_T_BUILD_LEVELS, RJ_T_PIP_WALK, RJ_T_BUILD_RUNS = 6, 7, 8, 9, 10, 11
 MISS_EID = 0xFFFFFFFF
+KNEAREST_MAX_K = 32  # RJ_KNEAREST_MAX_K
 
 XSECT_DTYPE = np.dtype(
     [("x_num", "<i8"), ("x_den", "<i8"), ("y_num", "<i8"), ("y_den", "<i8"),
@@ -146,6 +147,7 @@ SYMBOLS = {
     "rj_face_points": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, C.c_uint32, _u64, _u64, _vp, _vp, _vp, _vp]),
     "rj_neighbours_labels": (_int, [_vp, _vp, _u64, _vp]),
     "rj_nearest_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _i64, _vp, _vp, _vp]),
+    "rj_knearest_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, C.c_uint32, _i64, _vp, _vp, _vp, _vp]),
     "rj_within_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _i64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "rj_window_query": (_int, [_vp, _int, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "rj_pip_query": (_int, [_vp, _int, _int, _vp, _u64, _u64, _vp, _vp]),
@@ -806,6 +808,16 @@ class Handle:
         miss, or None).  max_dist: negative = unlimited, else only edges with d <= max_dist qualify, exactly.  Synchronous."""
         self._check(self.L.rj_nearest_query(self.h, base_map_id, query_map_id, _ptr(pts_dev), int(pt_begin), int(n), int(max_dist), _ptr(eid_dev),
                                             _ptr(rec_dev), _ptr(dist_dev)))
+
+    def knearest_query(self, base_map_id, query_map_id, pts_dev, pt_begin, n, k, eid_dev, count_dev=None, rec_dev=None, dist_dev=None, max_dist=-1):
+        """rj_knearest_query: for n points (pts_dev: int64 pairs in device memory, or None for the vertices [pt_begin, pt_begin + n)
+        of the query map) the eids of the k (1 .. KNEAREST_MAX_K) nearest edges of the indexed base map, nearest first, equal
+        distances to the smaller eid, into row i of eid_dev (uint32 [n][k]); how many there are into count_dev (uint32 [n], or
+        None), the exact records into rec_dev (NEAR_DTYPE [n][k], or None) and sqrt(d^2) into dist_dev (float64 [n][k], or
+        None); the entries of a row behind its count are the miss (MISS_EID, a zero record, +inf).  max_dist: negative =
+        unlimited, else only edges with d <= max_dist qualify, exactly.  Synchronous."""
+        self._check(self.L.rj_knearest_query(self.h, base_map_id, query_map_id, _ptr(pts_dev), int(pt_begin), int(n), int(k), int(max_dist),
+                                             _ptr(count_dev), _ptr(eid_dev), _ptr(rec_dev), _ptr(dist_dev)))
 
     def within_query(self, base_map_id, query_map_id, pts_dev, pt_begin, n, max_dist, pair_capacity=0, offsets_dev=None, eid_dev=None, rec_dev=None,
                      dist_dev=None):

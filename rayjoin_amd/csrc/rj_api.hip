@@ -22,6 +22,7 @@
 #include "rj_kernels.h"
 #include "rj_face_points.h"
 #include "rj_nearest.h"
+#include "rj_knearest.h"
 #include "rj_within.h"
 #include "rj_window.h"
 #include "rj_neighbours.h"
@@ -326,6 +327,9 @@ struct rj_handle_s {
   int nearest_unordered_next = 0;
   int debug_within_blocks = 0;  // rj_within_query: the grid of the traversal (0: by size; tests and sweeps: the same result)
   StageMs within_report;  // what the last rj_within_query took: ordering, traversal, sort + outputs, (nothing), (nothing), all (reports only)
+  int debug_knearest_blocks = 0;  // rj_knearest_query: the grid of the traversal (0: by size; tests and sweeps: the same result)
+  StageMs knearest_report;  // what the last rj_knearest_query took: ordering, traversal, (nothing), (nothing), (nothing), all (reports only)
+  uint64_t knearest_scratch = 0;  // ... and the bytes of its scratch (0: refused, or n == 0)
   // rj_window_query: the grid of the traversal (0: by size), the level it starts at (0: by rule), the containment shortcut
   // (1: on) -- tests and sweeps: the same result
   int debug_window_blocks = 0, debug_window_start_level = 0, debug_window_contained = 1;
@@ -691,6 +695,7 @@ const Option kOptions[] = {
     {"nearest_blocks", true, &rj_handle_s::debug_nearest_blocks, 0, 1 << 20},  // rj_nearest_query: blocks of its traversal (0: by size)
     {"nearest_order_nomem", true, &rj_handle_s::debug_nearest_order_nomem, 0, 1},  // rj_nearest_query and rj_within_query: the ordering pass behaves as without memory (the fallback)
     {"within_blocks", true, &rj_handle_s::debug_within_blocks, 0, 1 << 20},  // rj_within_query: blocks of its traversal (0: by size)
+    {"knearest_blocks", true, &rj_handle_s::debug_knearest_blocks, 0, 1 << 20},  // rj_knearest_query: blocks of its traversal (0: by size); its scratch goes by them
     {"window_blocks", true, &rj_handle_s::debug_window_blocks, 0, 1 << 20},  // rj_window_query: blocks of its traversal (0: by size)
     {"window_start_level", true, &rj_handle_s::debug_window_start_level, 0, kMaxTop},  // ... the level its work items start at (0: by rule; above the top: the top)
     {"window_contained", true, &rj_handle_s::debug_window_contained, 0, 1},  // ... 0: no containment shortcut, every pair is tested exactly
@@ -791,6 +796,8 @@ const Report kReports[] = {
     {"face_points_last_us", 5, RJ_READ(h->face_points_report.ms[k == 4 ? 5 : k] < 0 ? -1 : (int64_t) (h->face_points_report.ms[k == 4 ? 5 : k] * 1000.0f))},  // the last rj_face_points: universe, table, records, members, all
     {"nearest_last_us", 3, RJ_READ(h->nearest_report.ms[k == 2 ? 5 : k] < 0 ? -1 : (int64_t) (h->nearest_report.ms[k == 2 ? 5 : k] * 1000.0f))},  // the last rj_nearest_query: ordering, traversal, all
     {"within_last_us", 4, RJ_READ(h->within_report.ms[k == 3 ? 5 : k] < 0 ? -1 : (int64_t) (h->within_report.ms[k == 3 ? 5 : k] * 1000.0f))},  // the last rj_within_query: ordering, traversal, sort + outputs, all
+    {"knearest_last_us", 3, RJ_READ(h->knearest_report.ms[k == 2 ? 5 : k] < 0 ? -1 : (int64_t) (h->knearest_report.ms[k == 2 ? 5 : k] * 1000.0f))},  // the last rj_knearest_query: ordering, traversal, all
+    {"knearest_last_scratch_bytes", 0, RJ_READ(h->knearest_scratch)},  // ... the lists of its grid's waves: by the grid and by k, not by n
     {"window_last_us", 3, RJ_READ(h->window_report.ms[k == 2 ? 5 : k] < 0 ? -1 : (int64_t) (h->window_report.ms[k == 2 ? 5 : k] * 1000.0f))},  // the last rj_window_query: traversal, sort + outputs, all
     {"comm_ranks", 0, read_comm_ranks},
     {"lsi_share_blocks", 0, RJ_READ(h->lsi_share_blocks())},
@@ -905,7 +912,7 @@ int rj_create(int device_id, rj_handle* out) {
             hipHostMalloc((void**) &h->h_est, 64, hipHostMallocMapped) == hipSuccess &&
             hipHostGetDevicePointer((void**) &h->d_est, h->h_est, 0) == hipSuccess;
   if (ok) {
-    h->h_fault[0] = h->h_fault[1] = h->h_fault[kFaultNearestStack] = h->h_fault[kFaultWithinStack] = h->h_fault[kFaultWindowStack] = 0;
+    h->h_fault[0] = h->h_fault[1] = h->h_fault[kFaultNearestStack] = h->h_fault[kFaultWithinStack] = h->h_fault[kFaultWindowStack] = h->h_fault[kFaultKNearestStack] = 0;
     h->h_rest[0] = h->h_rest[1] = ~0ull;  // (no finished two-pass query yet)
     h->h_rest[2] = ~0ull;                 // (... and no records produced yet: k_lsi_points' pair count)
     h->h_rest[rj_handle_s::kRest3Word] = ~0ull;
@@ -2461,6 +2468,58 @@ int rj_nearest_query(rj_handle h, int base_map_id, int query_map_id, const int64
   RJ_HIP(h, hipStreamSynchronize(h->stream));
   ev.times(2, h->nearest_report.ms);
   return finish_distance_call(h, kFaultNearestStack, "k_nearest");
+}
+
+// ---- the k nearest edges of the base map for every point (rj_knearest.h, rj_knearest.hip) -----------------------------------
+// (everything of the call that runs while its scratch -- the lists of the grid's waves -- is alive; synchronised at the end)
+static int knearest_with_slab(rj_handle h, KNearestArgs& a, dim3 grid, bool callers, int query_map_id, uint64_t coh_begin, StageEvents& ev) {
+  RJ_HIP(h, ev.mark(0, h->stream));
+  if (int r = order_distance_points(h, a.pts, callers, query_map_id, coh_begin, a.n, &a.order)) return r;
+  if (h->stats_on) RJ_HIP(h, hipMemsetAsync(h->d_stats, 0, 128, h->stream));
+  RJ_HIP(h, ev.mark(1, h->stream));
+  RJ_HIP(h, launch_knearest(h->stream, a, grid, h->stats_on != 0));
+  RJ_HIP(h, ev.mark(2, h->stream));
+  if (int r = estimate_distance_points(h, a.pts, a.n)) return r;
+  RJ_HIP(h, hipStreamSynchronize(h->stream));
+  return RJ_OK;
+}
+
+int rj_knearest_query(rj_handle h, int base_map_id, int query_map_id, const int64_t* pts_dev, uint64_t pt_begin, uint64_t n, uint32_t k, int64_t max_dist,
+                      uint32_t* count_dev, uint32_t* eid_dev, rj_near* rec_dev, double* dist_dev) {
+  static_assert(RJ_KNEAREST_MAX_K == knearest::kMaxK, "the largest k");
+  RJ_CHECK_H(h);
+  h->knearest_report = StageMs{};
+  h->knearest_scratch = 0;
+  const int64_t* pts;
+  uint64_t coh_begin;
+  if (int r = check_distance_call(h, "rj_knearest_query",
+                                  k == 0 || k > knearest::kMaxK ? "k must lie in [1, RJ_KNEAREST_MAX_K]" : (n && !eid_dev ? "null output" : nullptr),
+                                  base_map_id, query_map_id, pts_dev, pt_begin, n, max_dist, INT64_MIN, n, "n < 2^32", &pts, &coh_begin))
+    return r;
+  if (n == 0) return RJ_OK;
+  if (int r = set_device(h)) return r;
+  StageEvents ev;
+  RJ_HIP(h, ev.create());
+  KNearestArgs a;
+  a.bvh = bvh_view(h->bvh[base_map_id]);
+  a.pts = pts; a.n = n; a.order = nullptr;
+  a.k = k;
+  a.max_dist = max_dist;
+  a.count = count_dev; a.eid = eid_dev; a.rec = reinterpret_cast<nearest::Near*>(rec_dev); a.dist = dist_dev;
+  a.fault = h->d_fault;
+  a.stats = h->stats_on ? h->d_stats : nullptr;
+  a.stack_cap = h->debug_stack_cap;
+  const dim3 grid = knearest_grid(n, h->debug_knearest_blocks, h->cus);
+  a.slab = nullptr;
+  RJ_HIP(h, hipMalloc((void**) &a.slab, knearest_slab_bytes(k, grid)));
+  h->knearest_scratch = knearest_slab_bytes(k, grid);
+  const int r = knearest_with_slab(h, a, grid, pts_dev != nullptr, query_map_id, coh_begin, ev);
+  if (r != RJ_OK) (void) hipStreamSynchronize(h->stream);  // (nothing of this call runs when its scratch goes)
+  const hipError_t fe = hipFree(a.slab);
+  if (r != RJ_OK) return r;
+  RJ_HIP(h, fe);
+  ev.times(2, h->knearest_report.ms);
+  return finish_distance_call(h, kFaultKNearestStack, "k_knearest");
 }
 
 // ---- every edge of the base map within a distance of each point (rj_within.h, rj_within.hip) --------------------------------

@@ -36,7 +36,7 @@ constexpr int kMaxTop = kMaxLevels - 1;  // highest level a tree accepted by rj_
 // the handle's fault word (-> RJ_E_INTERNAL) instead of writing past the stack.
 constexpr int kStackEntries = 64 + 126 * (kMaxTop - 1);  // 568
 constexpr int kPipStack = 64 + 63 * (kMaxTop - 1) + 4;   // 320 (316 needed)
-constexpr uint32_t kFaultLsiStack = 0, kFaultPipStack = 1, kFaultNearestStack = 2, kFaultWithinStack = 3, kFaultWindowStack = 4;  // index of the kernel's word in the handle's fault words (k_nearest and k_within: the one walk of rj_distance_walk.h, k_pip's stack discipline and capacity; k_window: rj_window.hip, the same discipline and capacity)
+constexpr uint32_t kFaultLsiStack = 0, kFaultPipStack = 1, kFaultNearestStack = 2, kFaultWithinStack = 3, kFaultWindowStack = 4, kFaultKNearestStack = 5;  // index of the kernel's word in the handle's fault words (k_nearest, k_within and k_knearest: the one walk of rj_distance_walk.h, k_pip's stack discipline and capacity; k_window: rj_window.hip, the same discipline and capacity)
 // A scheduler block = 8 chunk counters 128 B apart (zeroed before every launch) followed by one
 // line that is written once: the device-visible address of the handle's fault words.
 constexpr int kSchedFaultPtrWord = 8 * 32;  // in 32-bit words from the block's start

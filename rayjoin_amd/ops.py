@@ -64,6 +64,10 @@
   NearestLBVH(ctx).Init(n_points); .Query(query_map_id, query_points, max_dist=); .get_eids(); .get_records(); .get_dist()
       -- the nearest edge of the indexed map for every point and its exact distance (rj_nearest_query): Near, sjoin_nearest,
          the join within a distance
+  KNearestLBVH(ctx).Init(n_points, k); .Query(query_map_id, query_points, k=, max_dist=); .get_counts(); .get_eids();
+      .get_records(); .get_dist(); .to_csr()
+      -- the k (1 .. 32) nearest edges of the indexed map for every point, nearest first, as (n, k) arrays with a count per
+         row (rj_knearest_query): the closest-count of Near and Generate Near Table, the candidates of map matching
   WithinLBVH(ctx).Init(n_points, pair_capacity); .Query(query_map_id, query_points, max_dist=, grow=); .Count(...); .get_offsets();
       .get_eids(); .get_records(); .get_dist(); .to_csr(); .counts()
       -- every edge of the indexed map within max_dist of each point, as a CSR over the points (rj_within_query): dwithin,
@@ -305,7 +309,7 @@ class PIPLBVH:
 
 
 class _DistanceQuery:
-    """What NearestLBVH and WithinLBVH share: the per-row outputs (eid, exact record, distance in double; `rows_`: how many
+    """What NearestLBVH, KNearestLBVH and WithinLBVH share: the per-row outputs (eid, exact record, distance in double; `rows_`: how many
     the last call filled) and the freeing of the device buffers."""
 
     def __init__(self, dctx):
@@ -370,6 +374,70 @@ class NearestLBVH(_DistanceQuery):
 
     def free(self):
         self._free("eids", "records", "dist")
+
+
+class KNearestLBVH(_DistanceQuery):
+    """The k nearest edges of the indexed base map for every query point (rj_knearest_query), mirroring NearestLBVH: (n, k)
+    arrays -- row i holds point i's edges nearest first, equal distances to the smaller eid -- of the eid, the exact record
+    and the distance in double, and the count of every row; the entries of a row behind its count are the miss."""
+
+    def __init__(self, dctx):
+        super().__init__(dctx)
+        self.counts = None
+        self.n_alloc = self.k_alloc = self.k = 0
+
+    def Init(self, n_points, k):
+        self.free()
+        self.n_alloc, self.k_alloc = int(n_points), int(k)
+        assert 1 <= self.k_alloc <= _capi.KNEAREST_MAX_K
+        rows = max(1, self.n_alloc * self.k_alloc)
+        self.counts = self.h.alloc(4 * max(1, self.n_alloc))
+        self.eids = self.h.alloc(4 * rows)
+        self.records = self.h.alloc(_capi.NEAR_DTYPE.itemsize * rows)
+        self.dist = self.h.alloc(8 * rows)
+
+    def Query(self, query_map_id, query_points=None, point_range=None, k=None, max_dist=None, records=True, dist=True):
+        """query_points: int64[n,2] scaled host points, or None for the query map's own vertices, optionally a [begin, end)
+        sub-range (a shard).  k (None: Init's): how many edges per point, at most Init's.  max_dist (scaled units, None:
+        unlimited): only edges within it qualify.  records / dist: whether the call fills them.  Returns the number of
+        points."""
+        k = self.k_alloc if k is None else int(k)
+        assert k <= self.k_alloc
+        md = -1 if max_dist is None else int(max_dist)
+        rec, dst = (self.records if records else None), (self.dist if dist else None)
+        n, _ = _over_points(self, query_map_id, query_points, point_range,
+                            lambda buf, b, n: self.h.knearest_query(1 - query_map_id, query_map_id, buf, b, n, k, self.eids, self.counts, rec, dst, md))
+        self.n, self.k, self.rows_ = n, k, n * k
+        self.has_records, self.has_dist = bool(records), bool(dist)
+        return n
+
+    def get_counts(self):
+        """-> uint32[n]: the valid entries of every row"""
+        return self.counts.to_host(np.uint32, self.n)
+
+    def get_eids(self):
+        return super().get_eids().reshape(self.n, self.k)
+
+    def get_records(self):
+        return super().get_records().reshape(self.n, self.k)
+
+    def get_dist(self):
+        return super().get_dist().reshape(self.n, self.k)
+
+    @staticmethod
+    def exact(records):
+        """(n, k) NEAR_DTYPE rows -> per row [(eid, where, num, den)] as _DistanceQuery.exact gives them"""
+        return [_DistanceQuery.exact(row) for row in records]
+
+    def to_csr(self):
+        """-> (indptr int64[n + 1], eids uint32[sum of the counts]): the valid entries of every row, nearest first"""
+        counts, eids = self.get_counts(), self.get_eids()
+        indptr = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        return indptr, eids[np.arange(self.k)[None, :] < counts[:, None]]
+
+    def free(self):
+        self._free("counts", "eids", "records", "dist")
+        self.n_alloc = self.k_alloc = 0
 
 
 class WithinLBVH(_DistanceQuery):
